@@ -1,6 +1,7 @@
 """bench.py -- training samples/s of the PhysicsVAE hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--phase joint|world] [--config c2|c5]
+                    [--dump-outputs DIR] [--full]
 
 Launched plainly with --gpus N > 1 it starts the N ranks itself (one process per GPU, RCCL over
 xGMI; on a box with fewer GPUs than ranks the ranks share a GPU over gloo -- a functional check
@@ -18,9 +19,16 @@ phase of configs[1] is reported beside it as `world_value` with its own `world_r
 N > 1: data-parallel, 256 rows per GPU (global batch N*256, weak scaling), gradient SUM
 all-reduce over RCCL, replicated Adam.
 
-Timing protocol: W warm-up steps, then R = 3 timed regions of max(K, 200) steps each, every
-region bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over ranks per region;
-`value` / `ms_per_step` are the MEDIAN region (>= 200 steps, median of 3).
+Timing protocol: W warm-up steps, then exactly K timed steps, split into R = min(3, K) consecutive
+regions, every region bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over ranks
+per region; `value` / `ms_per_step` are the MEDIAN region (median of 3; pass K >= 600
+for >= 200 steps per region).  `--dump-outputs DIR` then writes what the last timed step produced
+(its loss terms and the parameters of the stacks it trained) as DIR/<name>.npy.
+
+A plain run does only that and prints the line.  Everything below is measured with `--full` only
+(the other phase, roofline and rocprofv3 passes, the stand-alone gather, the sustained MFMA clock,
+the CPU baseline; at N > 1 the replica check, the comparison with one process and the sweep of
+exchange forms); `--no-extra` / `--no-rocprof` / `--no-cpu-baseline` / `--no-sweep` trim a `--full` run.
 
 `roofline` (dominant kernel of the timed phase): algorithmic flops per launch / average launch
 duration.  Two clocks are reported: HIP events stamped at the kernel's own start / end on the
@@ -100,13 +108,56 @@ def parse_args(argv=None):
     ap.add_argument("--no-autotune", action="store_true",
                     help="N > 1 without --exchange: keep the library's default schedule instead of choosing the exchange form by "
                          "a short calibration before the warm-up")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary-phase, roofline and rocprofv3 passes")
     ap.add_argument("--no-rocprof", action="store_true", help="skip the rocprofv3 child runs (kernel trace + PMC)")
     ap.add_argument("--inner", action="store_true",
                     help="(internal) the child run that rocprofv3 wraps: one timed region of exactly --steps steps "
                          "of --phase, nothing else")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def region_sizes(steps, repeats=REPEATS):
+    """`steps` timed steps as min(repeats, steps) consecutive regions of (nearly) equal length."""
+    n = min(repeats, steps)
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+DUMP_BUDGET_FLOATS = 15 << 20         # 60 MB of float32 over all dumped arrays
+
+
+def dump_outputs(out_dir, eng, nets, loss_buf):
+    """What the last timed step handed its caller: the loss terms it wrote and the parameters of the stacks it trained
+    (float32, DUMP_BUDGET_FLOATS in all).  An array over its share of the budget is dumped as a sample whose indices are
+    the same every run (seeded), so that two builds can be compared entry for entry."""
+    import numpy as np
+    import torch
+    from physicsvae_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_terms": loss_buf}
+    for net in sorted(nets):
+        off, cnt = eng.segments[net]
+        if cnt > 0:
+            arrays["params" + _lib.NET_NAMES[net]] = eng.params[off:off + cnt]
+    share = DUMP_BUDGET_FLOATS // len(arrays)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > share:
+            g = torch.Generator(device="cpu").manual_seed(12345)
+            idx = torch.randperm(t.numel(), generator=g)[:share].sort().values
+            t = t[idx.to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+        written[name] = t.numel()
+    return written
 
 
 # ---------------------------------------------------------------------------------------------
@@ -441,12 +492,12 @@ def main():
             dt = float(t.item())
         return samples, dt
 
-    def timed(name, steps, warmup, repeats):
-        """-> (samples/s, ms/step, last loss, per-region samples/s): `repeats` regions of `steps` steps."""
+    def timed(name, regions, warmup):
+        """-> (samples/s, ms/step, last loss, per-region samples/s): one timed region per entry of `regions` (its steps)."""
         phase, nets = set_phase(name)
         run_steps(phase, nets, warmup, 0)
         rates, mss, start = [], [], warmup
-        for _ in range(repeats):
+        for steps in regions:
             samples, dt = region(phase, nets, steps, start)
             start += steps
             rates.append(samples / dt)
@@ -454,10 +505,11 @@ def main():
         return statistics.median(rates), statistics.median(mss), float(loss_buf[0].item()), rates
 
     if a.inner:                                # the command rocprofv3 wraps: one region, one line, done
-        v, ms, loss, _ = timed(a.phase, a.steps, a.warmup, 1)
+        v, ms, loss, _ = timed(a.phase, [a.steps], a.warmup)
         print(json.dumps({"inner": True, "phase": a.phase, "value": v, "ms_per_step": ms, "last_loss": loss}), flush=True)
         return
 
+    full = a.full
     autotune = None
     if dp.collective and dp.world > 1 and a.exchange is None and not a.no_autotune:
         # The exchange form is chosen by measurement, before the warm-up: every form this build and this machine offer
@@ -467,9 +519,12 @@ def main():
         ph, nets_ = set_phase(a.phase)
         chosen, report = dp.autotune_exchange(eng, lambda n: run_steps(ph, nets_, n, 0))
         autotune = {"chosen": chosen or "library default (no candidate qualified)", "candidates": report}
-    timed_steps = max(a.steps, MIN_TIMED_STEPS)
-    value, ms_per_step, last_loss, rates = timed(a.phase, timed_steps, a.warmup, REPEATS)
-    replicas_ok = dp.replicas_identical(eng) if dp.collective and dp.world > 1 else None
+    sizes = region_sizes(a.steps)
+    value, ms_per_step, last_loss, rates = timed(a.phase, sizes, a.warmup)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, eng, tr.phase()[1], loss_buf)
+    replicas_ok = dp.replicas_identical(eng) if full and dp.collective and dp.world > 1 else None
 
     def reference_steps(K=3):
         """N ranks against ONE process: K optimizer steps of the timed phase from a common state (this run's current
@@ -535,7 +590,7 @@ def main():
         return res
 
     single_ref = None
-    if dp.collective and dp.world > 1:
+    if full and dp.collective and dp.world > 1:
         try:
             single_ref = reference_steps()
         except Exception as exc:                                   # noqa: BLE001
@@ -561,9 +616,8 @@ def main():
     out = {
         "metric": METRIC,
         "value": value, "unit": "samples/s", "n_gpus": a.gpus,
-        # steps = what `ms_per_step` / `value` were timed over: ONE region of that many optimizer steps (the median of
-        # `timing.regions` such regions); --steps below MIN_TIMED_STEPS is raised to it (`steps_requested` echoes the flag)
-        "steps": timed_steps, "steps_requested": a.steps, "warmup": a.warmup,
+        # steps = the optimizer steps timed (--steps), in `timing.regions` regions; `value` / `ms_per_step` = the median region
+        "steps": a.steps, "steps_requested": a.steps, "warmup": a.warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s, batch %d/GPU, TE/MD/WM 4x1024, %s phase" % (workload, a.batch, a.phase),
@@ -573,8 +627,9 @@ def main():
                    # the previous step's last launch); "direct" = PVAE_DIRECT=1, the first layers read the demonstration set
                    # in place (bit-identical, slower at this size: docs/experiments.md, round 5)
                    "first_layers": "direct" if os.environ.get("PVAE_DIRECT", "0") not in ("", "0") else "staged"},
-        "timing": {"timed_steps_per_region": timed_steps, "regions": REPEATS, "statistic": "median",
+        "timing": {"timed_steps_per_region": sizes, "regions": len(sizes), "statistic": "median",
                    "region_values": rates},
+        "full": full, "dumped_outputs": dumped,
         "rccl_ranks": comm_ranks, "rccl_rank": comm_rank,
         "p2p_ranks": eng.p2p_status(sync=False)[1],
         "exchange_mode": a.exchange or (autotune["chosen"] if autotune else "default"),
@@ -585,12 +640,13 @@ def main():
     }
     # context for every fraction below: the clock the chip sustains under fp32-MFMA load on THESE weights
     ghz, peak_now = C.c_double(), C.c_double()
-    scratch = torch.zeros(1024, dtype=torch.float32, device=dev)
-    _lib.check(lib.pvae_mfma_clock_probe(eng.params.data_ptr(), eng.params.numel(), scratch.data_ptr(), C.byref(ghz),
-                                         C.byref(peak_now), torch.cuda.current_stream().cuda_stream), "clock probe")
-    out["mfma_clock_under_load"] = {"ghz": ghz.value, "fp32_mfma_peak_at_that_clock_tflops": peak_now.value,
-                                    "note": "all SIMDs issuing v_mfma_f32_16x16x4_f32 back to back on the parameter "
-                                            "arena's values; roofline.peak stays the 2.4 GHz spec figure"}
+    if full:
+        scratch = torch.zeros(1024, dtype=torch.float32, device=dev)
+        _lib.check(lib.pvae_mfma_clock_probe(eng.params.data_ptr(), eng.params.numel(), scratch.data_ptr(), C.byref(ghz),
+                                             C.byref(peak_now), torch.cuda.current_stream().cuda_stream), "clock probe")
+        out["mfma_clock_under_load"] = {"ghz": ghz.value, "fp32_mfma_peak_at_that_clock_tflops": peak_now.value,
+                                        "note": "all SIMDs issuing v_mfma_f32_16x16x4_f32 back to back on the parameter "
+                                                "arena's values; roofline.peak stays the 2.4 GHz spec figure"}
     fl_world, fl_joint = algorithmic_flops_per_sample(Db, Da, Z, W, D)
     fl = {"world": fl_world, "joint": fl_joint}
     out["step_mfma_frac"] = value / a.gpus * fl[a.phase] / (PEAK_F32_MFMA_TFLOPS * 1e12)
@@ -659,9 +715,9 @@ def main():
         kernels["gemm_time_share_of_step"] = sum(v["total_ms"] for v in cats.values()) / n_prof / ms_step
         return roof, kernels, coll
 
-    if not a.no_extra:
+    if full and not a.no_extra:
         other = "joint" if a.phase == "world" else "world"
-        v2, ms2, _, _ = timed(other, MIN_TIMED_STEPS, max(a.warmup // 2, 5), REPEATS)
+        v2, ms2, _, _ = timed(other, [MIN_TIMED_STEPS] * REPEATS, max(a.warmup // 2, 5))
         out[other + "_value"] = v2
         out[other + "_ms_per_step"] = ms2
         out[other + "_step_mfma_frac"] = v2 / a.gpus * fl[other] / (PEAK_F32_MFMA_TFLOPS * 1e12)
@@ -688,7 +744,7 @@ def main():
         elif dp.collective:
             out["allreduce_us_per_step"] = None                   # torch.distributed transport: not instrumented
 
-    if not a.no_extra:
+    if full and not a.no_extra:
         # the minibatch gather on its own (HBM-bound by nature; SURVEY.md 8d: (2 Db + Da) * 4 bytes read and the
         # same written per sample).  In the training step it rides in the last launch (prefetch), so this
         # stand-alone launch only ever runs for the first minibatch of a loader: reported for the roofline.
@@ -745,7 +801,7 @@ def main():
         except Exception as exc:                                   # noqa: BLE001
             out["gather_roofline"]["bandwidth_bound_case"] = {"error": str(exc)[:200]}
 
-    if dp.collective and not a.no_extra and not a.no_sweep:
+    if full and dp.collective and not a.no_extra and not a.no_sweep:
         # Every exchange form this build has, timed back to back in THIS run (one region each), so that one multi-GPU
         # lease yields the whole comparison: RCCL all-reduce in line / bucketed + overlapped / RCCL reduce-scatter +
         # sharded Adam + all-gather / the peer-mapped all-pairs exchange, and the step with the exchange switched off
@@ -787,7 +843,7 @@ def main():
                 torch.cuda.synchronize()
                 lib.pvae_profile_enable(0)
                 coll = read_cats().get(4)
-                v, ms, _, _ = timed(a.phase, MIN_TIMED_STEPS, 5, 1)
+                v, ms, _, _ = timed(a.phase, [MIN_TIMED_STEPS], 5)
                 entry = {"value": v, "ms_per_step": ms}
                 if coll:
                     entry["exchange_launches_per_step"] = coll["launches"] / 40
@@ -808,7 +864,7 @@ def main():
         if base:
             out["step_without_exchange_us"] = base * 1e3
             out["exchange_exposed_us_per_step"] = (ms_per_step - base) * 1e3
-    if rank == 0 and a.gpus == 1 and not a.no_cpu_baseline:
+    if full and rank == 0 and a.gpus == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a, sd, Db, Da, Z, W, D, a.phase, synth_demo)
     if dist.is_initialized():
         torch.cuda.synchronize()

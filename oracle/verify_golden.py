@@ -3,8 +3,8 @@
 Test infrastructure, dev container only (it imports /root/reference through oracle/gen_golden.py).  Regenerates every
 fixture of tests/golden/ into a scratch directory with the committed generator and compares it with the committed file
 array by array, byte for byte (names, dtypes, shapes, contents).  A generator change that silently alters a capture, or
-a fixture that was edited by hand, shows up here.  `tests/test_oracle_golden.py::test_fixtures_regenerate_byte_for_byte`
-runs it where /root/reference exists and skips elsewhere (the GPU box has no reference).
+a fixture that was edited by hand, shows up here.  Run it by hand where the reference is available: the test suite
+runs without the reference and does not call it.
 
     python oracle/verify_golden.py [--only NAME ...] [--jobs N]
 """

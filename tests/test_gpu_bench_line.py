@@ -31,10 +31,10 @@ def test_bench_plain_two_ranks_self_launch():
     """`python bench.py --gpus 2`, launched plainly, starts its two ranks itself and prints ONE line.
     On a 1-GPU box the ranks share the device and exchange over gloo (RCCL refuses two ranks on one
     device): same sharding / reduction / Adam path, flagged in the line."""
-    d = _bench("--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-rocprof")
-    assert d["n_gpus"] == 2 and d["steps_requested"] == 20 and d["steps"] == d["timing"]["timed_steps_per_region"] and d["warmup"] == 5
+    d = _bench("--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-rocprof")
+    assert d["n_gpus"] == 2 and d["steps_requested"] == 20 and d["steps"] == 20 and d["warmup"] == 5
     assert d["config"]["global_batch"] == 512 and d["config"]["parallelism"] == "dp2"
-    assert d["timing"]["timed_steps_per_region"] >= 200 and d["timing"]["regions"] == 3
+    assert sum(d["timing"]["timed_steps_per_region"]) == 20 and d["timing"]["regions"] == 3
     assert d["value"] > 0 and np.isfinite(d["last_loss"])
     if torch.cuda.device_count() < 2:
         assert d["ranks_share_a_gpu"] is True and d["rccl_ranks"] == 0
@@ -69,13 +69,13 @@ def test_bench_under_the_launcher_command_of_the_scaling_run():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29633", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "10", "--warmup", "3"], cwd=ROOT, env=env,
+                        "--gpus", "2", "--steps", "10", "--warmup", "3", "--full"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 2 and d["steps_requested"] == 10 and d["steps"] >= 200 and d["warmup"] == 3 and d["scaling"] == "weak"
+    assert d["n_gpus"] == 2 and d["steps_requested"] == 10 and d["steps"] == 10 and d["warmup"] == 3 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 512 and d["value"] > 0 and np.isfinite(d["last_loss"])
     assert d["replicas_identical"] is True and d["matches_single_process"] is True, d.get("single_process_reference")
     assert d["ranks_share_a_gpu"] is (torch.cuda.device_count() < 2)
@@ -83,7 +83,7 @@ def test_bench_under_the_launcher_command_of_the_scaling_run():
 
 
 def test_bench_plain_single_gpu_line():
-    d = _bench("--steps", "20", "--warmup", "5", "--no-rocprof")
+    d = _bench("--steps", "20", "--warmup", "5", "--full", "--no-rocprof")
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 0 and d["config"]["phase"] == "joint"
     assert d["metric"].startswith("train samples/sec (world-model+VAE step)")
     for key in ("roofline", "world_roofline", "cpu_baseline", "world_value"):
@@ -96,3 +96,28 @@ def test_bench_plain_single_gpu_line():
     assert cb["epochs_timed"] >= 1 and cb["warmup_epochs"] == 1 and cb["samples_per_epoch"] == 9990
     assert cb["cores"] == cb["threads_best"] and cb["physical_cores"] and cb["physical_cores"] <= cb["host_cpus"]
     assert len(d["timing"]["region_values"]) == 3
+
+
+def test_bench_plain_line_times_exactly_the_steps_asked_and_dumps_outputs(tmp_path):
+    """The plain line: exactly --steps timed steps (median of three regions), nothing measured beside the headline, and
+    --dump-outputs writes what the last timed step computed -- the same numbers in two runs with the same arguments."""
+    runs = []
+    for tag in ("a", "b"):
+        d = _bench("--steps", "30", "--warmup", "5", "--dump-outputs", str(tmp_path / tag))
+        assert d["n_gpus"] == 1 and d["steps"] == 30 and d["steps_requested"] == 30 and d["warmup"] == 5
+        assert d["timing"]["timed_steps_per_region"] == [10, 10, 10] and len(d["timing"]["region_values"]) == 3
+        assert d["metric"].startswith("train samples/sec (world-model+VAE step)") and d["unit"] == "samples/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["full"] is False
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(256 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+        for key in ("roofline", "world_value", "cpu_baseline", "mfma_clock_under_load", "gather_roofline"):
+            assert key not in d, key
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == sorted(n + ".npy" for n in d["dumped_outputs"]), files
+        assert {"loss_terms.npy", "params_task_encoder.npy", "params_motor_decoder.npy"} <= set(files)
+        arrays = {f: np.load(tmp_path / tag / f) for f in files}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrays.values())
+        assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+        assert arrays["loss_terms.npy"][0] == pytest.approx(d["last_loss"], rel=1e-6)
+        runs.append(arrays)
+    for f in runs[0]:
+        np.testing.assert_array_equal(runs[0][f], runs[1][f], err_msg=f)

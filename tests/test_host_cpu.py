@@ -1067,3 +1067,20 @@ def test_dp_buckets_follow_the_backward_plan():
                                               (0, 0, 300, 7)]
     assert TM.dp_buckets([(0, 500, 100), (0, 100, 100)]) == [(0, 500, 600, 0), (0, 100, 200, 1)]      # a gap closes too
     assert TM.dp_buckets([]) == [] and TM.dp_buckets([(2, 0, 0)]) == []
+
+
+def test_bench_arguments_and_timed_regions():
+    """bench.py's command line: --steps is the number of timed steps (split into at most three regions), a plain run
+    measures the headline only (--full off by default) and dumps nothing unless asked."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "20", "--warmup", "5"])
+    assert a.steps == 20 and a.warmup == 5 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    for k in (1, 2, 3, 20, 400, 1001):
+        sizes = bench.region_sizes(k)
+        assert sum(sizes) == k and len(sizes) == min(3, k) and max(sizes) - min(sizes) <= 1

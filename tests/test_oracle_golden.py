@@ -514,21 +514,3 @@ def test_helper_training_restatement_matches_reference(golden, name):
     assert steps["_motor_decoder_helper._model.0._model.0.weight"] == nb * (n_epochs if L > 1 else n_epochs - m_world)
     assert steps["_motor_decoder._model.0._model.0.weight"] == nb * (n_epochs - m_world)
 
-
-def test_fixtures_regenerate_byte_for_byte():
-    """The pin checks itself: the committed generator, run against the reference, writes the committed fixtures byte for
-    byte (oracle/verify_golden.py).  Dev container only -- the GPU box has no reference, the test skips there.  The
-    `*tiny*` fixtures (21 of 36, 20 s) always; all of them (5 min on 4 cores, profiles/r06_verify_golden.txt) with
-    PVAE_VERIFY_GOLDEN_ALL=1."""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    import verify_golden as V
-    if not os.path.isdir(V.REF):
-        pytest.skip("no reference at %s" % V.REF)
-    names = V.fixture_names()
-    if os.environ.get("PVAE_VERIFY_GOLDEN_ALL") != "1":
-        names = [n for n in names if "tiny" in n]
-    assert len(names) >= 20
-    bad = V.verify(names)
-    assert not bad, bad

@@ -2,7 +2,7 @@
 # A/B of runtime switches: bash tools/ab_env.sh "PVAE_WGRAD32=0" "PVAE_KROT=1" ...  ("" = defaults)
 for v in "" "$@" ""; do
   echo "== ${v:-defaults}"
-  env $v python bench.py --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 2>/dev/null | python -c "
+  env $v python bench.py --full --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 def row(k):

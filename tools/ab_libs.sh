@@ -7,7 +7,7 @@ for v in "" "$@" ""; do
   if [ -n "$AB_TEST" ]; then
     PVAE_LIB_PATH=${v:+$PWD/$v} python -m pytest tests/test_gpu_parity.py -x -q -k "gemm or single_batch or odd_minibatch or fused_adam" 2>&1 | tail -2
   fi
-  PVAE_LIB_PATH=${v:+$PWD/$v} python bench.py --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 2>/dev/null | python -c "
+  PVAE_LIB_PATH=${v:+$PWD/$v} python bench.py --full --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 def row(k):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # joint / world step time and per-category launch averages of one library: bash tools/bench_quick.sh [bench flags]
-python bench.py --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 "$@" 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-rocprof --steps 400 --warmup 40 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 def row(k):

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$ROOT/gpurun_out; mkdir -p "$O"
 cd "$ROOT"
 bash tools/profile_round.sh $TAG > "$O/${TAG}_profile_round.log" 2>&1
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 8 \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 8 --full \
     --steps 200 --warmup 20 > "$O/${TAG}_bench_n8_shared_gpu_torchrun.raw" 2> "$O/${TAG}_bench_n8.err"
 grep '^{' "$O/${TAG}_bench_n8_shared_gpu_torchrun.raw" | tail -1 > "$O/${TAG}_bench_n8_shared_gpu_torchrun.json"
 # staged (default) against direct first layers (PVAE_DIRECT=1), alternating in this lease (docs/experiments.md: SURVEY K5)

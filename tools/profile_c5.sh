@@ -12,6 +12,6 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 --kernel-trace --output-format csv -d "${P}_lds" -o l -- $CMD > /dev/null 2> "${P}_lds.err"
 python $ROOT/tools/step_trace.py "${P}_trace" > "${P}_step.txt" 2>&1
 cd "$ROOT"
-python bench.py --config c5 --no-cpu-baseline > "$O/r02_bench_c5.json" 2> "$O/r02_bench_c5.err"
+python bench.py --full --config c5 --no-cpu-baseline > "$O/r02_bench_c5.json" 2> "$O/r02_bench_c5.err"
 find "$O" -name '*.db' -delete
 tail -c 300 "$O/r02_bench_c5.json"
