@@ -544,6 +544,32 @@ int pvae_net_forward(pvae_ctx* ctx, int net, const float* in, int32_t rows, floa
 int pvae_reparam(pvae_ctx* ctx, const float* mu_logvar, int32_t rows, const float* eps, int noise,
                  uint64_t rng_seed, uint64_t rng_offset, float* z_out, void* stream);
 
+/* ---- backward of the stand-alone stages (torch autograd through the module: physicsvae_amd/autograd.py) ---------
+ * What PPO's loss.backward() does to PhysicsVAE.forward / forward_encoder / forward_decoder / forward_world
+ * (rmt:743-771 -> rmt:773-853) when the stacks are learnable (rmt:473, 488), on the tile kernels of the trainer.
+ *
+ * Backward of one arena stack from a caller-supplied output gradient (autograd of rmt:773-853).
+ * in[rows][n_in] dense (the same input pvae_net_forward takes), dy[rows][n_out] dense = dL/d(output AFTER the
+ * output activation: the helper's tanh).  dx[rows][n_in] (NULL: not wanted).  grad: pvae_net_segment(net)
+ * `count` floats, element 0 = arena offset `offset`, same layout as the arena (NULL: no parameter gradient,
+ * input-gradient launches only).  accumulate: 0 store, 1 add into grad.  1 <= rows <= max_batch.
+ * Recompute, not saved activations: `in` is padded into the stack's panels and the forward runs again (the launches of
+ * pvae_net_forward: the same bits), then the trainer's per-layer backward plan runs with a gradient store (or a
+ * read-add-write, EpiGradAccum: each output tile summed by one workgroup in a fixed order, so equal operands give equal
+ * bits) and no Adam.  The extra forward is about one third of forward + backward: the price of a forward under
+ * autograd that costs nothing extra when no backward follows.  The pad rows of the panels are zeroed or kept out of
+ * every contraction, so what earlier calls left there never reaches a gradient.  Like pvae_net_forward it overwrites
+ * the staging panels (the HIP trainer gathers again).  Weight-gradient launches count in pvae_profile_read
+ * categories 1-3. */
+int pvae_net_backward(pvae_ctx* ctx, int net, const float* in, int32_t rows, const float* dy, float* dx,
+                      float* grad, int32_t accumulate, void* stream);
+/* Backward of pvae_reparam (rmt:734-740, 795-816 per prior kind): d_mu_logvar from dz, the draws the forward used
+ * (eps_used, as the forward left them) and the forward's mu_logvar; noise = 0: z = mu.  No KL term (the caller's loss
+ * owns it).  mu_logvar / d_mu_logvar are [rows][2 Z] ([rows][Z] for PVAE_PRIOR_HYPERSPHERE / PVAE_PRIOR_NONE, where
+ * eps_used is not read), eps_used / dz [rows][Z], all dense. */
+int pvae_reparam_backward(pvae_ctx* ctx, const float* mu_logvar, const float* eps_used, const float* dz,
+                          int32_t rows, int noise, float* d_mu_logvar, void* stream);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

@@ -1,0 +1,234 @@
+"""Torch autograd through the arena stacks: what PPO's `loss.backward()` does to `PhysicsVAE.forward` (rmt:743-771) and the
+stage functions (rmt:773-853) when the task encoder / motor decoder are learnable (rmt:473, 488), on the HIP kernels.
+
+The arena stacks (TE, MD, WM, PR, MH) are views into the engine's flat parameter arena and their forward is a library call,
+so torch cannot differentiate it by itself.  The Functions below give those calls a backward built from
+`pvae_net_backward` (recompute the stack's forward, then the trainer's per-layer backward plan) and `pvae_reparam_backward`.
+Their forwards are the very calls the module makes without autograd, so values are the same bits either way.
+
+  HipNet      one stack: (x, *parameter views of the stack) -> output
+  HipReparam  the sampler: mu_logvar -> z, with the draws the forward used kept for the backward
+  HipPolicy   `forward()` as ONE `pvae_infer_logits` call: (obs, *TE, *MD, *MH, *WM) -> (a_hat, z, mu_logvar, s2)
+
+Every backward runs in chunks of at most `max_batch` rows, the parameter gradient summed over the chunks into one flat
+buffer per stack (accumulate = 1 after the first chunk) and handed back as views shaped like the parameters.  The
+parameter views, the inputs and the outputs a backward reads are saved with `save_for_backward`, never kept as ctx
+attributes: an output held by its own ctx is a reference cycle through the graph that the garbage collector cannot
+break.  An in-place write between forward and backward -- an optimizer step, `load_state_dict`, a caller recycling its
+observation buffer -- then raises torch's usual error instead of returning gradients taken at other values.  Double
+backward is not offered (`once_differentiable`).
+"""
+import sys
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from ._lib import NET_MD, NET_MH, NET_TE, NET_WM
+
+
+def chunks(rows, max_batch):
+    """[(lo, hi)] spans of at most `max_batch` rows covering [0, rows)."""
+    return [(lo, min(lo + max_batch, rows)) for lo in range(0, rows, max_batch)]
+
+
+def stack_params(fc):
+    """The weight / bias views of one FC stack in layer order (AppendLogStd is not part of the arena)."""
+    out = []
+    for m in fc._model:
+        lin = getattr(m, "_model", None)
+        if isinstance(lin, torch.nn.Sequential) and isinstance(lin[0], torch.nn.Linear):
+            out += [lin[0].weight, lin[0].bias]
+    return out
+
+
+def grad_views(eng, net, gbuf):
+    """`gbuf` (a flat gradient of stack `net`'s arena segment) as views shaped like the stack's parameters, in the order
+    of `stack_params`: W[:n_out, col0:col0 + n_in] of every padded block, then its bias."""
+    off0 = eng.segments[net][0]
+    out = []
+    for info in eng.layers:
+        if info["net"] != net:
+            continue
+        w0, b0 = info["w_offset"] - off0, info["b_offset"] - off0
+        blk = gbuf[w0: w0 + info["n_out_pad"] * info["ld"]].view(info["n_out_pad"], info["ld"])
+        out.append(blk[: info["n_out"], info["col0"]: info["col0"] + info["n_in"]])
+        out.append(gbuf[b0: b0 + info["n_out"]])
+    return out
+
+
+def net_forward(eng, net, x):
+    """`engine.net_forward` over any number of rows (chunks of at most `max_batch`)."""
+    x = x.reshape(x.shape[0], -1)
+    if x.shape[0] <= eng.max_batch:
+        return eng.net_forward(net, x)
+    return torch.cat([eng.net_forward(net, x[lo:hi]) for lo, hi in chunks(x.shape[0], eng.max_batch)])
+
+
+def net_backward(eng, net, x, dy, want_dx, want_grad):
+    """(dx | None, flat parameter gradient of the stack | None) over any number of rows."""
+    gbuf = torch.empty(eng.segments[net][1], dtype=torch.float32, device=eng.device) if want_grad else None
+    if not (want_dx or want_grad):
+        return None, None
+    dxs = [eng.net_backward(net, x[lo:hi], dy[lo:hi], want_dx, gbuf, accumulate=i > 0)
+           for i, (lo, hi) in enumerate(chunks(x.shape[0], eng.max_batch))]
+    dx = (dxs[0] if len(dxs) == 1 else torch.cat(dxs)) if want_dx else None
+    return dx, gbuf
+
+
+def _param_grads(eng, net, gbuf, needs):
+    if gbuf is None:
+        return [None] * len(needs)
+    return [g if n else None for g, n in zip(grad_views(eng, net, gbuf), needs)]
+
+
+class HipNet(torch.autograd.Function):
+    """One arena stack: `HipNet.apply(engine, net, x, *stack_params(fc))` -> output [rows, n_out] (after the output
+    activation: the helper's tanh).  Forward = `engine.net_forward` (chunked); backward = `engine.net_backward` with
+    grad = None when no parameter of the stack wants a gradient (frozen stack: input gradient only) and dx = None when
+    `x` does not."""
+
+    @staticmethod
+    def forward(ctx, eng, net, x, *params):
+        ctx.eng, ctx.net, ctx.x_shape, ctx.x_dtype = eng, net, x.shape, x.dtype
+        ctx.save_for_backward(x, *params)
+        return net_forward(eng, net, _dense(eng, x))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x = ctx.saved_tensors[0]                 # (raises if x or a parameter was written in place since the forward)
+        needs = ctx.needs_input_grad[3:]
+        dx, gbuf = net_backward(ctx.eng, ctx.net, _dense(ctx.eng, x), gy.float().contiguous(), ctx.needs_input_grad[2],
+                                any(needs))
+        if dx is not None:
+            dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
+        return (None, None, dx) + tuple(_param_grads(ctx.eng, ctx.net, gbuf, needs))
+
+
+def _dense(eng, x):
+    """x as the library reads it: [rows, features] fp32, dense, on the engine's device (x itself when it already is)."""
+    return x.reshape(x.shape[0], -1).to(eng.device, torch.float32).contiguous()
+
+
+def used_draws(eng, rows, eps, noise):
+    """The standard-normal draws a sampler call of `rows` rows just used (N(mu, s^2) kinds with noise on): the caller's
+    `eps`, or the Philox draws the library left in its eps panel -- a copy, taken in stream order behind that call."""
+    if not noise or eng.arch.prior in ("hypersphere_uniform", False):
+        return None
+    if eps is not None:
+        return eps.to(eng.device, torch.float32).reshape(rows, -1).clone()
+    return eng.panel("eps")[:rows].clone()
+
+
+class HipReparam(torch.autograd.Function):
+    """The sampler (rmt:734-740; per prior kind rmt:795-816): `HipReparam.apply(engine, noise, seed, offset, eps,
+    mu_logvar)` -> z [rows, Z], rows <= max_batch.  Forward = `engine.reparam`; backward = `engine.reparam_backward` on
+    the draws this forward used."""
+
+    @staticmethod
+    def forward(ctx, eng, noise, seed, offset, eps, mu_logvar):
+        z = eng.reparam(_dense(eng, mu_logvar), eps=eps, noise=noise, seed=seed, offset=offset)
+        ctx.eng, ctx.noise, ctx.dtype = eng, noise, mu_logvar.dtype
+        ctx.used = used_draws(eng, mu_logvar.shape[0], eps, noise)     # (a private copy: no cycle, nobody else writes it)
+        ctx.save_for_backward(mu_logvar)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz):
+        ml = _dense(ctx.eng, ctx.saved_tensors[0])
+        d = ctx.eng.reparam_backward(ml, ctx.used, dz.float().contiguous(), noise=ctx.noise)
+        return None, None, None, None, None, d.to(ctx.dtype)
+
+
+_served_warned = [False]
+
+
+def warn_served_once():
+    """The rollout server answers a graph-building call: say once that the served path is inference-only."""
+    if not _served_warned[0]:
+        _served_warned[0] = True
+        print("physicsvae_amd: forward() served by the rollout server returns no autograd graph (inference only); "
+              "pass the observation on the GPU, or stop the server, to train through forward()", file=sys.stderr)
+
+
+class HipPolicy(torch.autograd.Function):
+    """`PhysicsVAE.forward` (rmt:742-771) under autograd, keeping its one library call (`pvae_infer_logits`, so the action
+    is the same bits as without a graph): `HipPolicy.apply(model, obs, eps, noise, offset, want_s2, counts, *params)` with
+    params = TE | MD | MH | WM views (`counts` = how many of each) -> (a_hat [rows, Da], z [rows, Z], mu_logvar
+    [rows, n_out of TE], s2 [rows, Db] or None without `want_s2`), rows <= max_batch.
+    Backward, from the saved observation, [s_body | z], [s_body | a_hat], mu_logvar and the draws: WM (when s2 has a
+    gradient; its input gradient joins the action's), the helper (tanh seed, dy = range * d a_hat) and MD on [s_body | z],
+    then the sampler, then TE."""
+
+    @staticmethod
+    def forward(ctx, model, obs, eps, noise, offset, want_s2, counts, *params):
+        eng = model.engine
+        Da, Z = eng.arch.Da, eng.arch.Z
+        x = _dense(eng, obs)
+        rows = x.shape[0]
+        logits, s2, z = eng.infer_logits(x, model.__dict__["_als"].on_device(eng.device), eps=eps if noise else None,
+                                         noise=noise, seed=model._rng_seed, offset=offset, want_s2=want_s2)
+        if eng.arch.te_out == 2 * Z:
+            ml = torch.cat([eng.read("mu", rows), eng.read("logvar", rows)], dim=1)
+        else:                                    # (unit-sphere / no-prior encoders: the raw encoder output e)
+            ml = eng.read("mu", rows)
+        a = logits[:, :Da].contiguous()
+        # (nothing on ctx refers to the model or to an output: the module keeps this forward's outputs in its `_cur_*` state)
+        ctx.eng, ctx.mh_range = eng, float(model._motor_decoder_helper_range or 0.0)
+        ctx.noise, ctx.counts, ctx.obs_dtype = noise, counts, obs.dtype
+        ctx.used = used_draws(eng, rows, eps, noise)                   # (a private copy: no cycle, nobody else writes it)
+        ctx.save_for_backward(obs, a, z, ml, *params)
+        return a, z, ml, s2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_a, g_z, g_ml, g_s2):
+        obs_in, a, z, ml = ctx.saved_tensors[:4]     # (raises if any of them or a parameter was written in place since)
+        eng = ctx.eng
+        Db, Da, Z = eng.arch.Db, eng.arch.Da, eng.arch.Z
+        n_te, n_md, n_mh, n_wm = ctx.counts
+        needs = ctx.needs_input_grad[7:]
+        need_te, need_md = needs[:n_te], needs[n_te: n_te + n_md]
+        need_mh, need_wm = needs[n_te + n_md: n_te + n_md + n_mh], needs[n_te + n_md + n_mh:]
+        want_obs = ctx.needs_input_grad[1]
+        obs = _dense(eng, obs_in)
+        s_body = obs[:, :Db]
+        d_obs = torch.zeros_like(obs) if want_obs else None
+        g_wm = g_mh = g_md = g_te = None
+        if g_s2 is not None and (any(need_wm) or any(need_md) or any(need_mh) or any(need_te) or want_obs):
+            x_wm = torch.cat([s_body, a], dim=1)
+            dx, g_wm = net_backward(eng, NET_WM, x_wm, g_s2.float().contiguous(), True, any(need_wm))
+            g_a = dx[:, Db: Db + Da] if g_a is None else g_a + dx[:, Db: Db + Da]
+            if want_obs:
+                d_obs[:, :Db] += dx[:, :Db]
+        want_z = any(need_te) or want_obs               # (z feeds nothing but the encoder's gradient and the observation's)
+        dz = g_z.float() if g_z is not None else None
+        if g_a is not None:
+            g_a = g_a.float().contiguous()
+            md_in = torch.cat([s_body, z], dim=1)
+            stacks = [(NET_MD, g_a, need_md)]
+            if n_mh:
+                stacks.append((NET_MH, g_a * ctx.mh_range, need_mh))
+            grads = {}
+            for net, dy, need in stacks:
+                dx, grads[net] = net_backward(eng, net, md_in, dy, want_z, any(need))
+                if dx is not None:
+                    dz = dx[:, Db: Db + Z] if dz is None else dz + dx[:, Db: Db + Z]
+                    if want_obs:
+                        d_obs[:, :Db] += dx[:, :Db]
+            g_md, g_mh = grads.get(NET_MD), grads.get(NET_MH)
+        d_ml = g_ml.float() if g_ml is not None else None
+        if dz is not None and want_z:
+            d = torch.cat([eng.reparam_backward(ml[lo:hi], ctx.used[lo:hi] if ctx.used is not None else None,
+                                                dz[lo:hi].contiguous(), noise=ctx.noise)
+                           for lo, hi in chunks(dz.shape[0], eng.max_batch)])
+            d_ml = d if d_ml is None else d_ml + d
+        if d_ml is not None and want_z:
+            dx, g_te = net_backward(eng, NET_TE, obs, d_ml.contiguous(), want_obs, any(need_te))
+            if want_obs:
+                d_obs += dx
+        out = (_param_grads(eng, NET_TE, g_te, need_te) + _param_grads(eng, NET_MD, g_md, need_md)
+               + _param_grads(eng, NET_MH, g_mh, need_mh) + _param_grads(eng, NET_WM, g_wm, need_wm))
+        d_obs = d_obs.view(obs_in.shape).to(ctx.obs_dtype) if d_obs is not None else None
+        return (None, d_obs, None, None, None, None, None) + tuple(out)

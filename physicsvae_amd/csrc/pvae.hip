@@ -406,6 +406,73 @@ pad_copy_kernel(const float* __restrict__ src, int n, int rows, float* __restric
     }
 }
 
+// Output gradient of one stack from a caller's dy (pvae_net_backward; autograd of rmt:773-853): dz[r][c] = dy[r][c] *
+// act'(y[r][c]) with y the recomputed output panel (act 0: linear output layer, the derivative is 1; the helper's tanh:
+// 1 - y^2).  Written over ALL of [rows_pad][ld]: pad rows and pad columns get zeros, so that nothing an earlier call
+// left in them reaches a contraction.
+__global__ void __launch_bounds__(256)
+net_seed_kernel(const float* __restrict__ dy, int n, int rows, const float* __restrict__ y, int ld, int rows_pad, int act,
+                float* __restrict__ dz) {
+    const int total = rows_pad * ld;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / ld, c = idx - r * ld;
+        float g = 0.f;
+        if (r < rows && c < n) {
+            g = dy[(size_t)r * n + c];
+            if (act) g *= act_grad(y[idx], act);
+        }
+        dz[idx] = g;
+    }
+}
+
+// Rows [r0, r1) of up to PVAE_MAX_HIDDEN + 1 panels set to zero: the layer outputs of a <= 4-row forward, whose GEMV
+// path writes the live rows only (pvae_net_backward contracts over whole 32-row tiles; a stale NaN in a pad row would
+// meet a zero gradient row there and the product is NaN).
+struct PadRows {
+    float* p[PVAE_MAX_HIDDEN + 1];
+    int ld[PVAE_MAX_HIDDEN + 1];
+    int n, r0, r1;
+};
+__global__ void __launch_bounds__(256)
+zero_pad_rows_kernel(PadRows z) {
+    for (int k = 0; k < z.n; ++k) {
+        const int total = (z.r1 - z.r0) * z.ld[k];
+        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256)
+            z.p[k][(size_t)z.r0 * z.ld[k] + idx] = 0.f;
+    }
+}
+
+// Backward of the sampler on its own (pvae_reparam_backward; autograd of rmt:734-740 and, per prior kind, 795-816), no
+// KL term: dense mu_logvar / d_mu_logvar [rows][ldte], dz / eps_used [rows][Z].  One wave per row.
+//   N(mu, s^2) kinds:   z = mu + eps exp(lv / 2)      dmu = dz, dlv = dz eps exp(lv / 2) / 2  (noise = 0: z = mu, dlv = 0)
+//   hypersphere:        z = e / max(|e|, 1e-12)      de = (dz - z <z, dz>) / max(|e|, 1e-12)
+//   none (False):       z = e                        de = dz
+__global__ void __launch_bounds__(256)
+sampler_bwd_kernel(const float* __restrict__ mu_logvar, int ldte, const float* __restrict__ eps_used,
+                   const float* __restrict__ dz, int rows, int Z, int kind, int noise, float* __restrict__ d_ml) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float* e = mu_logvar + (size_t)r * ldte;
+    const float* g = dz + (size_t)r * Z;
+    float* d = d_ml + (size_t)r * ldte;
+    if (kind == PVAE_PRIOR_HYPERSPHERE) {
+        float e2 = 0.f, eg = 0.f;
+        for (int c = lane; c < Z; c += 64) { e2 += e[c] * e[c]; eg += e[c] * g[c]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { e2 += __shfl_xor(e2, o, 64); eg += __shfl_xor(eg, o, 64); }
+        const float ie = 1.0f / fmaxf(sqrtf(e2), 1e-12f);
+        const float zg = eg * ie;                                  // <z, dz>
+        for (int c = lane; c < Z; c += 64) d[c] = (g[c] - e[c] * ie * zg) * ie;
+    } else if (kind == PVAE_PRIOR_NONE) {
+        for (int c = lane; c < Z; c += 64) d[c] = g[c];
+    } else {
+        for (int c = lane; c < Z; c += 64) {
+            d[c] = g[c];
+            d[Z + c] = noise ? g[c] * eps_used[(size_t)r * Z + c] * 0.5f * expf(0.5f * e[Z + c]) : 0.f;
+        }
+    }
+}
+
 // Evaluation-only finalisation (training folds it into the last weight-gradient launch).
 __global__ void finalize_loss_kernel(LossFinal f) { finalize_loss_wave(f, threadIdx.x); }
 
@@ -849,6 +916,11 @@ static void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool
         e.gb = c->grads + l.b_off;
         return e;
     };
+    auto accum_epi = [=](const Layer& l) {
+        EpiGradAccum e{c->grads + l.w_off, l.ld};
+        e.gb = c->grads + l.b_off;
+        return e;
+    };
     // wgrad of layer i, optionally fused with the dgrad of layer j (j < 0: alone).  In a fused pair
     // that is not the step's last launch the gradient is stored and Adam deferred to workgroups of
     // the next weight-gradient launch (AdamSeg); every launch carries whatever is pending.
@@ -903,7 +975,7 @@ static void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool
             }
             return 0;
         };
-        if (!fused) return go(store_epi(l));
+        if (!fused) return c->grad_accum ? go(accum_epi(l)) : go(store_epi(l));
         if (!defer) return go(adam_epi(l));
         const int rc = go(store_epi(l));
         if (rc == 0) {
@@ -930,7 +1002,8 @@ static void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool
             if (carry) c->next_carried = true;
             return 0;
         };
-        const int rc = fused ? go(adam_epi(l1), adam_epi(l0)) : go(store_epi(l1), store_epi(l0));
+        const int rc = fused ? go(adam_epi(l1), adam_epi(l0))
+                             : (c->grad_accum ? go(accum_epi(l1), accum_epi(l0)) : go(store_epi(l1), store_epi(l0)));
         g_prof.end(pw2, st);
         return rc;
     };
@@ -955,7 +1028,7 @@ static void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool
             if (carry) c->next_carried = true;
             return 0;
         };
-        const int rc = fused ? go(adam_epi(l0)) : go(store_epi(l0));
+        const int rc = fused ? go(adam_epi(l0)) : (c->grad_accum ? go(accum_epi(l0)) : go(store_epi(l0)));
         g_prof.end(pw, st);
         return rc;
     };
@@ -2740,6 +2813,85 @@ int pvae_reparam(pvae_ctx* c, const float* mu_logvar, int32_t rows, const float*
     return launch_sampler(c, mu_logvar, ldte, eps, c->ws + c->W.eps, c->ws + c->W.net[PVAE_NET_MD].in, ld_md, rows, rows,
                           noise ? 1 : 0, (unsigned long long)rng_seed, (unsigned long long)rng_offset, (float*)nullptr,
                           z_out, (const float*)nullptr, 0, st);
+}
+
+int pvae_net_backward(pvae_ctx* c, int net, const float* in, int32_t rows, const float* dy, float* dx, float* grad,
+                      int32_t accumulate, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (net < 0 || net >= PVAE_NUM_NETS || c->L.net[net].layers.empty()) return fail(-1, "bad net id %d (or no such stack)", net);
+    if (!in || !dy) return fail(-1, "in / dy is null");
+    if (!dx && !grad) return fail(-1, "neither dx nor grad: nothing to compute");
+    if (rows < 1 || rows > c->L.cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, c->L.cfg.max_batch);
+    hipStream_t st = (hipStream_t)stream;
+    const NetLayout& N = c->L.net[net];
+    const NetWork& w = c->W.net[net];
+    const Layer& last = N.layers.back();
+    const int rows_pad = pad32(rows), ld = N.layers[0].ld;
+    // recompute: the very launches of pvae_net_forward, so the panels hold what that forward computed
+    int grid = (rows_pad * ld + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(pad_copy_kernel, dim3(grid), dim3(256), 0, st, in, N.n_in, rows, c->ws + w.in, ld, rows_pad,
+                       N.layers[0].col0, N.layers[0].n_in);
+    HIP_TRY(hipGetLastError());
+    c->staged_rows = 0;     // the training panels are no longer a coherent batch
+    c->staged_rows_f = rows;
+    if (rows <= 4 && rows < rows_pad) {       // GEMV path: the pad rows of the layer outputs are not written
+        PadRows z{};
+        z.n = (int)N.layers.size(); z.r0 = rows; z.r1 = rows_pad;
+        for (int i = 0; i < z.n; ++i) { z.p[i] = c->ws + w.act[i]; z.ld[i] = N.layers[i].n_out_pad; }
+        hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(8), dim3(256), 0, st, z);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = forward_net(c, net, rows_pad, st))) return rc;
+    grid = (rows_pad * last.n_out_pad + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(net_seed_kernel, dim3(grid), dim3(256), 0, st, dy, N.n_out, rows, c->ws + w.act.back(),
+                       last.n_out_pad, rows_pad, last.act, c->ws + w.dz.back());
+    HIP_TRY(hipGetLastError());
+    // the trainer's per-layer plan, gradient store (or accumulate) instead of Adam, into the caller's buffer: a bound
+    // arena, a pending update and a direct step of the trainer are set aside and put back untouched
+    float* const grads_keep = c->grads;
+    const AdamSeg pending_keep = c->pending_adam, held_keep = c->held_adam;
+    const bool dx_keep = c->dx.on;
+    c->grads = grad ? grad - N.off : grads_keep;
+    c->grad_accum = accumulate != 0;
+    c->pending_adam = AdamSeg();
+    c->held_adam = AdamSeg();
+    c->dx.on = false;
+    pvae_step_params sp;
+    memset(&sp, 0, sizeof(sp));
+    Plan plan;
+    plan_backward_net(c, net, rows_pad, grad != nullptr, dx != nullptr, &sp, false, st, nullptr, plan);
+    for (Stage& s : plan)
+        if ((rc = s.run())) break;
+    c->grads = grads_keep;
+    c->grad_accum = false;
+    c->pending_adam = pending_keep;
+    c->held_adam = held_keep;
+    c->dx.on = dx_keep;
+    if (rc) return rc;
+    if (dx) {
+        hipLaunchKernelGGL(copy_cols_kernel, dim3(32), dim3(256), 0, st, c->ws + w.d_in, ld, 0, dx, N.n_in, 0, rows, N.n_in);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int pvae_reparam_backward(pvae_ctx* c, const float* mu_logvar, const float* eps_used, const float* dz, int32_t rows,
+                          int noise, float* d_mu_logvar, void* stream) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!mu_logvar || !dz || !d_mu_logvar) return fail(-1, "mu_logvar / dz / d_mu_logvar is null");
+    const int kind = c->L.cfg.prior_kind;
+    if (noise && kind < PVAE_PRIOR_HYPERSPHERE && !eps_used) return fail(-1, "eps_used is null with noise on");
+    if (rows < 1 || rows > c->L.cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, c->L.cfg.max_batch);
+    const int Z = c->L.cfg.latent;
+    const int ldte = kind >= PVAE_PRIOR_HYPERSPHERE ? Z : 2 * Z;
+    hipLaunchKernelGGL(sampler_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, mu_logvar, ldte,
+                       eps_used, dz, rows, Z, kind, noise ? 1 : 0, d_mu_logvar);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 }  // extern "C"

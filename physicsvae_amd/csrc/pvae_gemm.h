@@ -2435,6 +2435,22 @@ struct EpiGradStore {         // weight gradient -> gradient arena (data-paralle
     __device__ inline void bias(int q, float v) const { gb[q] = v; }
 };
 
+// Read-add-write form of EpiGradStore (pvae_net_backward with accumulate = 1: one caller buffer summed over chunks of
+// a minibatch).  Every output tile -- and every bias column block -- belongs to ONE workgroup whose contraction runs in
+// a fixed order, so the same operands give the same bits; the old value is fetched under the loop like Adam's operands.
+struct EpiGradAccum {
+    float* g;
+    int ld;
+    float* gb = nullptr;
+    LossFinal loss{};
+    struct Pre { v4f g; };
+    __device__ inline Pre load(int q, int p) const { return Pre{*reinterpret_cast<const v4f*>(g + (size_t)q * ld + p)}; }
+    __device__ inline void apply(int q, int p, v4f v, const Pre& pre) const { store_stream(g + (size_t)q * ld + p, pre.g + v); }
+    __device__ inline void operator()(int q, int p, v4f v) const { apply(q, p, v, load(q, p)); }
+    __device__ inline bool has_bias() const { return gb != nullptr; }
+    __device__ inline void bias(int q, float v) const { gb[q] += v; }
+};
+
 struct EpiGradAdam {          // weight gradient consumed in registers by Adam (1-GPU path)
     float* w;
     float* m;

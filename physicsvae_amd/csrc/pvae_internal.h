@@ -196,6 +196,7 @@ struct pvae_ctx {
     StageArgs next_stage;        // rows_pad > 0: pending for the last launch of this step
     bool next_carried = false;   // set by the launch that took it
     bool seed_pads_clean = false;  // pad columns of the seed panels zeroed (see plan_backward)
+    bool grad_accum = false;       // pvae_net_backward(accumulate = 1): the plan's gradient stores add into the arena
     // deferred Adam (AdamSeg, pvae_gemm.h): the layer whose gradient the last launch stored; the next
     // weight-gradient launch of the step updates it with extra workgroups (PVAE_DEFER_ADAM=0: off)
     AdamSeg pending_adam;          // the most recent one

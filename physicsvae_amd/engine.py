@@ -824,13 +824,58 @@ class HipEngine:
         w = 2 * self.arch.Db
         return self.workspace[off: off + rows * w].view(rows, w)
 
+    def net_in_width(self, net):
+        """Columns of the dense input `net_forward` / `net_backward` read per row: the stack's full input width (a first layer
+        on an input subset reads its window of it, include/pvae.h pvae_config.te_inputs)."""
+        a = self.arch
+        return {NET_TE: 2 * a.Db, NET_MD: a.Db + a.Z, NET_MH: a.Db + a.Z, NET_WM: a.Db + a.Da, NET_PR: a.Db}[net]
+
     def net_forward(self, net, x):
         self._need_gpu()
         x = x.reshape(x.shape[0], -1).to(self.device, torch.float32).contiguous()
+        assert x.shape[1] == self.net_in_width(net), \
+            "x must be [rows, %d] (the stack's full input width), got %s" % (self.net_in_width(net), tuple(x.shape))
         n_out = [l for l in self.layers if l["net"] == net][-1]["n_out"]
         out = torch.empty(x.shape[0], n_out, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.pvae_net_forward(self.ctx, net, x.data_ptr(), x.shape[0], out.data_ptr(),
                                              self._stream()), "pvae_net_forward")
+        return out
+
+    def net_backward(self, net, x, dy, want_dx, grad=None, accumulate=False):
+        """Backward of one arena stack (`pvae_net_backward`): `x` [rows, n_in] as `net_forward` took it, `dy` [rows, n_out] =
+        dL/d(output).  Returns dx [rows, n_in] (None unless `want_dx`).  `grad`: a flat buffer of the stack's segment
+        (`segments[net]` count floats, arena layout) that receives the parameter gradient -- added to it with `accumulate`;
+        None: input gradient only.  At most `max_batch` rows; the forward is recomputed inside the call."""
+        self._need_gpu()
+        x = x.reshape(x.shape[0], -1).to(self.device, torch.float32).contiguous()
+        dy = dy.reshape(dy.shape[0], -1).to(self.device, torch.float32).contiguous()
+        rows = x.shape[0]
+        lays = [l for l in self.layers if l["net"] == net]
+        n_in = self.net_in_width(net)
+        assert x.shape[1] == n_in, "x must be [rows, %d] (the stack's full input width), got %s" % (n_in, tuple(x.shape))
+        assert dy.shape == (rows, lays[-1]["n_out"]), "dy must be [rows, n_out]"
+        if grad is not None:
+            assert grad.dtype == torch.float32 and grad.device == self.device and grad.is_contiguous() \
+                and grad.numel() == self.segments[net][1], "grad must be the stack's segment: %d floats" % self.segments[net][1]
+        dx = torch.empty(rows, n_in, dtype=torch.float32, device=self.device) if want_dx else None
+        _lib.check(self.lib.pvae_net_backward(self.ctx, net, x.data_ptr(), rows, dy.data_ptr(),
+                                              dx.data_ptr() if dx is not None else None,
+                                              grad.data_ptr() if grad is not None else None, 1 if accumulate else 0,
+                                              self._stream()), "pvae_net_backward")
+        return dx
+
+    def reparam_backward(self, mu_logvar, eps_used, dz, noise=True):
+        """Backward of `reparam` (`pvae_reparam_backward`): d(mu_logvar) from dz [rows, Z], the draws the forward used
+        (`eps_used` [rows, Z], None without noise or on the unit-sphere / no-prior encoders) and its mu_logvar."""
+        self._need_gpu()
+        ml = mu_logvar.to(self.device, torch.float32).contiguous()
+        dz = dz.to(self.device, torch.float32).contiguous()
+        out = torch.empty_like(ml)
+        if eps_used is not None:
+            eps_used = eps_used.to(self.device, torch.float32).contiguous()
+        _lib.check(self.lib.pvae_reparam_backward(self.ctx, ml.data_ptr(), eps_used.data_ptr() if eps_used is not None else None,
+                                                  dz.data_ptr(), ml.shape[0], 1 if noise else 0, out.data_ptr(),
+                                                  self._stream()), "pvae_reparam_backward")
         return out
 
     def reparam(self, mu_logvar, eps=None, noise=True, seed=0, offset=0):

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import autograd as AG
 from ._lib import NET_MD, NET_MH, NET_NAMES, NET_PR, NET_TE, NET_WM, PRIOR_KINDS
 from .engine import Arch, HipEngine, Stack
 
@@ -448,6 +449,8 @@ class PhysicsVAE(nn.Module):
         st = self._st
         if (self.__dict__.get("_srv_on") and rows <= 4 and obs.device.type == "cpu" and (eps is None or not noise)
                 and self._latent_prior_type != "hypersphere_uniform"):
+            if self._builds_graph(obs, NET_TE, NET_MD, NET_MH, NET_WM):
+                AG.warn_served_once()                  # (the served path stays as it is: inference only)
             if rows == 1:
                 return self._forward_served(obs, state, noise)
             if not self.__dict__.get("_srv_rows_off"):
@@ -462,6 +465,8 @@ class PhysicsVAE(nn.Module):
                     st._rng_calls -= 1                 # (the launch path below draws at the offset the request would have)
         obs = obs.to(eng.device)
         st._rng_calls += 1
+        if self._builds_graph(obs, NET_TE, NET_MD, NET_MH, NET_WM):
+            return self._forward_graph(obs, state, eps, noise)
         # (eager on purpose: with the input assembly, the sampler and the output copies inside the layer
         #  launches the call is 10 launches, and issue -> result at B = 1 measures 37 us eager against 44 us
         #  for a replay of the same launches as a HIP graph, whose fixed cost is higher; `graphed_infer`
@@ -483,6 +488,56 @@ class PhysicsVAE(nn.Module):
         st._mu = st._logvar = st._cur_value = None
         st._cur_latent_prior_mu = (eng.read("eps", rows) if self._latent_prior_type == "hypersphere_uniform"
                                    else None)                  # rmt:813-814: the unit prior sample of this forward
+        return logits, state
+
+    # -- autograd (physicsvae_amd/autograd.py) ------------------------------------------------------------------
+    def _stack_params(self, net):
+        """The parameter views of arena stack `net` in layer order ([] when the configuration has no such stack)."""
+        sp = self.__dict__.get("_stack_plist")
+        if sp is None:
+            mods = {NET_TE: self._task_encoder, NET_MD: self._motor_decoder, NET_WM: self._world_model,
+                    NET_PR: self._latent_prior, NET_MH: self._motor_decoder_helper}
+            sp = self.__dict__["_stack_plist"] = {n: AG.stack_params(m) if m is not None else [] for n, m in mods.items()}
+        return sp[net]
+
+    def _builds_graph(self, x, *nets):
+        """A graph-building call: autograd is on and the input, or a parameter of a stack the call runs, wants a gradient."""
+        if not torch.is_grad_enabled():
+            return False
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            return True
+        return any(p.requires_grad for n in nets for p in self._stack_params(n))
+
+    def _net(self, net, x, graph):
+        """One arena stack over any number of rows: through `HipNet` (graph-building calls) or `net_forward`."""
+        if graph:
+            return AG.HipNet.apply(self.engine, net, x, *self._stack_params(net))
+        return AG.net_forward(self.engine, net, x)
+
+    def _forward_graph(self, obs, state, eps, noise):
+        """`forward` of a graph-building call: the same `pvae_infer_logits` call (same bits), wrapped in `HipPolicy`.  The
+        tensors it hands out -- logits, z, mu / logvar, the world model's prediction -- carry the graph, so they are formed
+        with the forward instead of on first read: the prediction with every forward unless `rollout_predicts_state` is
+        False (then `_cur_future_state` stays None, as without autograd)."""
+        st, eng = self._st, self.engine
+        rows, Z = obs.shape[0], self._task_encoder_output_dim
+        nets = (NET_TE, NET_MD, NET_MH, NET_WM)
+        params = [self._stack_params(n) for n in nets]
+        a, z, ml, s2 = AG.HipPolicy.apply(self, obs, eps if noise else None, noise, st._rng_calls,
+                                          self.rollout_predicts_state is not False, tuple(len(p) for p in params),
+                                          *[p for ps in params for p in ps])
+        logits = self.__dict__["_als"](a)             # [a_hat | log_std] (AppendLogStd, rmt:160-206: a parameter trains)
+        st._cur_future_state = s2
+        st._cur_body_encoder_variable = obs[..., : self.dim_state_body]
+        st._cur_task_encoder_variable = z
+        # (value_function's torch path reads a copy: the caller may recycle its buffer right after this call)
+        st._lazy = (obs.clone(), rows)
+        if self._latent_prior_type in ("hypersphere_uniform", False):
+            st._mu, st._logvar = z, None
+        else:
+            st._mu, st._logvar = ml[:, :Z], ml[:, Z:]
+        st._cur_value = None
+        st._cur_latent_prior_mu = eng.read("eps", rows) if self._latent_prior_type == "hypersphere_uniform" else None
         return logits, state
 
     # -- the call-persistent rollout server (opt-in; include/pvae.h pvae_rollout_server_*) -------------------
@@ -623,26 +678,41 @@ class PhysicsVAE(nn.Module):
     def forward_encoder(self, obs, state=None, seq_lens=None, state_cnt=0, eps=None):
         Z = self._task_encoder_output_dim
         obs = obs.to(self.engine.device)
-        h = self.engine.net_forward(NET_TE, obs)
+        h = self._net(NET_TE, obs, self._builds_graph(obs, NET_TE))
         if self._latent_prior_type is False:                        # rmt:815-816: the encoder output is the code
             z_task = self._reparameterize(h, None)                  # (a copy through the sampler kernel, not normalised)
             return obs[..., : self.dim_state_body], z_task, state_cnt
         if self._latent_prior_type == "hypersphere_uniform":        # rmt:810-814 (z = mu: oracle PRIORS)
             z_task = self._reparameterize(h, eps)                   # e / |e|; the unit prior sample lands in "eps"
             self._cur_task_encoder_mu, self._cur_task_encoder_logvar = z_task, None
-            self._cur_latent_prior_mu = self.engine.read("eps", h.shape[0])
+            self._cur_latent_prior_mu = self.__dict__.pop("_sphere_u")
             return obs[..., : self.dim_state_body], z_task, state_cnt
         self._cur_task_encoder_mu, self._cur_task_encoder_logvar = h[:, :Z], h[:, Z:]
         z_task = self._reparameterize(h, eps)
         if self._latent_prior is not None:                          # rmt:801-809
-            self._cur_latent_prior_mu = self.engine.net_forward(NET_PR, obs[..., : self.dim_state_body].contiguous())
+            s_body = obs[..., : self.dim_state_body].contiguous()
+            self._cur_latent_prior_mu = self._net(NET_PR, s_body, self._builds_graph(s_body, NET_PR))
             self._cur_latent_prior_logvar = torch.zeros_like(self._cur_latent_prior_mu)
         return obs[..., : self.dim_state_body], z_task, state_cnt
 
     def _reparameterize(self, mu_logvar, eps=None):
-        self._rng_calls += 1
-        return self.engine.reparam(mu_logvar, eps=eps, noise=self.latent_prior_noise,
-                                   seed=self._rng_seed, offset=self._rng_calls)
+        """The sampler over any number of rows: one library call (and one Philox offset) per chunk of at most
+        `max_batch` rows; through `HipReparam` when mu_logvar carries a graph."""
+        eng, noise = self.engine, self.latent_prior_noise
+        graph = torch.is_grad_enabled() and mu_logvar.requires_grad
+        zs, us = [], []
+        for lo, hi in AG.chunks(mu_logvar.shape[0], eng.max_batch):
+            self._rng_calls += 1
+            e = eps[lo:hi] if eps is not None else None
+            if graph:
+                zs.append(AG.HipReparam.apply(eng, noise, self._rng_seed, self._rng_calls, e, mu_logvar[lo:hi]))
+            else:
+                zs.append(eng.reparam(mu_logvar[lo:hi], eps=e, noise=noise, seed=self._rng_seed, offset=self._rng_calls))
+            if self._latent_prior_type == "hypersphere_uniform":
+                us.append(eng.read("eps", hi - lo))                 # the unit prior sample of this chunk
+        if us:
+            self.__dict__["_sphere_u"] = us[0] if len(us) == 1 else torch.cat(us)
+        return zs[0] if len(zs) == 1 else torch.cat(zs)
 
     def forward_decoder(self, z_body, z_task, state=None, seq_lens=None, state_cnt=0):
         if (self.__dict__.get("_srv_on") and z_body.device.type == "cpu" and z_task.device.type == "cpu" and z_body.dim() == 2
@@ -651,7 +721,7 @@ class PhysicsVAE(nn.Module):
             a = self.engine.rollout_server_decode(torch.cat([z_body.float(), z_task.float()], dim=-1).numpy())
             return self._motor_decoder._model[-1](torch.from_numpy(a.copy())[None]), state_cnt
         z = torch.cat([z_body.to(self.engine.device), z_task.to(self.engine.device)], dim=-1)
-        a_hat = self.engine.net_forward(NET_MD, z)
+        a_hat = self._net(NET_MD, z, self._builds_graph(z, NET_MD))
         mh = self._motor_decoder_helper
         if mh is not None:                                            # rmt:833-835
             if self._motor_decoder_inputs != ["body", "task"]:        # rmt:822-829: the helper's own weights are compact
@@ -670,7 +740,7 @@ class PhysicsVAE(nn.Module):
     def forward_world(self, obs, logits):
         x = torch.cat([obs[..., : self.dim_state_body].to(self.engine.device),
                        logits[..., : self.dim_action].to(self.engine.device)], dim=-1)
-        return self.engine.net_forward(NET_WM, x)
+        return self._net(NET_WM, x, self._builds_graph(x, NET_WM))
 
     def forward_value_branch(self, obs, state=None, seq_lens=None, state_cnt=0):
         """rmt:846-853.  Sampling (no autograd: RLlib's rollout workers) runs the three small Linear layers as one
