@@ -756,6 +756,48 @@ __device__ inline void lds_dma16(const float* src, float* dst_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                      (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
 }
+// The same DMA with a wave-uniform 64-bit base in SGPRs and a per-lane 32-bit byte offset (scalar-base form).  A loader
+// wave shares its SIMD with a compute wave whose back-to-back fp32 MFMAs hold the vector issue (tools/dual_pipe.hip:
+// other waves' vector-ALU instructions drop to a fifth of their rate), so the loaders' steady state must issue NO
+// vector-ALU instruction: the lane offsets are computed once in front of the loop, one VGPR per DMA piece of a tile (no
+// piece waits for another's address register), and the k-tile advance is scalar arithmetic on the base.  hipcc turns
+// `base + offset` handed to the builtin back into a 64-bit vector add per DMA (v_lshl_add_u64, all pieces through one
+// register pair), hence inline assembly; M0 (the LDS destination) is compiler-reserved, so it is saved, written and
+// restored inside the statement that reads it, with the wait state the DMA needs after a scalar write of M0.  hipcc does
+// not count the instruction: every wait for it is one of the explicit wait_vmcnt<> here, as it already was.
+__device__ inline void lds_dma16_sbase(const char* base_uniform, unsigned lane_byte_off, float* dst_wave_base) {
+    const unsigned m0v = (unsigned)(size_t)(__attribute__((address_space(3))) void*)dst_wave_base;
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(lane_byte_off), "s"(base_uniform), "s"(m0v)
+                 : "memory");
+}
+// A/B switch of the diagnostic builds (build.py defines=["PVAE_LOADER_VADDR"] into ab_libs/): the dense loaders as they
+// were, one 64-bit vector add in front of every DMA.
+#ifdef PVAE_LOADER_VADDR
+constexpr bool kLoaderScalarBase = false;
+#else
+constexpr bool kLoaderScalarBase = true;
+#endif
+// Lane offsets are 32-bit: a tile spans at most 64 rows x ld floats (checked where the launches are planned).
+inline bool ws_offsets_fit(int ldq, int ldp) { return ldq >= 0 && ldq < (1 << 24) && ldp >= 0 && ldp < (1 << 24); }
+// The dense loaders' walk over the k-tiles: tile bases (bytes) and ring slot advance by wrap-around increments, all of it
+// wave-uniform (SGPRs; no division per issue).  Tiles are issued strictly in order, starting at step `t`.
+struct DenseWalk {
+    const char *q0, *p0, *q, *p;      // bases of k-tile 0 and of the next tile to issue
+    unsigned long long kq, kp;        // bytes per k-tile
+    int kt, nk, slot;
+    __device__ inline DenseWalk(const char* qb, const char* pb, unsigned long long kq_, unsigned long long kp_, int nk_)
+        : q0(qb), p0(pb), q(qb), p(pb), kq(kq_), kp(kp_), kt(0), nk(nk_), slot(0) {}
+    __device__ inline void seek(int kt_, int slot_) { kt = kt_; slot = slot_; q = q0 + kt_ * kq; p = p0 + kt_ * kp; }
+    template <int S>
+    __device__ inline void next() {
+        q += kq; p += kp;
+        if (++kt == nk) { kt = 0; q = q0; p = p0; }           // (k_rotation's wrap)
+        if (++slot == S) slot = 0;
+    }
+};
 // this wave's DMAs of a tile have landed once at most `younger` tiles (4 instructions each)
 // issued after it are still in flight
 __device__ inline void wait_dma_tile(int younger) {
@@ -926,11 +968,32 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
 
     const size_t kstep_p = P_ROW ? (size_t)BK : (size_t)BK * ldp;
     const int rot = k_rotation(ga, loc, tile_q, nk);
+    // Dense operands: wave-uniform byte bases of k-tile 0's two panels + each lane's 32-bit byte offset of 16-byte slot j
+    // (the XOR swizzle stays on the source offset) -- see lds_dma16_sbase.  Gathered operands keep per-lane pointers.
+    constexpr bool kSB = QS::kAlwaysFast && kLoaderScalarBase;
+    const char* const qb0 = reinterpret_cast<const char*>(Q + (size_t)q0 * ldq);
+    const char* const pb0 = reinterpret_cast<const char*>(P_ROW ? P + (size_t)p0 * ldp : P + p0);
+    auto off_rows = [](int j, int ld) {
+        const int row = j >> 4, c = (j & 15) ^ (row & 15);
+        return ((unsigned)row * (unsigned)ld + c * 4) * 4u;
+    };
+    auto off_q = [&](int j) { return off_rows(j, ldq); };
+    auto off_p = [&](int j) {
+        if (P_ROW) return off_rows(j, ldp);
+        const int r = j >> 3, k = r ^ ((r >> 2) & 1);
+        return ((unsigned)k * (unsigned)ldp + (j & 7) * 4) * 4u;
+    };
     // k-tile 0 is fetched by ALL eight waves (one eighth of each operand image per wave, two DMA
     // instructions each): it is in flight ~0.1 us after the workgroup starts instead of queueing
     // behind the loaders' three-tile prologue (each global_load_lds holds its wave ~150 cycles, so
     // the prologue alone took 0.67 us -- tools/timeline_probe.hip).
-    if (!PVAE_PROBE(6) && wave < 8) {
+    if constexpr (kSB) {
+        if (!PVAE_PROBE(6) && wave < 8) {
+            const int j = wave * 64 + lane;               // 16-byte slot inside the 8 KB tile image
+            lds_dma16_sbase(qb0 + (size_t)rot * (BK * 4), off_q(j), lds + wave * 256);
+            lds_dma16_sbase(pb0 + (size_t)rot * kstep_p * 4, off_p(j), lds + kTile + wave * 256);
+        }
+    } else if (!PVAE_PROBE(6) && wave < 8) {
         const int j = wave * 64 + lane;                   // 16-byte slot inside the 8 KB tile image
         typename QS::Base s0q;
         const float* s0p;
@@ -969,8 +1032,30 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                 sp[u] = P + (size_t)k * ldp + p0 + (j & 7) * 4;
             }
         }
+        // dense operands: lane offsets of this wave's pieces (distinct VGPRs), tile walk in SGPRs; issue() is called
+        // for t = 1, 2, 3, ... in order, so the walk only ever steps to the next tile
+        unsigned vq[kWsPer], vp[kWsPer];
+#pragma unroll
+        for (int u = 0; u < kWsPer; ++u) {
+            vq[u] = off_q((u0 + kWsLoaders * u) * 64 + lane);
+            vp[u] = off_p((u0 + kWsLoaders * u) * 64 + lane);
+        }
+        DenseWalk walk(qb0, pb0, BK * 4, kstep_p * 4, nk);
+        walk.seek(rot + 1 < nk ? rot + 1 : 0, 1);
         auto issue = [&](int t) {
             if (PVAE_PROBE(6)) return;                    // probe: loaders only keep the barriers
+            if constexpr (kSB) {
+                float* slot = lds + walk.slot * kStage;
+                const char* const qb = PVAE_PROBE(2) ? qb0 : walk.q;   // probe: every step re-reads tile 0 (cache-resident)
+                const char* const pb = PVAE_PROBE(2) ? pb0 : walk.p;
+#pragma unroll
+                for (int u = 0; u < kWsPer; ++u) {
+                    lds_dma16_sbase(qb, vq[u], slot + (u0 + kWsLoaders * u) * 256);
+                    lds_dma16_sbase(pb, vp[u], slot + kTile + (u0 + kWsLoaders * u) * 256);
+                }
+                walk.template next<S>();
+                return;
+            }
             float* slot = lds + (t % S) * kStage;
             int kt = t + rot;                             // k-tile this workgroup reads at step t
             if (kt >= nk) kt -= nk;
@@ -1214,7 +1299,28 @@ __device__ inline void splitk_ws64_body(float* lds, int bid, const GemmArgs& ga,
         const int r = j >> 3, k = r ^ ((r >> 2) & 1);
         return P + (size_t)k * ldp + p0 + (j & 7) * 4;
     };
+    // dense operands: wave-uniform panel bases + 32-bit lane offsets of the same slots (lds_dma16_sbase)
+    constexpr bool kSB = QS::kAlwaysFast && kLoaderScalarBase;
+    const char* const qb0 = reinterpret_cast<const char*>(Q + (size_t)q0 * ldq);
+    const char* const pb0 = reinterpret_cast<const char*>(P_ROW ? P + (size_t)p0 * ldp : P + p0);
+    auto off_rows = [](int j, int ld) {
+        const int row = j >> 4, c = (j & 15) ^ (row & 15);
+        return ((unsigned)row * (unsigned)ld + c * 4) * 4u;
+    };
+    auto off_q = [&](int j) { return off_rows(j, ldq); };
+    auto off_p = [&](int j) {
+        if (P_ROW) return off_rows(j, ldp);
+        if (PT == 64) return ((unsigned)(j >> 4) * (unsigned)ldp + (j & 15) * 4) * 4u;
+        const int r = j >> 3, k = r ^ ((r >> 2) & 1);
+        return ((unsigned)k * (unsigned)ldp + (j & 7) * 4) * 4u;
+    };
     // k-tile 0 by all eight waves: Q image = 1024 slots (two per lane and wave), P image = 512 / 1024 (one / two)
+    if constexpr (kSB) {
+        lds_dma16_sbase(qb0, off_q(wave * 64 + lane), lds + wave * 256);
+        lds_dma16_sbase(qb0, off_q((wave + 8) * 64 + lane), lds + (wave + 8) * 256);
+        lds_dma16_sbase(pb0, off_p(wave * 64 + lane), lds + kTileQ + wave * 256);
+        if (PT == 64) lds_dma16_sbase(pb0, off_p((wave + 8) * 64 + lane), lds + kTileQ + (wave + 8) * 256);
+    } else {
     if (QS::kAlwaysFast || qs.fast(0)) {
         lds_dma16(qs.tile_fast(src_q(wave * 64 + lane), 0), lds + wave * 256);
         lds_dma16(qs.tile_fast(src_q((wave + 8) * 64 + lane), 0), lds + (wave + 8) * 256);
@@ -1224,6 +1330,7 @@ __device__ inline void splitk_ws64_body(float* lds, int bid, const GemmArgs& ga,
     }
     lds_dma16(src_p(wave * 64 + lane), lds + kTileQ + wave * 256);
     if (PT == 64) lds_dma16(src_p((wave + 8) * 64 + lane), lds + kTileQ + (wave + 8) * 256);
+    }
     if (wave >= 4) {
         // ---------------- loader waves: 4 Q + NB P instructions per tile ----------------
         const int u0 = wave - 4;
@@ -1233,7 +1340,23 @@ __device__ inline void splitk_ws64_body(float* lds, int bid, const GemmArgs& ga,
         for (int u = 0; u < 4; ++u) sq[u] = src_q((u0 + 4 * u) * 64 + lane);
 #pragma unroll
         for (int u = 0; u < NB; ++u) sp[u] = src_p((u0 + 4 * u) * 64 + lane);
-        auto issue = [&](int t) {
+        unsigned vq[4], vp[NB];                                  // (dense: see splitk_ws_body)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vq[u] = off_q((u0 + 4 * u) * 64 + lane);
+#pragma unroll
+        for (int u = 0; u < NB; ++u) vp[u] = off_p((u0 + 4 * u) * 64 + lane);
+        DenseWalk walk(qb0, pb0, BK * 4, kstep_p * 4, nk);
+        walk.seek(1 < nk ? 1 : 0, 1);
+        auto issue = [&](int t) {                                // called for t = 1, 2, 3, ... in order
+            if constexpr (kSB) {
+                float* slot = lds + walk.slot * kStage;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) lds_dma16_sbase(walk.q, vq[u], slot + (u0 + 4 * u) * 256);
+#pragma unroll
+                for (int u = 0; u < NB; ++u) lds_dma16_sbase(walk.p, vp[u], slot + kTileQ + (u0 + 4 * u) * 256);
+                walk.template next<S>();
+                return;
+            }
             float* slot = lds + (t % S) * kStage;
             if (QS::kAlwaysFast || qs.fast(t)) {
 #pragma unroll
@@ -2542,6 +2665,7 @@ inline int forward_tiles(int M, int N) {
 template <class Epi>
 inline hipError_t gemm_forward_epi(const float* X, int ldx, const float* W, int ldw, int M, int N, int K,
                                    const Epi& e, hipStream_t st) {
+    if (!ws_offsets_fit(ldx, ldw)) return hipErrorInvalidValue;
     if (forward_uses_16x16(M, N)) {
         const GemmGrid g = make_grid(M, N, 16, 16);
         const GemmArgs ga{X, ldx, W, ldw, K, g.tiles_q, g.tiles_p, g.p_per_xcd};
@@ -2572,6 +2696,7 @@ inline bool forward_pro_ok(int M, int N) { return !forward_uses_16x16(M, N) && !
 template <class Epi, class Pro>
 inline hipError_t gemm_forward_pro(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, const Epi& e,
                                    const Pro& pro, hipStream_t st) {
+    if (!ws_offsets_fit(ldx, ldw)) return hipErrorInvalidValue;
     const GemmGrid g = make_grid(M, N, 32, 32);
     const GemmArgs ga{X, ldx, W, ldw, K, g.tiles_q, g.tiles_p, g.p_per_xcd};
     PVAE_LAUNCH((gemm_splitk_ws_pro_kernel<Epi, Pro>), dim3(g.grid), dim3(kWsThreads), st, PVAE_GA_PASS(ga), e, pro);
@@ -2645,6 +2770,7 @@ inline DgradPlan plan_dgrad(const float* dZ, int ldz, const float* W, int ldw, i
 template <class EpiD>
 inline hipError_t gemm_dgrad_epi(const float* dZ, int ldz, const float* W, int ldw, int M, int Kin, int N,
                                  const EpiD& e, hipStream_t st) {
+    if (!ws_offsets_fit(ldz, ldw)) return hipErrorInvalidValue;
     if constexpr (std::is_same<EpiD, EpiMask>::value) {
         if (uses_64x64(M, Kin)) {                               // ... at >= 1024 rows
             GemmArgs ga{dZ, ldz, W, ldw, N, 0, 0, 0};

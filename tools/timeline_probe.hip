@@ -62,6 +62,13 @@ int main() {
             printf("   %-24s min %6.2f  median %6.2f  max %6.2f us after the first workgroup entered\n", names[id],
                    v.front(), v[v.size() / 2], v.back());
         }
+        // k-tile period: each workgroup's own (main loop done - tile 0 seen) over its K / 64 k-tiles
+        std::vector<double> per;
+        for (int w = 0; w < g.grid; ++w)
+            per.push_back((double)(h[(size_t)w * 8 + 2] - h[(size_t)w * 8 + 1]) * 10.0 / (K / 64));
+        std::sort(per.begin(), per.end());
+        printf("   k-tile period            min %6.1f  median %6.1f  max %6.1f ns (%d k-tiles per workgroup)\n", per.front(),
+               per[per.size() / 2], per.back(), K / 64);
     }
     return 0;
 }
