@@ -216,7 +216,8 @@ int pvae_set_direct(pvae_ctx* ctx, int on);
  * PVAE_* variables is set here (the Python host, physicsvae_amd/engine.py, still maps those variables onto these calls for
  * the tests and the A/B scripts).  Defaults are the production values.
  *   ctx == NULL, process-wide kernel geometry:  "ws64" "ws6464" "ws6464_rows" "pair64" "dgrad16" (0 / 1), "wgrad32" (0 / 1 / 2),
- *       "krot" "rowxcd" (0 / 1, experiments, default 0), "look_pair" "rollout_fused" (0 / 1)
+ *       "krot" "rowxcd" (0 / 1, experiments, default 0), "look_pair" "rollout_fused" (0 / 1),
+ *       "fc_per_stack" (0 / 1: the stack set's launches one per stack instead of one per layer depth, see pvae_fc_* below)
  *   ctx, that context's schedule:  "pair" "defer_adam" "same_layer" "fold_sampler" (0 / 1), "direct" (= pvae_set_direct),
  *       "p2p_timeout_ms" (> 0), "p2p_selftest_flags_only" (0 / 1), "server_mailbox" (0 auto, 1 pinned host memory, 2 device)
  * Every variant gives the same bits as the default (held by tests/test_gpu_shapes.py, test_gpu_fuzz.py).  -1: unknown name. */
@@ -569,6 +570,77 @@ int pvae_net_backward(pvae_ctx* ctx, int net, const float* in, int32_t rows, con
  * eps_used is not read), eps_used / dz [rows][Z], all dense. */
 int pvae_reparam_backward(pvae_ctx* ctx, const float* mu_logvar, const float* eps_used, const float* dz,
                           int32_t rows, int noise, float* d_mu_logvar, void* stream);
+
+/* ---- stack set: S fully connected stacks on ONE shared input (FullyConnectedPolicy "fcnn", rmt:323-457) -------------
+ * The reference's other custom model: `_policy_fn`, `_value_fn` and, with log_std_type "state_dependent", `_log_std_fn`
+ * (rmt:386-427) are independent FC stacks (rmt:234-283) that all read the same observation (rmt:430-441).  At their sizes
+ * (256x2 / 64x2) a step is bound by launch boundaries, so the stacks run TOGETHER: one launch per layer depth for all of
+ * them, instead of one per layer per stack.
+ *
+ * pvae_fc_config: stack s has depth[s] hidden layers of width[s][i] with activation act[s][i] (PVAE_ACT_*), then a linear
+ * output layer of n_out[s] values.  1 <= n_stacks <= PVAE_FC_MAX_STACKS, depth in [0, PVAE_MAX_HIDDEN].
+ *
+ * Arena (one flat fp32 buffer, the padding rules of the five-net arena: W[n_out_pad][ld] row-major with ld = n_in rounded
+ * up to 64 and n_out_pad = n_out rounded up to 64, then bias[n_out_pad]; pads are zero and stay zero):
+ *   [ W_0 of stack 0 | W_0 of stack 1 | ... | bias_0 of stack 0 | bias_0 of stack 1 | ... | per stack: W_1 b_1 W_2 b_2 ... ]
+ * The first layers share their input and therefore their row stride: back to back they are one weight block, so the
+ * first layer of all stacks is ONE GEMM over the concatenated output features, and the gradient with respect to the
+ * input is one GEMM whose contraction over those features is the sum over the stacks.  The checkpoint tensor
+ * `_policy_fn._model.<i>._model.0.weight` [n_out, n_in] is the strided view W[:n_out, :n_in] of its block; nothing is
+ * packed or copied per call.  A gradient arena has the same layout.
+ *
+ *   pvae_fc_num_layers / pvae_fc_layer   enumerate the Linear layers stack by stack, first layer first (pvae_layer_info:
+ *                       net = stack, col0 = 0); offsets follow the arena order above, not the enumeration order
+ *   pvae_fc_arena_floats / pvae_fc_workspace_bytes   sizes of the parameter (gradient) arena and of the workspace
+ *   pvae_fc_create / pvae_fc_destroy / pvae_fc_bind   the opaque context (layout tables + the two bound device buffers)
+ *   pvae_fc_forward     x[rows][n_in] dense -> out[s][rows][n_out[s]] dense per stack (out[s] NULL: not wanted -- the stack
+ *                       still runs unless no later stack is wanted either), 1 <= rows <= max_batch.  Replaces
+ *                       FullyConnectedPolicy.forward's three FC calls (rmt:434-438).  rows <= 4: the GEMV family (one
+ *                       wave per output feature, rollout latency); above: tile kernels.  Launches: one copy of x into the
+ *                       padded input panel, ONE for the first layer of all stacks, ONE per deeper layer depth in which
+ *                       the workgroup index maps to (stack, tile) -- stacks that are shallower drop out, narrower ones
+ *                       contribute fewer tiles.  The output layers write the dense results themselves.
+ *   pvae_fc_backward    what loss.backward() does to those calls.  dy[s][rows][n_out[s]] dense per stack, NULL: that stack
+ *                       gets no gradient and costs nothing (its layers run neither forward nor backward, except where
+ *                       its first layer lies between two wanted ones in the shared block).  dx[rows][n_in] (NULL: not
+ *                       wanted) = the input gradient SUMMED over the stacks with a dy.  grad (NULL: none): a gradient
+ *                       arena; stack s writes its part only when bit s of grad_mask is set (a frozen stack passes the
+ *                       input gradient and leaves its part of `grad` untouched); accumulate: 0 store, 1 read-add-write
+ *                       (EpiGradAccum, as pvae_net_backward: every output tile summed by one workgroup in a fixed order).
+ *                       Recompute, as pvae_net_backward: the forward launches run again on the panels, a seed launch
+ *                       forms every output gradient, then ONE launch per layer depth, last to first, holding the input-
+ *                       gradient and the weight-gradient tiles (and bias sums) of every participating stack at that depth
+ *                       (the same-layer pairing of the trainer's backward plan, inside the group); the first-layer launch
+ *                       holds the one input-gradient GEMM and the stacks' weight gradients.  Pad rows and pad columns of
+ *                       every panel a contraction reads are written (zeros, or finite values that meet zeros) by this
+ *                       call, so nothing an earlier call left in the workspace reaches a gradient.
+ *   pvae_fc_launches    kernel launches of the last pvae_fc_forward / pvae_fc_backward call on this context.
+ * pvae_set_option(NULL, "fc_per_stack", 1): the same tiles, one launch per stack where the default issues one per depth
+ * (the A/B baseline of the grouping; the input-gradient GEMM of the first layers stays one launch -- split, it would need
+ * a sum over the stacks in another order).  Tile geometry is a function of the problem alone, so both schedules give the
+ * same bits. */
+#define PVAE_FC_MAX_STACKS 4
+typedef struct pvae_fc_config {
+    int32_t n_in;       /* width of the shared input (the flattened observation, rmt:384) */
+    int32_t n_stacks;
+    int32_t max_batch;  /* largest number of rows of one call */
+    int32_t depth[PVAE_FC_MAX_STACKS];      /* hidden layers per stack */
+    int32_t n_out[PVAE_FC_MAX_STACKS];      /* width of the linear output layer */
+    int32_t width[PVAE_FC_MAX_STACKS][16];  /* hidden widths */
+    int32_t act[PVAE_FC_MAX_STACKS][16];    /* PVAE_ACT_* per hidden layer (0 = relu) */
+} pvae_fc_config;
+typedef struct pvae_fc pvae_fc;
+int pvae_fc_num_layers(const pvae_fc_config* cfg);
+int pvae_fc_layer(const pvae_fc_config* cfg, int i, pvae_layer_info* out);
+int64_t pvae_fc_arena_floats(const pvae_fc_config* cfg);
+size_t pvae_fc_workspace_bytes(const pvae_fc_config* cfg);
+int pvae_fc_create(const pvae_fc_config* cfg, pvae_fc** out);
+void pvae_fc_destroy(pvae_fc* fc);
+int pvae_fc_bind(pvae_fc* fc, float* params, void* workspace, size_t workspace_bytes);
+int pvae_fc_forward(pvae_fc* fc, const float* x, int32_t rows, float* const* out, void* stream);
+int pvae_fc_backward(pvae_fc* fc, const float* x, int32_t rows, const float* const* dy, float* dx, float* grad,
+                     int32_t grad_mask, int32_t accumulate, void* stream);
+int pvae_fc_launches(pvae_fc* fc, int32_t* forward, int32_t* backward);
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the

@@ -61,6 +61,16 @@ class LayerInfo(C.Structure):
                 ("w_offset", C.c_int64), ("b_offset", C.c_int64), ("act", C.c_int32), ("col0", C.c_int32)]
 
 
+FC_MAX_STACKS = 4
+
+
+class FcConfig(C.Structure):
+    """pvae_fc_config: a stack set (S fully connected stacks on one shared input)."""
+    _fields_ = [("n_in", C.c_int32), ("n_stacks", C.c_int32), ("max_batch", C.c_int32),
+                ("depth", C.c_int32 * FC_MAX_STACKS), ("n_out", C.c_int32 * FC_MAX_STACKS),
+                ("width", (C.c_int32 * 16) * FC_MAX_STACKS), ("act", (C.c_int32 * 16) * FC_MAX_STACKS)]
+
+
 class StepParams(C.Structure):
     _fields_ = [("a_rec_coeff", C.c_float), ("kl_coeff", C.c_float), ("s_rec_coeff", C.c_float),
                 ("cycle_coeff", C.c_float), ("lr", C.c_double), ("beta1", C.c_double),
@@ -142,6 +152,16 @@ _SIGS = {
     "pvae_reparam": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int, C.c_uint64, C.c_uint64, _P, _P]),
     "pvae_net_backward": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "pvae_reparam_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, _P, _P]),
+    "pvae_fc_num_layers": (C.c_int, [C.POINTER(FcConfig)]),
+    "pvae_fc_layer": (C.c_int, [C.POINTER(FcConfig), C.c_int, C.POINTER(LayerInfo)]),
+    "pvae_fc_arena_floats": (C.c_int64, [C.POINTER(FcConfig)]),
+    "pvae_fc_workspace_bytes": (C.c_size_t, [C.POINTER(FcConfig)]),
+    "pvae_fc_create": (C.c_int, [C.POINTER(FcConfig), C.POINTER(_P)]),
+    "pvae_fc_destroy": (None, [_P]),
+    "pvae_fc_bind": (C.c_int, [_P, _P, _P, C.c_size_t]),
+    "pvae_fc_forward": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P]),
+    "pvae_fc_backward": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P), _P, _P, C.c_int32, C.c_int32, _P]),
+    "pvae_fc_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),
@@ -189,7 +209,7 @@ PROCESS_OPTIONS = {
     "PVAE_KROT": ("krot", _flag), "PVAE_ROWXCD": ("rowxcd", _flag), "PVAE_WS64": ("ws64", _flag),
     "PVAE_WS6464": ("ws6464", _flag), "PVAE_WS6464_ROWS": ("ws6464_rows", _flag), "PVAE_PAIR64": ("pair64", _flag),
     "PVAE_DGRAD16": ("dgrad16", _flag), "PVAE_WGRAD32": ("wgrad32", int), "PVAE_LOOK_PAIR": ("look_pair", _flag),
-    "PVAE_ROLLOUT_FUSED": ("rollout_fused", _flag),
+    "PVAE_ROLLOUT_FUSED": ("rollout_fused", _flag), "PVAE_FC_PER_STACK": ("fc_per_stack", _flag),
 }
 CONTEXT_OPTIONS = {
     "PVAE_PAIR": ("pair", _flag), "PVAE_DEFER_ADAM": ("defer_adam", _flag), "PVAE_SAME_LAYER": ("same_layer", _flag),

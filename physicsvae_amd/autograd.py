@@ -9,6 +9,7 @@ Their forwards are the very calls the module makes without autograd, so values a
   HipNet      one stack: (x, *parameter views of the stack) -> output
   HipReparam  the sampler: mu_logvar -> z, with the draws the forward used kept for the backward
   HipPolicy   `forward()` as ONE `pvae_infer_logits` call: (obs, *TE, *MD, *MH, *WM) -> (a_hat, z, mu_logvar, s2)
+  HipStackSet a stack set (`pvae_fc_*`, FullyConnectedPolicy): (x, *params of all stacks) -> (out_0, ..., out_{S-1})
 
 Every backward runs in chunks of at most `max_batch` rows, the parameter gradient summed over the chunks into one flat
 buffer per stack (accumulate = 1 after the first chunk) and handed back as views shaped like the parameters.  The
@@ -232,3 +233,67 @@ class HipPolicy(torch.autograd.Function):
                + _param_grads(eng, NET_MH, g_mh, need_mh) + _param_grads(eng, NET_WM, g_wm, need_wm))
         d_obs = d_obs.view(obs_in.shape).to(ctx.obs_dtype) if d_obs is not None else None
         return (None, d_obs, None, None, None, None, None) + tuple(out)
+
+
+def stack_set_forward(eng, x, want=None):
+    """`StackSetEngine.forward` over any number of rows (chunks of at most `max_batch`)."""
+    if x.shape[0] <= eng.max_batch:
+        return eng.forward(x, want)
+    parts = [eng.forward(x[lo:hi], want) for lo, hi in chunks(x.shape[0], eng.max_batch)]
+    return [None if p[0] is None else torch.cat(p) for p in zip(*parts)]
+
+
+def stack_set_grad_views(eng, gbuf):
+    """`gbuf` (a flat gradient with the stack set's arena layout) as views shaped like the parameters, stack by stack in
+    layer order: weight, bias, weight, bias, ..."""
+    return [t for s in range(len(eng.stacks)) for wb in eng.views(s, gbuf) for t in wb]
+
+
+class HipStackSet(torch.autograd.Function):
+    """A stack set under autograd (FullyConnectedPolicy.forward, rmt:430-441: the policy, the value and the log-std
+    stacks on one observation): `HipStackSet.apply(engine, x, *params)` with params = the weight / bias views of all stacks,
+    stack by stack in layer order -> (out_0, ..., out_{S-1}).  Forward = `engine.forward` (chunked), the very call made
+    without a graph.  Backward = `engine.backward` per chunk: an output nobody differentiates costs nothing, a stack none
+    of whose parameters wants a gradient (frozen) passes the input gradient only, and the parameter gradient is summed over
+    the chunks inside the library (accumulate = 1 after the first).  x and the parameters are kept with
+    `save_for_backward` only; no double backward."""
+
+    @staticmethod
+    def forward(ctx, eng, x, *params):
+        ctx.eng, ctx.x_shape, ctx.x_dtype = eng, x.shape, x.dtype
+        ctx.set_materialize_grads(False)         # an output nobody differentiates arrives as None, not as a tensor of zeros
+        ctx.save_for_backward(x, *params)
+        return tuple(stack_set_forward(eng, x.reshape(x.shape[0], -1).to(eng.device, torch.float32).contiguous()))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gys):
+        eng = ctx.eng
+        x = ctx.saved_tensors[0]                 # (raises if x or a parameter was written in place since the forward)
+        x = x.reshape(x.shape[0], -1).to(eng.device, torch.float32).contiguous()
+        needs = ctx.needs_input_grad[2:]
+        want_dx = ctx.needs_input_grad[1]
+        mask, k = 0, 0
+        for s in range(len(eng.stacks)):
+            n = 2 * len(eng.stack_layers(s))
+            if any(needs[k: k + n]) and gys[s] is not None:
+                mask |= 1 << s
+            k += n
+        dys = [None if g is None else g.float().contiguous() for g in gys]
+        gbuf = torch.empty(eng.arena_floats, dtype=torch.float32, device=eng.device) if mask else None
+        if not (want_dx or mask) or all(d is None for d in dys):
+            return (None, None) + (None,) * len(needs)
+        dxs = [eng.backward(x[lo:hi], [None if d is None else d[lo:hi] for d in dys], want_dx, gbuf, mask, accumulate=i > 0)
+               for i, (lo, hi) in enumerate(chunks(x.shape[0], eng.max_batch))]
+        dx = None
+        if want_dx:
+            dx = (dxs[0] if len(dxs) == 1 else torch.cat(dxs)).view(ctx.x_shape).to(ctx.x_dtype)
+        grads = [None] * len(needs)
+        if mask:
+            views, k = stack_set_grad_views(eng, gbuf), 0
+            for s in range(len(eng.stacks)):
+                n = 2 * len(eng.stack_layers(s))
+                if (mask >> s) & 1:
+                    grads[k: k + n] = [v if nd else None for v, nd in zip(views[k: k + n], needs[k: k + n])]
+                k += n
+        return (None, dx) + tuple(grads)

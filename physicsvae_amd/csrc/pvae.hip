@@ -5,6 +5,7 @@
 // Reference lines restated by each kernel are cited at the kernel (tpv / tm / rmt as in
 // include/pvae.h).
 #include "pvae_internal.h"
+#include "pvae_fc_layout.h"
 
 // ---------------------------------------------------------------------------------------
 // glue kernels
@@ -1234,6 +1235,7 @@ int pvae_set_option(pvae_ctx* c, const char* name, int64_t value) {
         else if (k == "wgrad32") g_wgrad32 = v;
         else if (k == "look_pair") g_look_pair = v != 0;
         else if (k == "rollout_fused") g_rollout_fused = v != 0;
+        else if (k == "fc_per_stack") g_fc_per_stack = v != 0;
         else return fail(-1, "unknown process-wide option '%s'", name);
         return 0;
     }

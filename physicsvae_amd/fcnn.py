@@ -1,0 +1,151 @@
+"""FullyConnectedPolicy ("fcnn"; reference: rllib_model_torch.py rmt:323-457) on the grouped HIP stack kernels.
+
+The reference's other custom model, used by the imitation specs (`custom_model: fcnn`): a policy stack, a value stack
+and -- with `log_std_type: state_dependent` -- a log-std stack, each a small FC (256x2 / 64x2 by default) on the same
+observation.  Kept from the reference so that specs, checkpoints and callers drop in unchanged:
+  * `DEFAULT_CONFIG`, the constructor (obs_space, action_space, num_outputs, model_config, name)
+  * sub-module names -> state_dict keys `_policy_fn._model.<i>._model.0.{weight,bias}`, `_policy_fn._model.<n>.log_std`
+    ("state_independent"), `_value_fn.*`, `_log_std_fn.*` with shapes [n_out, n_in] / [n_out]
+  * forward(input_dict, state, seq_lens) -> (logits, state), value_function(), set_exploration_std,
+    save_policy_weights / load_policy_weights
+
+What is different by design: the parameters of all stacks are strided views into ONE flat device arena owned by a
+`StackSetEngine` (include/pvae.h `pvae_fc_*`), and a forward is ONE library call in which every layer depth of all stacks is
+one launch -- the value is computed in that same call, since the observation is shared.  Under autograd the call goes
+through `autograd.HipStackSet`.  There is no CPU fallback: without a GPU the forward raises.
+"""
+import copy
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import autograd as AG
+from .engine import StackSetEngine
+from .model import FC, _fc_stack, _portable, fc_spec
+
+DEFAULT_FC_64X2 = fc_spec(64, 2)
+DEFAULT_FC_256X2 = fc_spec(256, 2)
+
+
+class FullyConnectedPolicy(nn.Module):
+    """A policy that generates action and value with FCNN (rmt:323-457)."""
+
+    DEFAULT_CONFIG = {
+        "log_std_type": "constant",
+        "sample_std": 1.0,
+        "policy_fn_type": "mlp",
+        "policy_fn_layers": DEFAULT_FC_256X2,
+        "log_std_fn_layers": DEFAULT_FC_64X2,
+        "value_fn_layers": DEFAULT_FC_256X2,
+        # ours: where the arena lives and how many rows one library call may carry (larger batches run in chunks);
+        # 512 covers the specs' sgd_minibatch_size of 500 in one call
+        "device": None,
+        "max_batch": 512,
+    }
+
+    def __init__(self, obs_space, action_space, num_outputs, model_config, name, **model_kwargs):
+        super().__init__()
+        self.obs_space, self.action_space = obs_space, action_space
+        self.model_config, self.name = model_config, name
+        cfg = copy.deepcopy(FullyConnectedPolicy.DEFAULT_CONFIG)
+        cfg.update(model_config.get("custom_model_config") or {})
+        log_std_type = cfg.get("log_std_type")
+        assert log_std_type in ["constant", "state_independent", "state_dependent"]            # rmt:364-366
+        sample_std = cfg.get("sample_std")
+        assert np.array(sample_std).all() > 0.0, "The value shoulde be positive"                # rmt:368-370
+        assert num_outputs % 2 == 0, ("num_outputs must be divisible by two", num_outputs)      # rmt:372-374
+        self.num_outputs = num_outputs
+        n_act = num_outputs // 2
+        if cfg.get("policy_fn_type") != "mlp":
+            raise NotImplementedError(cfg.get("policy_fn_type"))                               # rmt:398-399
+        self.dim_state = int(np.prod(obs_space.shape))
+        state_dependent = log_std_type == "state_dependent"
+
+        specs = [("_policy_fn", "policy_fn_layers", n_act), ("_value_fn", "value_fn_layers", 1)]
+        if state_dependent:
+            specs.append(("_log_std_fn", "log_std_fn_layers", n_act))
+        parsed = [_fc_stack(cfg[key], key) for _, key, _ in specs]      # (bn / softmax / hardmax / swish / non-linear output: refused by name)
+        device = cfg["device"] or ("cuda" if torch.cuda.is_available() else "cpu")
+        self.engine = StackSetEngine(self.dim_state, [(st, n) for (st, _), (_, _, n) in zip(parsed, specs)],
+                                     int(cfg["max_batch"]), device=device)
+
+        def build(s, **kw):
+            dims = [(l["n_in"], l["n_out"]) for l in self.engine.stack_layers(s)]
+            return FC(dims, views=self.engine.views(s), act=parsed[s][0].acts, inits=parsed[s][1], **kw)
+
+        # registration order fixes the state_dict order: policy, value, [log-std] (rmt:386-427)
+        if state_dependent:
+            self._policy_fn = build(0)
+        else:
+            self._policy_fn = build(0, append_log_std=True, sample_std=1.0, log_std_type=log_std_type,
+                                    device=self.engine.device)
+            with torch.no_grad():                  # (rmt:266-270: init_val = np.log(sample_std), a scalar or one value per action)
+                init = torch.as_tensor(np.log(np.asarray(sample_std, dtype=np.float64)) * np.ones(n_act), dtype=torch.float32)
+                self._policy_fn._model[-1].log_std.copy_(init)
+        self._value_fn = build(1)
+        self._log_std_fn = None
+        if state_dependent:
+            self._log_std_fn = build(2)
+            self._log_std_base = np.log(sample_std)
+            self.__dict__["_ls_base"] = torch.as_tensor(np.asarray(self._log_std_base, dtype=np.float64) * np.ones(n_act),
+                                                        dtype=torch.float32, device=self.engine.device)
+        self._cur_value = None
+
+    # -- nn.Module plumbing ---------------------------------------------------------------
+    def _apply(self, fn, recurse=True):
+        """`.to()/.cuda()/.float()` would re-allocate the arena-backed parameters and break the aliasing; the device is
+        chosen at construction (custom_model_config['device'])."""
+        probe = fn(torch.zeros(1, device=self.engine.device))
+        if probe.device.type != self.engine.device.type or probe.dtype != torch.float32:
+            raise RuntimeError("FullyConnectedPolicy lives on %s/float32 (chosen at construction); rebuild it with "
+                               "custom_model_config['device'] instead of .to()" % self.engine.device)
+        return self
+
+    def get_initial_state(self):
+        return []
+
+    def __call__(self, input_dict, state=None, seq_lens=None):
+        # ModelV2.__call__ semantics: obs_flat = obs, then forward
+        d = dict(input_dict)
+        d["obs_flat"] = d["obs"] if "obs" in d else d["obs_flat"]
+        return self.forward(d, state or [], seq_lens)
+
+    def _params(self):
+        out = []
+        for fn in (self._policy_fn, self._value_fn, self._log_std_fn):
+            if fn is not None:
+                out += AG.stack_params(fn)
+        return out
+
+    # -- forward (rmt:429-441): one library call for the policy, the value and the log-std ---------------
+    def forward(self, input_dict, state, seq_lens):
+        obs = input_dict["obs_flat"].float()
+        obs = obs.reshape(obs.shape[0], -1)
+        self.engine._need_gpu()
+        params = self._params()
+        if torch.is_grad_enabled() and (obs.requires_grad or any(p.requires_grad for p in params)):
+            outs = AG.HipStackSet.apply(self.engine, obs, *params)
+        else:
+            outs = AG.stack_set_forward(self.engine, obs.to(self.engine.device).contiguous())
+        self._cur_value = outs[1].squeeze(1)
+        if self._log_std_fn is not None:
+            logits = torch.cat([outs[0], self.__dict__["_ls_base"] + outs[2]], dim=-1)
+        else:
+            logits = self._policy_fn._model[-1](outs[0])                       # AppendLogStd (rmt:194-206)
+        return logits, state
+
+    def value_function(self):
+        assert self._cur_value is not None, "must call forward() first"
+        return self._cur_value
+
+    def set_exploration_std(self, std):
+        self._policy_fn._model[-1].set_val(math.log(std))                         # rmt:448-450
+
+    def save_policy_weights(self, file):
+        torch.save(_portable(self._policy_fn.state_dict()), file)                 # rmt:452-453
+
+    def load_policy_weights(self, file):
+        self._policy_fn.load_state_dict(torch.load(file, map_location="cpu"))     # rmt:455-457
+        self._policy_fn.eval()
