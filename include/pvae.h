@@ -723,6 +723,89 @@ int pvae_fc_ppo_launches(pvae_fc* fc, int32_t* per_step);
 /* sizeof(pvae_fc_ppo_params) / sizeof(pvae_fc_ppo_batch) as the library was compiled (binding self-check): which = 0 / 1 */
 int pvae_fc_ppo_sizeof(int which);
 
+/* ---- Train-batch preparation for the PPO learner: evaluate, bootstrap, GAE, standardisation ---------------------------
+ * What RLlib 1.11 does on the host between rollout and SGD (postprocessing.compute_advantages + standardized), on the
+ * device, so that a learner needs only obs, actions, rewards and the fragment table there and hands the result straight
+ * to pvae_fc_ppo_sgd.  A SEGMENT is a run of consecutive rows of one episode in time order (what RLlib postprocesses as one
+ * trajectory): segment s = rows seg_start[s] .. seg_start[s + 1] - 1; last_value[s] = 0 if it ended its episode
+ * (seg_done[s]), else the value function at the observation after its last row (boot_obs[s]).  Rows t of a segment, last
+ * row first (adv past the end = 0, v_next of the last row = last_value[s]):
+ *   delta[t] = rewards[t] + gamma v_next[t] - vf_preds[t];  adv[t] = delta[t] + gamma lambda adv[t + 1]
+ *   value_targets[t] = adv[t] + vf_preds[t]
+ * then, over all n_rows rows and only with `standardize` (population std):
+ *   advantages = (adv - mean(adv)) / max(1e-4, std(adv))
+ *
+ * Launches.  Evaluate: per chunk of max_batch rows the stack set's forward (copy-in + one per layer depth) + ONE epilogue
+ * that reads the stacks' outputs in their panels and writes vf_preds[r], old_dist[r] = [mean | log_std] and old_logp[r] of
+ * actions[r] (the loss head's logp, term for term; log_std by kind as in the PPO step, the vector taken from
+ * pvae_fc_ppo_bind).  Bootstrap: the same path with the value stack alone over boot_obs; the copy-in never reads the row of
+ * a done segment and the epilogue writes last_value[s] = 0 for it.  GAE: ONE launch, a wavefront per segment walking it
+ * from its end in 64-row pieces (a wave scan per piece, the carry passed on), any segment length >= 1; it leaves per-
+ * workgroup sums of adv and adv^2, in double, in the scratch.  Standardise: ONE launch, every workgroup adds those partials
+ * in the same order and rescales its slice in place; skipped when standardize == 0.  No atomics, no host synchronisation,
+ * no allocation: the same inputs give the same bits.
+ *
+ * seg_start lives on the device, so the library cannot read it without a synchronisation: the caller passes the two ends
+ * it wrote (seg_first = seg_start[0], seg_last = seg_start[n_segs]), which must be 0 and n_rows; that the table increases
+ * in between is the caller's contract.  The kernels clamp every bound into [0, n_rows]: a table that breaks the contract
+ * gives wrong numbers, never an access outside the columns.
+ *
+ *   pvae_fc_gae_workspace_bytes   size of the scratch (the partial sums) for n_segs segments, a multiple of 16; 0 on error
+ *   pvae_gae               the dense form, no stack set: rewards / vf_preds [n_rows], last_values [n_segs] (read as 0 where
+ *                          seg_done[s]; seg_done NULL: as given) -> advantages, value_targets [n_rows].  Returns the
+ *                          number of launches it enqueued (2, or 1 without standardize).
+ *   pvae_fc_ppo_evaluate   the evaluate pass alone: the rows (when out->vf_preds is given; then old_dist and old_logp too)
+ *                          and / or the bootstrap values (when out->last_value is given).
+ *   pvae_fc_ppo_prepare    all of it on one stream: evaluate -- or, when the rollout carries the sampler's own vf_preds,
+ *                          old_dist and old_logp (all three or none), those as they are and no evaluate launch over the
+ *                          rows --, bootstrap, GAE, standardise.
+ *   pvae_fc_gae_launches   launches of the last pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate on this context: the evaluate
+ *                          pass over the rows, and the rest (bootstrap + GAE + standardise).
+ * Bad arguments (ends of seg_start that are not 0 and n_rows, n_segs < 1, a stack set that is not [policy, value(,
+ * log-std)], an unbound buffer, a short scratch) return a negative code and launch nothing. */
+typedef struct pvae_gae_params {
+    float gamma, lambda;
+    int32_t standardize;    /* 0: the raw advantages, no rescale launch */
+    int32_t log_std_kind;   /* evaluate: 0 constant, 1 state_independent, 2 state_dependent (as pvae_fc_ppo_params) */
+    float log_std_base;     /* kind 2: log_std = log_std_base + third stack */
+    int32_t reserved;
+} pvae_gae_params;
+typedef struct pvae_fc_rollout {
+    const float* obs;             /* [n_rows][n_in] */
+    const float* actions;         /* [n_rows][k] */
+    const float* rewards;         /* [n_rows] */
+    const int32_t* seg_start;     /* [n_segs + 1], increasing from 0 to n_rows */
+    const uint8_t* seg_done;      /* [n_segs]: the segment ended its episode */
+    const float* boot_obs;        /* [n_segs][n_in]: the observation after each segment's last row (done: never read) */
+    const float* vf_preds;        /* the sampler's own columns, all three or none (NULL): [n_rows] */
+    const float* old_dist;        /* [n_rows][2k] */
+    const float* old_logp;        /* [n_rows] */
+    int64_t n_rows;
+    int32_t n_segs;
+    int32_t k;                    /* actions per row */
+    int64_t seg_first, seg_last;  /* seg_start[0] and seg_start[n_segs] as the caller wrote them */
+} pvae_fc_rollout;
+typedef struct pvae_fc_prepared {
+    float* vf_preds;              /* [n_rows]     written by evaluate (may be NULL when the sampler's are given) */
+    float* old_dist;              /* [n_rows][2k] */
+    float* old_logp;              /* [n_rows] */
+    float* last_value;            /* [n_segs] */
+    float* advantages;            /* [n_rows] */
+    float* value_targets;         /* [n_rows] */
+} pvae_fc_prepared;
+size_t pvae_fc_gae_workspace_bytes(int32_t n_segs);
+int pvae_gae(const float* rewards, const float* vf_preds, const float* last_values, const int32_t* seg_start,
+             const uint8_t* seg_done, int64_t n_rows, int32_t n_segs, int64_t seg_first, int64_t seg_last,
+             const pvae_gae_params* params, float* advantages, float* value_targets, void* scratch, size_t scratch_bytes,
+             void* stream);
+int pvae_fc_ppo_evaluate(pvae_fc* fc, const pvae_fc_rollout* rollout, const pvae_gae_params* params,
+                         const pvae_fc_prepared* out, void* stream);
+int pvae_fc_ppo_prepare(pvae_fc* fc, const pvae_fc_rollout* rollout, const pvae_gae_params* params,
+                        const pvae_fc_prepared* out, void* scratch, size_t scratch_bytes, void* stream);
+int pvae_fc_gae_launches(pvae_fc* fc, int32_t* evaluate, int32_t* rest);
+/* sizeof(pvae_gae_params) / sizeof(pvae_fc_rollout) / sizeof(pvae_fc_prepared) as the library was compiled: which = 0 / 1 / 2 */
+int pvae_gae_sizeof(int which);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

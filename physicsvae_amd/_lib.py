@@ -93,6 +93,24 @@ class FcPpoBatch(C.Structure):
                                           "vf_preds")] + [("n_rows", C.c_int64), ("k", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GaeParams(C.Structure):
+    """pvae_gae_params: the discount, GAE's lambda, whether the advantages are standardised; for evaluate the log-std kind."""
+    _fields_ = [("gamma", C.c_float), ("lambda_", C.c_float), ("standardize", C.c_int32), ("log_std_kind", C.c_int32),
+                ("log_std_base", C.c_float), ("reserved", C.c_int32)]
+
+
+class FcRollout(C.Structure):
+    """pvae_fc_rollout: device pointers to a rollout's columns and its segment table."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "actions", "rewards", "seg_start", "seg_done", "boot_obs", "vf_preds",
+                                          "old_dist", "old_logp")] + [
+        ("n_rows", C.c_int64), ("n_segs", C.c_int32), ("k", C.c_int32), ("seg_first", C.c_int64), ("seg_last", C.c_int64)]
+
+
+class FcPrepared(C.Structure):
+    """pvae_fc_prepared: device pointers to the columns train-batch preparation writes."""
+    _fields_ = [(n, C.c_void_p) for n in ("vf_preds", "old_dist", "old_logp", "last_value", "advantages", "value_targets")]
+
+
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
 
 _P = C.c_void_p
@@ -186,6 +204,14 @@ _SIGS = {
     "pvae_fc_ppo_sgd": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.c_int32, C.POINTER(FcPpoParams), _P, _P]),
     "pvae_fc_ppo_launches": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "pvae_fc_ppo_sizeof": (C.c_int, [C.c_int]),
+    "pvae_fc_gae_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pvae_gae": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(GaeParams), _P, _P, _P,
+                           C.c_size_t, _P]),
+    "pvae_fc_ppo_evaluate": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(FcPrepared), _P]),
+    "pvae_fc_ppo_prepare": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(FcPrepared), _P, C.c_size_t,
+                                      _P]),
+    "pvae_fc_gae_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pvae_gae_sizeof": (C.c_int, [C.c_int]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),

@@ -31,6 +31,7 @@ struct pvae_fc {
     float* log_std_m = nullptr;
     float* log_std_v = nullptr;
     int ppo_launches = 0;
+    int eval_launches = 0, gae_launches = 0;      // pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate (pvae_fc_gae_launches)
 };
 
 namespace {
@@ -405,6 +406,156 @@ fc_adam_kernel(FcAdam a) {
         reinterpret_cast<v4f*>(a.m)[q] = mm;
         reinterpret_cast<v4f*>(a.v)[q] = vv;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// train-batch preparation: evaluate epilogue, GAE, standardisation (include/pvae.h "Train-batch preparation")
+// ---------------------------------------------------------------------------------------
+// input panel of the bootstrap pass: fc_pad_copy_kernel, except that row r of a segment that ended its episode (done[r])
+// is zeros and its source row is never read
+__global__ void __launch_bounds__(256)
+fc_boot_copy_kernel(const float* __restrict__ src, int n, int rows, float* __restrict__ dst, int ld, int rows_pad,
+                    const uint8_t* __restrict__ done) {
+    const int total = rows_pad * ld;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / ld, c = idx - r * ld;
+        dst[idx] = (r < rows && c < n && !done[r]) ? src[(size_t)r * n + c] : 0.f;
+    }
+}
+
+// The epilogue of one evaluated chunk: a wave per row reads the stacks' outputs in their panels and writes vf[r],
+// dist[r] = [mean | log_std] and logp[r] of actions[r] -- the arithmetic of fc_ppo_head_kernel's logp, term for term, so
+// that the learner's first step sees a ratio of exactly 1.  mean == NULL: the bootstrap use -- the value stack ran alone;
+// vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.
+constexpr int kEvalMaxBlocks = 1024;
+struct FcEval {
+    const float* mean; const float* ls; const float* value;
+    long long ld_mean, ld_ls, ld_value;
+    float ls_base;
+    const float* actions;
+    const uint8_t* done;
+    int rows, k;
+    float* vf; float* dist; float* logp;
+};
+__global__ void __launch_bounds__(256)
+fc_eval_epilogue_kernel(FcEval e) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int k = e.k;
+    for (int r = wave; r < e.rows; r += waves) {
+        if (!e.mean) {
+            if (lane == 0) e.vf[r] = e.done[r] ? 0.f : e.value[r * e.ld_value];
+            continue;
+        }
+        const float* mu = e.mean + r * e.ld_mean;
+        const float* ls = e.ls + r * e.ld_ls;
+        const float* act = e.actions + (size_t)r * k;
+        float* dist = e.dist + (size_t)r * 2 * k;
+        float zz = 0.f, lss = 0.f;
+        for (int j = lane; j < k; j += 64) {
+            const float l = e.ls_base + ls[j], inv_sig = expf(-l);
+            const float z = (act[j] - mu[j]) * inv_sig;
+            zz = fmaf(z, z, zz);
+            lss += l;
+            dist[j] = mu[j];
+            dist[k + j] = l;
+        }
+        zz = wave_sum(zz); lss = wave_sum(lss);
+        if (lane == 0) {
+            e.logp[r] = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                  // log(2 pi)
+            e.vf[r] = e.value[r * e.ld_value];
+        }
+    }
+}
+
+// GAE: adv[t] = delta[t] + gamma lambda adv[t + 1] inside a segment, a reverse linear recurrence.  One wavefront per
+// segment (wave w takes segments w, w + waves, ...) walks it from its end in 64-row pieces: lane l holds the row l places
+// before the piece's last one, the piece is an inclusive wave scan of the pairs (c, delta) under
+// (a2, b2) o (a1, b1) = (a1 a2, b2 + a2 b1), and the advantage of the row after the piece is the carry into it.  Segment
+// bounds are clamped into [0, n_rows]: a bad table cannot make the kernel touch memory outside the columns.  Every
+// workgroup leaves the sums of adv and adv^2 over its waves' rows, in double, in part[block][2]: no atomics, the
+// standardisation adds them in block order.
+constexpr int kGaeMaxBlocks = 1024;
+struct GaeArgs {
+    const float* rewards; const float* vpred; const float* last_value;
+    const uint8_t* done;                  // null: last_value as given
+    const int32_t* seg_start;
+    long long n_rows;
+    int n_segs;
+    float gamma, c;                       // c = gamma lambda
+    float* adv; float* vtarg;
+    double* part;
+};
+__device__ inline double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ void __launch_bounds__(256)
+fc_gae_kernel(GaeArgs g) {
+    __shared__ double red[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wave = blockIdx.x * 4 + wv, waves = gridDim.x * 4;
+    double s1 = 0.0, s2 = 0.0;
+    for (int s = wave; s < g.n_segs; s += waves) {
+        long long a = g.seg_start[s], b = g.seg_start[s + 1];
+        a = a < 0 ? 0 : (a > g.n_rows ? g.n_rows : a);
+        b = b < a ? a : (b > g.n_rows ? g.n_rows : b);
+        if (b <= a) continue;             // (the same for every lane of the wave)
+        const float last = (g.done && g.done[s]) ? 0.f : g.last_value[s];
+        float carry = 0.f;
+        for (long long hi = b; hi > a; hi -= 64) {
+            const long long t = hi - 1 - lane;
+            const bool live = t >= a;
+            float pa = 1.f, pb = 0.f, v = 0.f;
+            if (live) {
+                v = g.vpred[t];
+                const float vn = t + 1 < b ? g.vpred[t + 1] : last;
+                pb = g.rewards[t] + g.gamma * vn - v;
+                pa = g.c;
+            }
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float qa = __shfl_up(pa, o, 64), qb = __shfl_up(pb, o, 64);
+                if (lane >= o) { pb = fmaf(pa, qb, pb); pa *= qa; }
+            }
+            const float x = fmaf(pa, carry, pb);
+            carry = __shfl(x, 63, 64);
+            if (live) {
+                g.adv[t] = x;
+                g.vtarg[t] = x + v;
+                s1 += (double)x;
+                s2 += (double)x * (double)x;
+            }
+        }
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    if (lane == 0) { red[wv][0] = s1; red[wv][1] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        g.part[(size_t)blockIdx.x * 2 + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// advantages = (adv - mean) / max(1e-4, std), population std: every workgroup adds the GAE launch's partial sums in the
+// same order (thread i the partials i, i + 256, ..., then a tree over the threads) and rescales its slice in place
+__global__ void __launch_bounds__(256)
+fc_standardize_kernel(float* __restrict__ adv, long long n, const double* __restrict__ part, int nparts) {
+    __shared__ double sh[2][256];
+    const int tid = threadIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int i = tid; i < nparts; i += 256) { a += part[2 * (size_t)i]; b += part[2 * (size_t)i + 1]; }
+    sh[0][tid] = a; sh[1][tid] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { sh[0][tid] += sh[0][tid + o]; sh[1][tid] += sh[1][tid + o]; }
+        __syncthreads();
+    }
+    const double mean = sh[0][0] / (double)n;
+    double var = sh[1][0] / (double)n - mean * mean;
+    if (!(var > 0.0)) var = 0.0;
+    const double sd = sqrt(var), inv = 1.0 / (sd > 1e-4 ? sd : 1e-4);
+    for (long long i = blockIdx.x * 256ll + tid; i < n; i += gridDim.x * 256ll) adv[i] = (float)(((double)adv[i] - mean) * inv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -854,6 +1005,163 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
     return 0;
 }
 
+// ---- train-batch preparation, host side ----
+int gae_blocks(int n_segs) {
+    const int b = (n_segs + 3) / 4;
+    return b > kGaeMaxBlocks ? kGaeMaxBlocks : (b < 1 ? 1 : b);
+}
+size_t gae_scratch_bytes(int n_segs) { return (size_t)gae_blocks(n_segs) * 2 * sizeof(double); }
+
+int check_gae_params(const pvae_gae_params* p) {
+    if (!p) return fail(-1, "null params");
+    if (!(p->gamma >= 0.f && p->gamma <= 1.f) || !(p->lambda >= 0.f && p->lambda <= 1.f))
+        return fail(-1, "gamma and lambda must lie in [0, 1]");
+    return 0;
+}
+
+int check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last) {
+    if (n_rows < 1 || n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", n_rows);
+    if (n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", n_segs);
+    if (n_segs > n_rows) return fail(-1, "n_segs %d > n_rows %lld: a segment has at least one row", n_segs, n_rows);
+    if (seg_first != 0 || seg_last != n_rows)
+        return fail(-1, "seg_start must run from 0 to n_rows %lld, got %lld .. %lld", n_rows, seg_first, seg_last);
+    return 0;
+}
+
+int check_gae_scratch(const void* scratch, size_t bytes, int n_segs) {
+    if (!scratch) return fail(-1, "scratch is null");
+    if ((uintptr_t)scratch & 15) return fail(-1, "scratch must be 16-byte aligned");
+    if (bytes < gae_scratch_bytes(n_segs)) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, gae_scratch_bytes(n_segs));
+    return 0;
+}
+
+// the GAE launch and, with `standardize`, the rescale launch (arguments checked by the caller); `launches` counts them
+int run_gae(const float* rewards, const float* vpred, const float* last_value, const uint8_t* done, const int32_t* seg_start,
+            long long n_rows, int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st,
+            int& launches) {
+    GaeArgs g;
+    memset(&g, 0, sizeof(g));
+    g.rewards = rewards; g.vpred = vpred; g.last_value = last_value; g.done = done; g.seg_start = seg_start;
+    g.n_rows = n_rows; g.n_segs = n_segs; g.gamma = p->gamma; g.c = p->gamma * p->lambda;
+    g.adv = adv; g.vtarg = vtarg; g.part = (double*)scratch;
+    const int blocks = gae_blocks(n_segs);
+    hipLaunchKernelGGL(fc_gae_kernel, dim3(blocks), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    if (p->standardize) {
+        long long grid = (n_rows + 255) / 256;
+        if (grid > 1024) grid = 1024;
+        hipLaunchKernelGGL(fc_standardize_kernel, dim3((int)grid), dim3(256), 0, st, adv, n_rows, (const double*)scratch, blocks);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    return 0;
+}
+
+// what evaluate and prepare ask of the stack set; `rows_pass`: the policy's distribution is evaluated (its log-std is needed)
+int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) {
+    if (!c) return fail(-1, "null stack set");
+    if (!ro || !p || !out) return fail(-1, "null rollout, params or outputs");
+    if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
+    const FcLayout& L = c->L;
+    if (L.S < 2 || L.S > 3) return fail(-1, "a PPO learner needs [policy, value] or [policy, value, log-std] stacks, got %d", L.S);
+    if (L.cfg.n_out[1] != 1) return fail(-1, "stacks in the wrong order: stack 1 must be the value function (n_out 1, got %d)", L.cfg.n_out[1]);
+    if (L.S == 3 && L.cfg.n_out[2] != L.cfg.n_out[0])
+        return fail(-1, "stacks in the wrong order: the log-std stack (2) must be as wide as the policy stack (0)");
+    if (ro->n_rows < 1 || ro->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)ro->n_rows);
+    if (rows_pass) {
+        if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
+        if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
+        if (ro->k != L.cfg.n_out[0]) return fail(-1, "rollout k %d != policy outputs %d", ro->k, L.cfg.n_out[0]);
+        if (p->log_std_kind != 2 && !c->log_std) return fail(-2, "log_std vector not bound (pvae_fc_ppo_bind)");
+        if (!ro->obs || !ro->actions) return fail(-1, "rollout obs or actions is null");
+        if (!out->vf_preds || !out->old_dist || !out->old_logp) return fail(-1, "an evaluate output (vf_preds, old_dist, old_logp) is null");
+    }
+    return 0;
+}
+
+int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) {
+    if (ro->n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", ro->n_segs);
+    if (!ro->boot_obs || !ro->seg_done) return fail(-1, "rollout boot_obs or seg_done is null");
+    if (!out->last_value) return fail(-1, "last_value is null");
+    return 0;
+}
+
+void fill_eval_value(FcEval& e, const pvae_fc* c) {
+    const int lv = (int)c->L.stack[1].size() - 1;
+    e.value = act_ptr(c, 1, lv); e.ld_value = panel_ld(c, 1, lv);
+}
+
+int launch_eval_epilogue(Run& r, const FcEval& e) {
+    int blocks = (e.rows + 3) / 4;
+    if (blocks > kEvalMaxBlocks) blocks = kEvalMaxBlocks;
+    hipLaunchKernelGGL(fc_eval_epilogue_kernel, dim3(blocks), dim3(256), 0, r.st, e);
+    HIP_TRY(hipGetLastError());
+    ++r.launches;
+    return 0;
+}
+
+// rows of the rollout through all stacks in chunks of max_batch: copy-in, one launch per depth, the epilogue
+int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, hipStream_t st,
+              int& launches) {
+    const FcLayout& L = c->L;
+    const int k = ro->k;
+    for (long long first = 0; first < ro->n_rows; first += L.cfg.max_batch) {
+        const int rows = (int)(ro->n_rows - first < L.cfg.max_batch ? ro->n_rows - first : L.cfg.max_batch);
+        Run r{c, st, rows, pad32(rows)};
+        for (int s = 0; s < L.S; ++s) r.want[s] = true;
+        set_range(r, L.S);
+        int rc;
+        if ((rc = copy_in(r, ro->obs + (size_t)first * L.cfg.n_in))) return rc;
+        if ((rc = run_forward(r, nullptr))) return rc;
+        FcEval e;
+        memset(&e, 0, sizeof(e));
+        const int lp = (int)L.stack[0].size() - 1;
+        e.mean = act_ptr(c, 0, lp); e.ld_mean = panel_ld(c, 0, lp);
+        fill_eval_value(e, c);
+        if (p->log_std_kind == 2) {
+            const int ll = (int)L.stack[2].size() - 1;
+            e.ls = act_ptr(c, 2, ll); e.ld_ls = panel_ld(c, 2, ll); e.ls_base = p->log_std_base;
+        } else {
+            e.ls = c->log_std; e.ld_ls = 0;
+        }
+        e.actions = ro->actions + (size_t)first * k;
+        e.rows = rows; e.k = k;
+        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
+        if ((rc = launch_eval_epilogue(r, e))) return rc;
+        launches += r.launches;
+    }
+    return 0;
+}
+
+// last_value[s] = seg_done[s] ? 0 : value(boot_obs[s]): the value stack alone, in chunks of max_batch
+int eval_boot(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st, int& launches) {
+    const FcLayout& L = c->L;
+    for (int first = 0; first < ro->n_segs; first += L.cfg.max_batch) {
+        const int rows = ro->n_segs - first < L.cfg.max_batch ? ro->n_segs - first : L.cfg.max_batch;
+        Run r{c, st, rows, pad32(rows)};
+        r.want[1] = true;
+        set_range(r, L.S);
+        int grid = (r.rows_pad * L.ld0 + 255) / 256;
+        if (grid > 1024) grid = 1024;
+        hipLaunchKernelGGL(fc_boot_copy_kernel, dim3(grid), dim3(256), 0, st, ro->boot_obs + (size_t)first * L.cfg.n_in,
+                           L.cfg.n_in, rows, c->ws + c->W.in, L.ld0, r.rows_pad, ro->seg_done + first);
+        HIP_TRY(hipGetLastError());
+        ++r.launches;
+        int rc;
+        if ((rc = run_forward(r, nullptr))) return rc;
+        FcEval e;
+        memset(&e, 0, sizeof(e));
+        fill_eval_value(e, c);
+        e.done = ro->seg_done + first;
+        e.rows = rows; e.k = ro->k;
+        e.vf = out->last_value + first;
+        if ((rc = launch_eval_epilogue(r, e))) return rc;
+        launches += r.launches;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1075,6 +1383,79 @@ int pvae_fc_ppo_sgd(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* perm,
 int pvae_fc_ppo_launches(pvae_fc* c, int32_t* per_step) {
     if (!c || !per_step) return fail(-1, "null argument");
     *per_step = c->ppo_launches;
+    return 0;
+}
+
+size_t pvae_fc_gae_workspace_bytes(int32_t n_segs) {
+    if (n_segs < 1) { fail(-1, "n_segs must be >= 1, got %d", n_segs); return 0; }
+    return (gae_scratch_bytes(n_segs) + 15) / 16 * 16;
+}
+
+int pvae_gae_sizeof(int which) {
+    return which == 0 ? (int)sizeof(pvae_gae_params) : which == 1 ? (int)sizeof(pvae_fc_rollout)
+         : which == 2 ? (int)sizeof(pvae_fc_prepared) : fail(-1, "which must be 0, 1 or 2");
+}
+
+int pvae_gae(const float* rewards, const float* vf_preds, const float* last_values, const int32_t* seg_start,
+             const uint8_t* seg_done, int64_t n_rows, int32_t n_segs, int64_t seg_first, int64_t seg_last,
+             const pvae_gae_params* p, float* advantages, float* value_targets, void* scratch, size_t scratch_bytes,
+             void* stream) {
+    int rc = check_gae_params(p);
+    if (rc) return rc;
+    if (!rewards || !vf_preds || !last_values || !seg_start) return fail(-1, "rewards, vf_preds, last_values or seg_start is null");
+    if (!advantages || !value_targets) return fail(-1, "an output is null");
+    if ((rc = check_segments(n_rows, n_segs, seg_first, seg_last))) return rc;
+    if ((rc = check_gae_scratch(scratch, scratch_bytes, n_segs))) return rc;
+    int launches = 0;
+    if ((rc = run_gae(rewards, vf_preds, last_values, seg_done, seg_start, n_rows, n_segs, p, advantages, value_targets, scratch,
+                      (hipStream_t)stream, launches)))
+        return rc;
+    return launches;
+}
+
+int pvae_fc_ppo_evaluate(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
+                         void* stream) {
+    const bool rows_pass = out && out->vf_preds, boot = out && out->last_value;
+    int rc = check_eval(c, ro, p, out, rows_pass);
+    if (rc) return rc;
+    if (!rows_pass && !boot) return fail(-1, "neither vf_preds nor last_value: nothing to compute");
+    if (boot && (rc = check_boot(ro, out))) return rc;
+    int ev = 0, rest = 0;
+    if (rows_pass && (rc = eval_rows(c, ro, p, out, (hipStream_t)stream, ev))) return rc;
+    if (boot && (rc = eval_boot(c, ro, out, (hipStream_t)stream, rest))) return rc;
+    c->eval_launches = ev; c->gae_launches = rest;
+    return 0;
+}
+
+int pvae_fc_ppo_prepare(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
+                        void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_gae_params(p);
+    if (rc) return rc;
+    if (!ro || !out) return fail(-1, "null rollout or outputs");
+    const int given = (ro->vf_preds != nullptr) + (ro->old_dist != nullptr) + (ro->old_logp != nullptr);
+    if (given != 0 && given != 3) return fail(-1, "the sampler's vf_preds, old_dist and old_logp go together: all three or none");
+    if ((rc = check_eval(c, ro, p, out, given == 0))) return rc;
+    if ((rc = check_boot(ro, out))) return rc;
+    if (!ro->rewards || !ro->seg_start) return fail(-1, "rollout rewards or seg_start is null");
+    if (!out->advantages || !out->value_targets) return fail(-1, "advantages or value_targets is null");
+    if ((rc = check_segments(ro->n_rows, ro->n_segs, ro->seg_first, ro->seg_last))) return rc;
+    if ((rc = check_gae_scratch(scratch, scratch_bytes, ro->n_segs))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int ev = 0, rest = 0;
+    if (given == 0 && (rc = eval_rows(c, ro, p, out, st, ev))) return rc;
+    if ((rc = eval_boot(c, ro, out, st, rest))) return rc;
+    // (last_value already holds the zeros of the done segments)
+    if ((rc = run_gae(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, nullptr, ro->seg_start, ro->n_rows,
+                      ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))
+        return rc;
+    c->eval_launches = ev; c->gae_launches = rest;
+    return 0;
+}
+
+int pvae_fc_gae_launches(pvae_fc* c, int32_t* evaluate, int32_t* rest) {
+    if (!c) return fail(-1, "null stack set");
+    if (evaluate) *evaluate = c->eval_launches;
+    if (rest) *rest = c->gae_launches;
     return 0;
 }
 

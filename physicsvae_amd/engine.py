@@ -1081,6 +1081,109 @@ class StackSetEngine:
         _lib.check(self.lib.pvae_fc_ppo_launches(self.ctx, C.byref(n)), "pvae_fc_ppo_launches")
         return n.value
 
+    # -- train-batch preparation (include/pvae.h "Train-batch preparation") --------------------------
+    def _rollout(self, ro, need):
+        """(pvae_fc_rollout, [tensors kept alive]) from a dict of device tensors: obs, actions, rewards, seg_start (int32
+        [S + 1]), seg_done (bool / uint8 [S]), boot_obs ([S, n_in]) and, optionally, the sampler's vf_preds / old_dist /
+        old_logp.  `need`: the names that must be there.  A `seg_start` given on the host is checked (its ends) and
+        uploaded; one on the device is taken under the caller's contract: it runs from 0 to the number of rows."""
+        k, f32 = self.n_outs[0], torch.float32
+        r, keep = _lib.FcRollout(), []
+        n = next((int(ro[c].shape[0]) for c in ("actions", "rewards", "obs") if ro.get(c) is not None), 1)
+        s = int(ro["seg_done"].shape[0])
+        shapes = {"obs": (n, self.n_in), "actions": (n, k), "rewards": (n,), "boot_obs": (s, self.n_in), "vf_preds": (n,),
+                  "old_dist": (n, 2 * k), "old_logp": (n,)}
+        for name in need:
+            if ro.get(name) is None:
+                raise KeyError("rollout lacks %s" % name)
+        for name, shape in shapes.items():
+            t = ro.get(name)
+            if t is None:
+                continue
+            t = t.reshape(t.shape[0], -1) if name in ("obs", "boot_obs") else t
+            t = t.to(self.device, f32).contiguous()
+            assert tuple(t.shape) == shape, "%s must be %s, got %s" % (name, shape, tuple(t.shape))
+            keep.append(t)
+            setattr(r, name, t.data_ptr())
+        done = ro["seg_done"]
+        done = done.to(self.device).contiguous()
+        assert done.dtype in (torch.bool, torch.uint8) and done.dim() == 1, "seg_done must be bool or uint8 [S]"
+        keep.append(done)
+        r.seg_done = done.data_ptr()
+        r.n_rows, r.n_segs, r.k = n, s, k
+        r.seg_first, r.seg_last = 0, n
+        if ro.get("seg_start") is not None:
+            seg, (r.seg_first, r.seg_last) = _seg_start(ro["seg_start"], s, n, self.device)
+            keep.append(seg)
+            r.seg_start = seg.data_ptr()
+        return r, keep
+
+    def _prepared(self, n, s, names, out):
+        k = self.n_outs[0]
+        shapes = {"vf_preds": (n,), "old_dist": (n, 2 * k), "old_logp": (n,), "last_value": (s,), "advantages": (n,),
+                  "value_targets": (n,)}
+        o, res = _lib.FcPrepared(), {}
+        for name in names:
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shapes[name], dtype=torch.float32, device=self.device)
+            assert t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) == shapes[name], \
+                "out[%r] must be contiguous float32 %s on %s" % (name, shapes[name], self.device)
+            res[name] = t
+            setattr(o, name, t.data_ptr())
+        return o, res
+
+    def _gae_scratch(self, n_segs):
+        need = int(self.lib.pvae_fc_gae_workspace_bytes(int(n_segs)))
+        if getattr(self, "gae_scratch", None) is None or self.gae_scratch.numel() * 8 < need:
+            self.gae_scratch = torch.zeros(need // 8 + 2, dtype=torch.float64, device=self.device)
+        return self.gae_scratch, need
+
+    def ppo_evaluate(self, rollout, params, out=None):
+        """`pvae_fc_ppo_evaluate`: the current policy and value function over a device-resident rollout, in chunks of
+        `max_batch` rows -- vf_preds [N], old_dist [N, 2k] = [mean | log_std], old_logp [N] of `actions` (when the rollout
+        has obs and actions) and last_value [S], the bootstrap values (when it has seg_done and boot_obs; 0 for a done
+        segment, whose boot_obs row is never read).  `params`: `PPOConfig.gae_params(kind, base)`; the log-std vector of a
+        constant / state-independent kind is the one `ppo_bind` bound.  Returns the dict of what was computed."""
+        self._need_gpu()
+        rows = rollout.get("obs") is not None
+        boot = rollout.get("boot_obs") is not None
+        ro = {c: rollout.get(c) for c in ("obs", "actions", "seg_done", "boot_obs")}
+        if not boot:
+            ro["seg_done"] = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        r, keep = self._rollout(ro, (("obs", "actions") if rows else ()) + (("boot_obs",) if boot else ()))
+        names = (("vf_preds", "old_dist", "old_logp") if rows else ()) + (("last_value",) if boot else ())
+        o, res = self._prepared(int(r.n_rows), int(r.n_segs), names, out)
+        _lib.check(self.lib.pvae_fc_ppo_evaluate(self.ctx, C.byref(r), C.byref(params), C.byref(o), self._stream()),
+                   "pvae_fc_ppo_evaluate")
+        return res
+
+    def ppo_prepare(self, rollout, params, out=None):
+        """`pvae_fc_ppo_prepare`: evaluate (unless the rollout carries the sampler's own vf_preds, old_dist and old_logp: all
+        three or none), bootstrap, GAE and -- with `params.standardize` -- the standardisation, all enqueued on the current
+        stream; nothing synchronises.  Returns {vf_preds, old_dist, old_logp, last_value, advantages, value_targets}; the
+        sampler's columns, when given, come back as they are.  `out`: tensors to write into, by those names."""
+        self._need_gpu()
+        r, keep = self._rollout(rollout, ("obs", "actions", "rewards", "seg_start", "boot_obs"))
+        given = [rollout.get(name) is not None for name in ("vf_preds", "old_dist", "old_logp")]
+        if any(given) and not all(given):
+            raise ValueError("the sampler's vf_preds, old_dist and old_logp go together: all three or none")
+        names = (() if all(given) else ("vf_preds", "old_dist", "old_logp")) + ("last_value", "advantages", "value_targets")
+        o, res = self._prepared(int(r.n_rows), int(r.n_segs), names, out)
+        scratch, nbytes = self._gae_scratch(r.n_segs)
+        _lib.check(self.lib.pvae_fc_ppo_prepare(self.ctx, C.byref(r), C.byref(params), C.byref(o), scratch.data_ptr(), nbytes,
+                                                self._stream()), "pvae_fc_ppo_prepare")
+        if all(given):
+            res.update({name: rollout[name] for name in ("vf_preds", "old_dist", "old_logp")})
+        return res
+
+    def gae_launches(self):
+        """(evaluate, rest): kernel launches of the last ppo_prepare / ppo_evaluate -- the pass over the rows, and bootstrap +
+        GAE + standardisation."""
+        e, r = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.pvae_fc_gae_launches(self.ctx, C.byref(e), C.byref(r)), "pvae_fc_gae_launches")
+        return e.value, r.value
+
     def launches(self):
         """(forward, backward): kernel launches of the last call of each kind."""
         f, b = C.c_int32(), C.c_int32()
@@ -1150,3 +1253,52 @@ def ppo_loss(mean, log_std, value, batch, params, index=None):
                                      d_mean.data_ptr(), d_ls.data_ptr(), d_val.data_ptr(), stats.data_ptr(),
                                      torch.cuda.current_stream(dev).cuda_stream), "pvae_ppo_loss")
     return stats, d_mean, d_ls, d_val
+
+
+def _seg_start(seg_start, n_segs, n_rows, device):
+    """(int32 device tensor [S + 1], (first, last)): a table on the host has its ends read; one already on the device cannot
+    be read without a synchronisation and is taken under the caller's contract (0 .. n_rows)."""
+    device = torch.device(device)
+    seg = torch.as_tensor(seg_start)
+    assert seg.dim() == 1 and seg.shape[0] == n_segs + 1, "seg_start must be [S + 1] = [%d], got %s" % (n_segs + 1, tuple(seg.shape))
+    assert seg.dtype in (torch.int32, torch.int64), "seg_start must hold integers"
+    ends = (int(seg[0]), int(seg[-1])) if seg.device.type == "cpu" else (0, n_rows)
+    return seg.to(device, torch.int32).contiguous(), ends
+
+
+_gae_scratch = {}
+
+
+def gae(rewards, vf_preds, last_values, seg_start, gamma, lambda_, standardize=True, seg_done=None, out=None, info=None):
+    """`pvae_gae`: GAE and the standardisation on dense device columns, no stack set (the specification: `ppo.gae_torch`,
+    `ppo.standardize_torch`).  rewards / vf_preds [N], last_values [S] (read as 0 where `seg_done`), seg_start [S + 1].
+    Returns (advantages, value_targets); `out`: a pair of tensors to write into; `info`: a dict that receives the number
+    of kernel launches.  Nothing synchronises."""
+    from .ppo import make_gae_params
+    lib = _lib.load()
+    dev = rewards.device
+    assert dev.type == "cuda", "pvae_gae needs a GPU (there is no CPU fallback)"
+    n, s = int(rewards.shape[0]), int(last_values.shape[0])
+    cols = [t.to(dev, torch.float32).contiguous() for t in (rewards, vf_preds, last_values)]
+    assert tuple(cols[1].shape) == (n,) and cols[0].dim() == 1 and cols[2].dim() == 1
+    seg, ends = _seg_start(seg_start, s, n, dev)
+    if seg_done is not None:
+        seg_done = seg_done.to(dev).contiguous()
+        assert seg_done.dtype in (torch.bool, torch.uint8) and tuple(seg_done.shape) == (s,), "seg_done must be bool or uint8 [S]"
+    adv, vtarg = out if out is not None else (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    for t in (adv, vtarg):
+        assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and tuple(t.shape) == (n,)
+    need = int(lib.pvae_fc_gae_workspace_bytes(s))
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    scratch = _gae_scratch.get(key)
+    if scratch is None or scratch.numel() * 8 < need:
+        scratch = _gae_scratch[key] = torch.zeros(need // 8 + 2, dtype=torch.float64, device=dev)
+    params = make_gae_params(gamma, lambda_, standardize)
+    with torch.cuda.device(dev):
+        rc = _lib.check(lib.pvae_gae(cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(), seg.data_ptr(),
+                                     seg_done.data_ptr() if seg_done is not None else None, n, s, ends[0], ends[1],
+                                     C.byref(params), adv.data_ptr(), vtarg.data_ptr(), scratch.data_ptr(), need, key[1]),
+                        "pvae_gae")
+    if info is not None:
+        info["launches"] = rc
+    return adv, vtarg

@@ -155,6 +155,46 @@ class FullyConnectedPolicy(nn.Module):
             mask |= (1 << s) if all(flags) else 0
         return mask
 
+    def _ppo_log_std(self):
+        """(kind, base, vector, trained) of the log-std as the library's PPO calls take it."""
+        kind, base, log_std, train_ls = "state_dependent", 0.0, None, False
+        if self._log_std_fn is None:
+            als = self._policy_fn._model[-1]
+            kind = als.type
+            log_std = als.on_device(self.engine.device)
+            train_ls = kind == "state_independent" and als.log_std.requires_grad
+            if kind == "state_independent" and not train_ls:
+                kind = "constant"                # a frozen vector is a constant one to the step
+        else:
+            base = float(self._log_std_base)
+        return kind, base, log_std, train_ls
+
+    def ppo_prepare(self, rollout, config):
+        """The first half of a learner iteration, on the device (`pvae_fc_ppo_prepare`): from a device-resident rollout to the
+        train batch `ppo_learn` takes.  `rollout`: device tensors obs [N, n_in], actions [N, k], rewards [N], seg_start (int32
+        [S + 1], from 0 to N), seg_done (bool / uint8 [S]) and next_obs_last [S, n_in] -- the segment table, see
+        `ppo.segment_table` --, and optionally the sampler's own vf_preds, action_dist_inputs and action_logp (used as given
+        when all three are there; otherwise the current policy is evaluated over the rows).  Then the bootstrap value of
+        every segment that did not end its episode, GAE with `config.gamma` / `config.lambda_`, the value targets, and
+        (`config.standardize`) the advantages standardised over the batch.  Returns a dict under RLlib's sample-batch keys
+        that `ppo_learn` accepts unchanged (plus `last_value` [S]); nothing synchronises."""
+        from . import ppo as P
+        eng = self.engine
+        eng._need_gpu()
+        missing = [k for k in P.ROLLOUT_KEYS if rollout.get(k) is None]
+        if missing:
+            raise KeyError("rollout lacks %s" % ", ".join(missing))
+        kind, base, log_std, train_ls = self._ppo_log_std()
+        eng.ppo_bind(log_std, train_ls)
+        ro = {k: rollout[k] for k in ("obs", "actions", "rewards", "seg_start", "seg_done")}
+        ro["boot_obs"] = rollout["next_obs_last"]
+        if all(rollout.get(k) is not None for k in P.SAMPLER_KEYS):
+            ro.update(vf_preds=rollout["vf_preds"], old_dist=rollout["action_dist_inputs"], old_logp=rollout["action_logp"])
+        res = eng.ppo_prepare(ro, config.gae_params(kind, base))
+        return {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
+                "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
+                "value_targets": res["value_targets"], "last_value": res["last_value"]}
+
     def ppo_learn(self, batch, config, perm=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_fc_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step
@@ -170,16 +210,7 @@ class FullyConnectedPolicy(nn.Module):
             raise ValueError("sgd_minibatch_size %d > max_batch %d (custom_model_config['max_batch'])"
                              % (config.sgd_minibatch_size, eng.max_batch))
         mask = self._ppo_train_mask()
-        kind, base, log_std, train_ls = "state_dependent", 0.0, None, False
-        if self._log_std_fn is None:
-            als = self._policy_fn._model[-1]
-            kind = als.type
-            log_std = als.on_device(eng.device)
-            train_ls = kind == "state_independent" and als.log_std.requires_grad
-            if kind == "state_independent" and not train_ls:
-                kind = "constant"                # a frozen vector is a constant one to the step
-        else:
-            base = float(self._log_std_base)
+        kind, base, log_std, train_ls = self._ppo_log_std()
         if mask == 0 and train_ls:
             raise NotImplementedError("every stack is frozen: the fused PPO step does not train the state_independent "
                                       "log_std vector alone")

@@ -13,9 +13,24 @@ the same terms), its closed-form gradients (what `fc_ppo_head_kernel` follows), 
 
 The fused step itself -- forward, this loss, backward and Adam in one library call -- is `FullyConnectedPolicy.ppo_learn`
 (physicsvae_amd/fcnn.py) on `StackSetEngine.ppo_sgd`.
+
+What comes before it -- the train batch's advantages and value targets, RLlib 1.11's compute_advantages (use_gae) and
+standardized -- is restated in `gae_torch` / `standardize_torch`.  A segment is a run of consecutive rows of one episode
+in time order (what RLlib postprocesses as one trajectory), rows seg_start[s] .. seg_start[s + 1] - 1; last_value[s] is
+0 if the segment ended its episode, else the value function at the observation after its last row.  Last row first:
+
+    v_next[t]        = vf_preds[t + 1]              (last row: last_value[s])
+    delta[t]         = rewards[t] + gamma v_next[t] - vf_preds[t]
+    adv[t]           = delta[t] + gamma lambda adv[t + 1]        (adv past the end = 0)
+    value_targets[t] = adv[t] + vf_preds[t]
+    advantages       = (adv - mean(adv)) / max(1e-4, std(adv))   over the whole train batch, population std
+
+On the device: `FullyConnectedPolicy.ppo_prepare` (`pvae_fc_ppo_prepare`); `segment_table` builds the segment table on
+the host from RLlib's eps_id / dones / new_obs columns.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -37,7 +52,7 @@ class PPOConfig:
 
     def __init__(self, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1.0, kl_coeff=0.2, entropy_coeff=0.0, lr=5e-5,
                  sgd_minibatch_size=128, num_sgd_iter=30, grad_clip=None, betas=(0.9, 0.999), adam_eps=1e-8,
-                 weight_decay=0.0):
+                 weight_decay=0.0, gamma=0.99, lambda_=1.0, standardize=True):
         if grad_clip is not None:
             raise NotImplementedError("grad_clip=%r: gradient clipping is not part of the fused PPO step" % (grad_clip,))
         self.clip_param, self.vf_clip_param = float(clip_param), float(vf_clip_param)
@@ -45,12 +60,21 @@ class PPOConfig:
         self.lr, self.betas, self.adam_eps, self.weight_decay = float(lr), tuple(betas), float(adam_eps), float(weight_decay)
         self.sgd_minibatch_size, self.num_sgd_iter = int(sgd_minibatch_size), int(num_sgd_iter)
         self.grad_clip = None
+        self.gamma, self.lambda_, self.standardize = float(gamma), float(lambda_), bool(standardize)
         assert self.sgd_minibatch_size >= 1 and self.num_sgd_iter >= 1
+        assert 0.0 <= self.gamma <= 1.0 and 0.0 <= self.lambda_ <= 1.0
 
     @classmethod
     def from_spec(cls, config):
         """From a spec's `config:` mapping (loco_imitation.yaml): the keys this class knows, the rest ignored."""
-        return cls(**{k: config[k] for k in cls.KEYS + ("grad_clip",) if k in config})
+        kw = {k: config[k] for k in cls.KEYS + ("grad_clip", "gamma") if k in config}
+        if "lambda" in config:
+            kw["lambda_"] = config["lambda"]
+        return cls(**kw)
+
+    def gae_params(self, log_std_kind=0, log_std_base=0.0):
+        """The `pvae_gae_params` of a train-batch preparation."""
+        return make_gae_params(self.gamma, self.lambda_, self.standardize, log_std_kind, log_std_base)
 
     def params(self, log_std_kind, log_std_base=0.0, adam_t=1, train_mask=0):
         """The `pvae_fc_ppo_params` of a step."""
@@ -62,6 +86,71 @@ class PPOConfig:
         p.log_std_kind = _lib.LOG_STD_KINDS[log_std_kind] if isinstance(log_std_kind, str) else int(log_std_kind)
         p.log_std_base = float(log_std_base)
         return p
+
+
+def make_gae_params(gamma, lambda_, standardize=True, log_std_kind=0, log_std_base=0.0):
+    p = _lib.GaeParams()
+    p.gamma, p.lambda_, p.standardize = float(gamma), float(lambda_), 1 if standardize else 0
+    p.log_std_kind = _lib.LOG_STD_KINDS[log_std_kind] if isinstance(log_std_kind, str) else int(log_std_kind)
+    p.log_std_base = float(log_std_base)
+    return p
+
+
+def gae_torch(rewards, vf_preds, last_values, seg_start, gamma, lambda_):
+    """The recurrence of the module docstring in plain torch, any dtype and device: (adv, value_targets) [N] before
+    standardisation.  rewards / vf_preds [N]; last_values [S] (already 0 where the segment ended its episode); seg_start
+    [S + 1] integers from 0 to N.  One vectorised step per time offset: as many steps as the longest segment has rows."""
+    n = rewards.shape[0]
+    start = torch.as_tensor(seg_start, dtype=torch.long, device=rewards.device)
+    assert int(start[0]) == 0 and int(start[-1]) == n, "seg_start must run from 0 to the number of rows"
+    length = start[1:] - start[:-1]
+    assert bool((length >= 1).all()), "every segment has at least one row"
+    end = start[1:]
+    adv = torch.zeros_like(vf_preds)
+    nxt_adv = torch.zeros_like(last_values)
+    nxt_v = last_values.clone()
+    for i in range(int(length.max())):
+        live = length > i
+        t = (end - 1 - i)[live]
+        v = vf_preds[t]
+        a = rewards[t] + gamma * nxt_v[live] - v + gamma * lambda_ * nxt_adv[live]
+        adv[t] = a
+        nxt_adv[live] = a
+        nxt_v[live] = v
+    return adv, adv + vf_preds
+
+
+def standardize_torch(adv):
+    """(adv - mean) / max(1e-4, std), population std, over every row given."""
+    return (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
+
+
+def segment_table(eps_id, dones, new_obs, unroll_id=None):
+    """The segment table of a train batch from RLlib's columns (numpy, on the host): rows are concatenated fragments, each
+    in time order; a new segment starts wherever `eps_id` changes, the row before was `dones`, or -- when the batch's
+    `unroll_id` column is passed -- the fragment changes (RLlib postprocesses an episode that spans two fragments as two
+    trajectories; without the column such neighbours are one segment).  Returns (seg_start int32
+    [S + 1], seg_done uint8 [S] -- the segment's last row ended its episode --, next_obs_last float32 [S, n_in] -- `new_obs`
+    of each segment's last row, the observation the bootstrap value is taken at)."""
+    eps_id, dones = np.asarray(eps_id).reshape(-1), np.asarray(dones).reshape(-1).astype(bool)
+    n = eps_id.shape[0]
+    assert n >= 1 and dones.shape[0] == n and len(new_obs) == n, "eps_id, dones and new_obs must have one entry per row"
+    first = np.ones(n, dtype=bool)
+    first[1:] = (eps_id[1:] != eps_id[:-1]) | dones[:-1]
+    if unroll_id is not None:
+        unroll_id = np.asarray(unroll_id).reshape(-1)
+        assert unroll_id.shape[0] == n, "unroll_id must have one entry per row"
+        first[1:] |= unroll_id[1:] != unroll_id[:-1]
+    starts = np.flatnonzero(first)
+    seg_start = np.concatenate([starts, [n]]).astype(np.int32)
+    last = seg_start[1:] - 1
+    new_obs = np.asarray(new_obs)
+    return seg_start, dones[last].astype(np.uint8), np.ascontiguousarray(new_obs[last].reshape(len(last), -1), dtype=np.float32)
+
+
+# what `FullyConnectedPolicy.ppo_prepare` reads from a rollout, and the sampler's own columns it takes as given
+ROLLOUT_KEYS = ("obs", "actions", "rewards", "seg_start", "seg_done", "next_obs_last")
+SAMPLER_KEYS = ("vf_preds", "action_dist_inputs", "action_logp")
 
 
 def _terms(mean, log_std, value, actions, old_dist, old_logp, advantages, value_targets, vf_preds, cfg):
