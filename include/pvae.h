@@ -806,6 +806,59 @@ int pvae_fc_gae_launches(pvae_fc* fc, int32_t* evaluate, int32_t* rest);
 /* sizeof(pvae_gae_params) / sizeof(pvae_fc_rollout) / sizeof(pvae_fc_prepared) as the library was compiled: which = 0 / 1 / 2 */
 int pvae_gae_sizeof(int which);
 
+/* ---- PPO learner step of PhysicsVAE (the second stage: `run: DDPPO`, `custom_model: physics_vae`) --------------------
+ * One minibatch update of PhysicsVAE -- its forward without the world model (rmt:742-771), the loss above, backward, Adam --
+ * as ONE library call with no host synchronisation.  The value branch (rmt:846-853) is a ONE-stack stack set [value] with
+ * n_in = 2 Db, bound with pvae_fc_bind and pvae_fc_ppo_bind (its gradient arena and moments are the ones bound there).
+ *
+ * Launches of one step, in order:
+ *   copy-in            obs[index[r]] = [s_body | s_task] into the encoder's input panel, the body columns of the decoder's and
+ *                      the value stack's input panel (whole padded panels; an input subset's left-out block is zeros)
+ *   [rows <= 4]        zero the pad rows of the layer-output panels the GEMV forward leaves unwritten
+ *   TE layers          one per layer -> [mu | logvar]
+ *   sampler            z = mu + eps exp(logvar / 2) into the decoder's input panel (noise = 0: z = mu; prior False: z = e)
+ *   MD layers          one per layer -> a_hat
+ *   value layers       the stack set's forward, one per layer
+ *   loss head          reads a_hat, the log-std vector and the value in their panels and the batch columns through `index`;
+ *                      writes d_mean and d_value over the padded gradient panels and the per-wave partials
+ *   MD backward        one per layer, last to first (input gradient + weight gradient of a layer in one launch; weight
+ *                      gradients only when MD is trained, the first layer's input gradient only when TE is trained);
+ *                      skipped when neither TE nor MD is trained
+ *   sampler backward   the z columns of the decoder's input gradient -> the encoder's output gradient (TE trained)
+ *   TE backward        one per layer (TE trained)
+ *   value backward     one per layer (value trained)
+ *   Adam + stats       ONE launch over the trained segments (TE, MD: their segments of the arena; value: its own arena);
+ *                      its extra workgroup finishes stats_out[5] and, log_std_kind 1, the log-std gradient and its update
+ * No forward is recomputed: the three stacks share no panel, and every panel stays live until its backward has run.
+ * Gradients go to `grad`, moments to `m` / `v` of pvae_ppo_bind: buffers of the parameter arena's layout that are NOT the
+ * ones of pvae_bind_arenas (the supervised trainer's gradient arena and moments are never touched).
+ *
+ *   pvae_ppo_workspace_bytes  size of the scratch (the head's partial sums), a multiple of 16; 0 on error
+ *   pvae_ppo_bind      grad / m / v (arena layout, m and v zero-initialised by the caller), scratch, log_std: the vector of
+ *                      Da values, with its moments when it is trained (log_std_kind 1); value: the bound [value] stack set
+ *   pvae_ppo_step      one minibatch, rows and index as pvae_fc_ppo_step.  params: pvae_fc_ppo_params with log_std_kind 0 / 1;
+ *                      train_mask bits: 1 TE, 2 MD, 4 value (0: all three) -- a net that is not trained runs forward (and, the
+ *                      decoder, passes the gradient on) and neither its parameters nor its moments are touched.
+ *                      eps: device [rows][Z] draws, or NULL: Philox (rng_seed, rng_offset) as pvae_infer; noise = 0: z = mu.
+ *                      The draws used are left in workspace panel 6.  batch->obs is [n_rows][2 Db], batch->k = Da.
+ *   pvae_ppo_sgd       the SGD loop as pvae_fc_ppo_sgd; step i uses eps + i minibatch Z (dense per step: [steps][minibatch][Z],
+ *                      not gathered through perm) or Philox offset rng_offset + i, and Adam time step adam_t + i.
+ *   pvae_ppo_launches  kernel launches of the last step.
+ *   pvae_ppo_sizeof    sizeof(pvae_fc_ppo_params) / sizeof(pvae_fc_ppo_batch) / sizeof(pvae_config): which = 0 / 1 / 2
+ * Needs lookahead 1, prior ZERO_MEAN or NONE, no helper stack.  Bad arguments, an unbound buffer or rows > max_batch return a
+ * negative code and launch nothing. */
+size_t pvae_ppo_workspace_bytes(const pvae_config* cfg);
+int pvae_ppo_bind(pvae_ctx* ctx, float* grad, float* m, float* v, void* scratch, size_t scratch_bytes, float* log_std,
+                  float* log_std_m, float* log_std_v, pvae_fc* value);
+int pvae_ppo_step(pvae_ctx* ctx, const pvae_fc_ppo_batch* batch, const int32_t* index, int64_t first, int32_t rows,
+                  const pvae_fc_ppo_params* params, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                  float* stats_out, void* stream);
+int pvae_ppo_sgd(pvae_ctx* ctx, const pvae_fc_ppo_batch* batch, const int32_t* perm, int32_t minibatch, int32_t num_sgd_iter,
+                 const pvae_fc_ppo_params* params, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                 float* stats_out, void* stream);
+int pvae_ppo_launches(pvae_ctx* ctx, int32_t* per_step);
+int pvae_ppo_sizeof(int which);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

@@ -212,6 +212,14 @@ _SIGS = {
                                       _P]),
     "pvae_fc_gae_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_gae_sizeof": (C.c_int, [C.c_int]),
+    "pvae_ppo_workspace_bytes": (C.c_size_t, [C.POINTER(Config)]),
+    "pvae_ppo_bind": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "pvae_ppo_step": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int64, C.c_int32, C.POINTER(FcPpoParams), _P, C.c_int,
+                                C.c_uint64, C.c_uint64, _P, _P]),
+    "pvae_ppo_sgd": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.c_int32, C.POINTER(FcPpoParams), _P, C.c_int,
+                               C.c_uint64, C.c_uint64, _P, _P]),
+    "pvae_ppo_launches": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "pvae_ppo_sizeof": (C.c_int, [C.c_int]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),

@@ -2897,3 +2897,59 @@ int pvae_reparam_backward(pvae_ctx* c, const float* mu_logvar, const float* eps_
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// what the fused PPO learner step (pvae_ppo.hip) runs of this unit: a stack's forward on the panels as they are, the
+// sampler into the decoder's input panel, and a stack's backward plan with a gradient store into `grad_arena` -- the
+// launches of pvae_infer / pvae_net_backward without their copies, seed launches and recomputed forward
+// ---------------------------------------------------------------------------------------
+void ppo_enter(pvae_ctx* c, int rows) {
+    c->staged_rows = 0;          // the training panels are no longer a coherent batch
+    c->staged_rows_f = rows;
+    c->pf.valid = false;
+    c->dx.on = false;
+}
+
+int ppo_forward_net(pvae_ctx* c, int net, int rows, hipStream_t st, int* launches) {
+    const int rc = forward_net(c, net, pad32(rows), st);
+    if (rc == 0) *launches += (int)c->L.net[net].layers.size();
+    return rc;
+}
+
+int ppo_sampler(pvae_ctx* c, const float* eps, int rows, int noise, uint64_t seed, uint64_t offset, hipStream_t st,
+                int* launches) {
+    const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    const int rc = launch_sampler(c, c->ws + c->W.net[PVAE_NET_TE].act.back(), TE.layers.back().n_out_pad, eps,
+                                  c->ws + c->W.eps, c->ws + c->W.net[PVAE_NET_MD].in, c->L.net[PVAE_NET_MD].layers[0].ld, rows,
+                                  pad32(rows), noise ? 1 : 0, (unsigned long long)seed, (unsigned long long)offset,
+                                  (float*)nullptr, (float*)nullptr, (const float*)nullptr, 0, st);
+    if (rc == 0) ++*launches;
+    return rc;
+}
+
+int ppo_backward_net(pvae_ctx* c, int net, int rows, bool train, bool input_grad, float* grad_arena, hipStream_t st,
+                     int* launches) {
+    // as pvae_net_backward: a bound arena, a pending update and a direct step of the trainer are set aside and put back
+    float* const grads_keep = c->grads;
+    const AdamSeg pending_keep = c->pending_adam, held_keep = c->held_adam;
+    const bool dx_keep = c->dx.on;
+    c->grads = grad_arena;
+    c->grad_accum = false;
+    c->pending_adam = AdamSeg();
+    c->held_adam = AdamSeg();
+    c->dx.on = false;
+    pvae_step_params sp;
+    memset(&sp, 0, sizeof(sp));
+    Plan plan;
+    plan_backward_net(c, net, pad32(rows), train, input_grad, &sp, false, st, nullptr, plan);
+    int rc = 0;
+    for (Stage& s : plan) {
+        if ((rc = s.run())) break;
+        ++*launches;
+    }
+    c->grads = grads_keep;
+    c->pending_adam = pending_keep;
+    c->held_adam = held_keep;
+    c->dx.on = dx_keep;
+    return rc;
+}

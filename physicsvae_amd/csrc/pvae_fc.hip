@@ -408,6 +408,47 @@ fc_adam_kernel(FcAdam a) {
     }
 }
 
+// fc_adam_kernel over segments of up to three DIFFERENT arenas (the PhysicsVAE step: the encoder's and the decoder's
+// segments of the five-net arena and the value stack set's arena, each with its own gradient and moment buffers): the
+// same adam_update4 per element, the same last workgroup for the stats and the log-std vector.
+struct PpoAdam {
+    PpoAdamSegs seg;
+    long long end4[3];                              // running float4 count through segment i
+    AdamScalars s;
+    const float* part; int nparts, part_stride; float inv_rows; float* stats_out;
+    int k; float* ls; float* ls_m; float* ls_v;
+};
+__global__ void __launch_bounds__(256)
+ppo_adam_kernel(PpoAdam a) {
+    if (blockIdx.x == gridDim.x - 1) {
+        if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
+        if (a.ls)
+            for (int j = threadIdx.x; j < a.k; j += 256) {
+                double gs = 0.0;
+                for (int i = 0; i < a.nparts; ++i) gs += (double)a.part[(size_t)i * a.part_stride + kPartStats + j];
+                const float g = (float)gs;
+                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
+                adam_update(g, p, m, v, a.s);
+                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
+            }
+        return;
+    }
+    const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
+        int k = 0;
+        while (i >= a.end4[k]) ++k;
+        const long long q = i - (k ? a.end4[k - 1] : 0);
+        v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
+        const v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
+        v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
+        v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
+        adam_update4(gg, pp, mm, vv, a.s);
+        reinterpret_cast<v4f*>(a.seg.p[k])[q] = pp;
+        reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
+        reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // train-batch preparation: evaluate epilogue, GAE, standardisation (include/pvae.h "Train-batch preparation")
 // ---------------------------------------------------------------------------------------
@@ -1163,6 +1204,86 @@ int eval_boot(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_fc_prepared* out
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------------------
+// what the PPO learner step of PhysicsVAE (pvae_ppo.hip) runs of this unit (pvae_internal.h)
+// ---------------------------------------------------------------------------------------
+int fc_value_stack(pvae_fc* c, FcValueStack* out) {
+    if (!c) return fail(-1, "null value stack set");
+    if (!c->params || !c->ws) return fail(-2, "value stack set: pvae_fc_bind has not been called");
+    if (!c->grad || !c->m || !c->v) return fail(-2, "value stack set: pvae_fc_ppo_bind has not been called");
+    const FcLayout& L = c->L;
+    if (L.S != 1 || L.cfg.n_out[0] != 1) return fail(-1, "the value stack set must be one stack with one output, got %d stacks", L.S);
+    const int lv = (int)L.stack[0].size() - 1;
+    memset(out, 0, sizeof(*out));
+    out->in = c->ws + c->W.in; out->ld_in = L.ld0; out->n_in = L.cfg.n_in;
+    out->value = act_ptr(c, 0, lv); out->ld_value = panel_ld(c, 0, lv);
+    out->d_value = dz_ptr(c, 0, lv); out->ld_dv = panel_ld(c, 0, lv); out->width_dv = L.stack[0][lv].n_out_pad;
+    out->params = c->params; out->grad = c->grad; out->m = c->m; out->v = c->v;
+    out->arena_floats = L.arena_floats;
+    out->max_batch = L.cfg.max_batch;
+    for (int i = 0; i <= lv; ++i) {
+        out->panel[i] = act_ptr(c, 0, i);
+        out->panel_ld[i] = panel_ld(c, 0, i);
+    }
+    out->n_panels = lv + 1;
+    return 0;
+}
+
+int fc_value_forward(pvae_fc* c, int rows, hipStream_t st, int* launches) {
+    Run r{c, st, rows, pad32(rows)};
+    r.want[0] = true;
+    set_range(r, 1);
+    const int rc = run_forward(r, nullptr);
+    *launches += r.launches;
+    return rc;
+}
+
+int fc_value_backward(pvae_fc* c, int rows, hipStream_t st, int* launches) {
+    Run r{c, st, rows, pad32(rows)};
+    r.want[0] = true;
+    set_range(r, 1);
+    const int rc = run_backward_layers<EpiGradStore>(r, false, c->grad, 1);
+    *launches += r.launches;
+    return rc;
+}
+
+size_t ppo_head_scratch_floats(int max_batch, int k) { return (size_t)head_waves(pad32(max_batch)) * part_stride(k, true); }
+
+int ppo_head_check(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows) { return check_loss_args(b, p, rows); }
+
+int ppo_head_launch(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0, int rows,
+                    const PpoHeadIo& io, hipStream_t st) {
+    const int rows_pad = pad32(rows);
+    PpoHead h;
+    fill_head(h, b, p, index, row0, rows, rows_pad);
+    h.mean = io.mean; h.ld_mean = io.ld_mean; h.ls = io.ls; h.ld_ls = 0; h.value = io.value; h.ld_value = io.ld_value;
+    h.d_mean = io.d_mean; h.ld_dm = io.ld_dm; h.width_dm = io.width_dm;
+    h.d_value = io.d_value; h.ld_dv = io.ld_dv; h.width_dv = io.width_dv;
+    h.part = io.part; h.part_stride = part_stride(b->k, io.colsum != 0); h.colsum = io.colsum;
+    hipLaunchKernelGGL(fc_ppo_head_kernel, dim3(head_waves(rows_pad) / 4), dim3(256), 0, st, h);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
+    PpoAdam a;
+    memset((void*)&a, 0, sizeof(a));
+    a.seg = segs;
+    long long total4 = 0;
+    for (int i = 0; i < segs.n; ++i) { total4 += segs.n4[i]; a.end4[i] = total4; }
+    a.s = ppo_adam_scalars(p, adam_t);
+    a.part = part; a.nparts = head_waves(pad32(rows)); a.part_stride = part_stride(k, colsum != 0);
+    a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
+    a.k = k;
+    if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
+    long long grid = (total4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 extern "C" {
 

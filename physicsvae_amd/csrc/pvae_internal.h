@@ -4,6 +4,8 @@
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
+//   pvae_fc.hip              the stack set and the PPO learner step on it
+//   pvae_ppo.hip             the PPO learner step of PhysicsVAE: joins the launches of pvae.hip and pvae_fc.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -233,6 +235,15 @@ struct pvae_ctx {
     hipStream_t param_stream = nullptr;                  // (NULL is a stream too: the default one.  The caller's stream must
                                                          //  outlive the writes it queued, as for any other call here.)
     bool param_pending = false;                          // work that writes the parameters may still be queued on it
+    // PPO learner step (pvae_ppo_bind): gradient and moment arenas of the parameter arena's layout -- not the supervised
+    // trainer's grads / m / v above --, the head's scratch, the log-std vector and the stack set of the value branch
+    struct Ppo {
+        float* grad = nullptr; float* m = nullptr; float* v = nullptr;
+        float* scratch = nullptr;
+        float* log_std = nullptr; float* log_std_m = nullptr; float* log_std_v = nullptr;
+        pvae_fc* value = nullptr;
+        int launches = 0;
+    } ppo;
 };
 static inline void params_touched(pvae_ctx* c, hipStream_t st, bool queued = true) {
     // one stream is remembered: writes still queued on ANOTHER one are drained here (a caller that switches streams with
@@ -323,3 +334,46 @@ struct Bucket { int64_t off, cnt; };
 int64_t auto_bucket_bytes(const pvae_ctx* c, int phase);
 std::vector<Bucket> exchange_buckets(const pvae_ctx* c, int net);
 int exchange_bucket(pvae_ctx* c, int net, const Bucket& b, const pvae_step_params* sp, hipStream_t st, hipStream_t cs, int& n_events);
+
+// ---- the PPO learner step of PhysicsVAE (pvae_ppo.hip) and what it runs of pvae.hip and pvae_fc.hip ----
+// pvae.hip: a stack's forward on the panels as they are, the sampler into the decoder's input panel, a stack's backward plan
+// with a gradient store into `grad_arena` (arena layout); `launches` counts what went out
+void ppo_enter(pvae_ctx* c, int rows);
+int ppo_forward_net(pvae_ctx* c, int net, int rows, hipStream_t st, int* launches);
+int ppo_sampler(pvae_ctx* c, const float* eps, int rows, int noise, uint64_t seed, uint64_t offset, hipStream_t st, int* launches);
+int ppo_backward_net(pvae_ctx* c, int net, int rows, bool train, bool input_grad, float* grad_arena, hipStream_t st, int* launches);
+// pvae_fc.hip: the one-stack set [value] that carries the value branch, as the step sees it
+struct FcValueStack {
+    float* in; int ld_in, n_in;                 // input panel [rows_pad][ld_in] of n_in live columns
+    const float* value; int ld_value;           // column 0 of the output layer's panel
+    float* d_value; int ld_dv, width_dv;        // the output gradient block [rows_pad][width_dv]
+    float* params; float* grad; float* m; float* v;
+    long long arena_floats;
+    int max_batch;
+    int n_panels;                               // the layer-output panels (what a <= 4-row forward leaves unwritten below its rows)
+    float* panel[PVAE_MAX_HIDDEN + 1];
+    int panel_ld[PVAE_MAX_HIDDEN + 1];
+};
+int fc_value_stack(pvae_fc* c, FcValueStack* out);                                   // < 0: not a bound [value] set
+int fc_value_forward(pvae_fc* c, int rows, hipStream_t st, int* launches);           // on the input panel as it is
+int fc_value_backward(pvae_fc* c, int rows, hipStream_t st, int* launches);          // from d_value, into `grad`
+// pvae_fc.hip: the loss head on any panels, and the Adam + stats launch over up to three arena segments
+struct PpoHeadIo {
+    const float* mean; long long ld_mean;
+    const float* ls;                            // one vector of k values for all rows
+    const float* value; long long ld_value;
+    float* d_mean; int ld_dm, width_dm;         // null: not wanted
+    float* d_value; int ld_dv, width_dv;
+    float* part; int colsum;
+};
+size_t ppo_head_scratch_floats(int max_batch, int k);
+int ppo_head_check(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows);
+int ppo_head_launch(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0, int rows,
+                    const PpoHeadIo& io, hipStream_t st);
+struct PpoAdamSegs {
+    int n;
+    float* p[3]; const float* g[3]; float* m[3]; float* v[3];
+    long long n4[3];                            // float4 elements of segment i
+};
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);

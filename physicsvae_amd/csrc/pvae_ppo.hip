@@ -1,0 +1,293 @@
+// pvae_ppo.hip -- the PPO learner step of PhysicsVAE (include/pvae.h pvae_ppo_*; `run: DDPPO`, `custom_model: physics_vae`):
+// one minibatch update -- rmt:742-771 without the world model, the clipped-surrogate loss, backward, Adam -- as ONE
+// library call with no host synchronisation.  It joins launches that exist: the stacks' forward and backward plans of
+// pvae.hip, the stack set's grouped launches (the value branch) and the loss head of pvae_fc.hip.  No forward is
+// recomputed: the encoder's, the decoder's and the value stack's panels stay live from the forward to their backward
+// (the three stacks share no panel).  Launch order of a step:
+//   copy-in | [rows <= 4: zero pad rows] | TE layers | sampler | MD layers | value layers | loss head |
+//   MD backward (input gradient when the encoder is trained) | sampler backward | TE backward | value backward | Adam + stats
+#include "pvae_internal.h"
+
+namespace {
+
+// batch row of minibatch row r: index[r] clamped into [0, n_rows) (a bad entry must not read out of bounds), or row0 + r
+__device__ inline long long ppo_batch_row(const int32_t* __restrict__ index, long long row0, long long n_rows, int r) {
+    if (!index) return row0 + r;
+    const long long i = index[r];
+    return i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
+}
+
+// obs[index[r]] = [s_body (Db) | s_task (Db)] into the three input panels, each written over its WHOLE [rows_pad][ld]
+// block: zeros in pad rows, in pad columns and in the blocks an input subset leaves out (StageArgs::in_off).  The decoder's
+// z columns are written by the sampler.  blockIdx.y = panel: 0 encoder, 1 decoder, 2 value stack.
+struct PpoCopyIn {
+    const float* obs; const int32_t* index; long long row0, n_rows;
+    int rows, rows_pad, Db, in_off;
+    float* dst[3]; int ld[3];
+};
+__global__ void __launch_bounds__(256)
+ppo_copy_in_kernel(PpoCopyIn a) {
+    const int k = blockIdx.y;
+    float* __restrict__ dst = a.dst[k];
+    const int ld = a.ld[k], Db = a.Db;
+    const int total = a.rows_pad * ld;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / ld, c = idx - r * ld;
+        bool on = r < a.rows;
+        if (k == 0) on = on && c < 2 * Db && !(a.in_off & (c < Db ? 1 : 2));
+        else if (k == 1) on = on && c < Db && !(a.in_off & 4);
+        else on = on && c < 2 * Db;
+        dst[idx] = on ? a.obs[(size_t)ppo_batch_row(a.index, a.row0, a.n_rows, r) * (2 * Db) + c] : 0.f;
+    }
+}
+
+// Rows [r0, r1) of the layer-output panels set to zero: a <= 4-row forward runs on the GEMV kernels, which write the live
+// rows only, while the backward contractions read whole 32-row tiles.  blockIdx.y = panel.
+constexpr int kPpoZeroPanels = 3 * (PVAE_MAX_HIDDEN + 1);
+struct PpoZeroRows {
+    float* p[kPpoZeroPanels];
+    int ld[kPpoZeroPanels];
+    int r0, r1;
+};
+__global__ void __launch_bounds__(256)
+ppo_zero_rows_kernel(PpoZeroRows z) {
+    const int k = blockIdx.y;
+    float* __restrict__ p = z.p[k] + (size_t)z.r0 * z.ld[k];
+    const int total = (z.r1 - z.r0) * z.ld[k];
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) p[idx] = 0.f;
+}
+
+// Backward of the sampler on the panels (sampler_bwd_kernel's arithmetic, pvae.hip; autograd of rmt:734-740, no KL term:
+// the PPO loss has none): dz = the z columns of the decoder's input gradient, mu_logvar = the encoder's output panel,
+// d_mu_logvar -> the encoder's output gradient panel, written over its whole [rows_pad][ld] block (zeros in pad rows / columns).
+//   N(mu, s^2):  dmu = dz, dlv = dz eps exp(lv / 2) / 2 (noise = 0: z = mu, dlv = 0);   no prior (False): de = dz
+__global__ void __launch_bounds__(256)
+ppo_sampler_bwd_kernel(const float* __restrict__ te_out, const float* __restrict__ eps_used, const float* __restrict__ d_md_in,
+                       int ld_md, int Db, int Z, int rows, int rows_pad, int with_logvar, int noise, float* __restrict__ dz_te, int ld) {
+    const int total = rows_pad * ld;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / ld, c = idx - r * ld;
+        float d = 0.f;
+        if (r < rows) {
+            if (c < Z) d = d_md_in[(size_t)r * ld_md + Db + c];
+            else if (with_logvar && noise && c < 2 * Z) {
+                const int j = c - Z;
+                d = d_md_in[(size_t)r * ld_md + Db + j] * eps_used[(size_t)r * Z + j] * 0.5f * expf(0.5f * te_out[idx]);
+            }
+        }
+        dz_te[idx] = d;
+    }
+}
+
+enum { kTrainTE = 1, kTrainMD = 2, kTrainValue = 4 };
+
+size_t scratch_bytes(const pvae_config& cfg) {
+    return (ppo_head_scratch_floats(cfg.max_batch, cfg.dim_action) * sizeof(float) + 15) / 16 * 16;
+}
+
+int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows,
+              const float* stats, FcValueStack* vs) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    const pvae_ctx::Ppo& q = c->ppo;
+    if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
+    if ((rc = ppo_head_check(b, p, rows))) return rc;
+    if (!b->obs) return fail(-1, "batch obs is null");
+    if (!stats) return fail(-1, "stats_out is null");
+    const pvae_config& cfg = c->L.cfg;
+    if (cfg.lookahead != 1) return fail(-1, "the PPO step needs a lookahead 1 context, got %d", cfg.lookahead);
+    if (cfg.prior_kind != PVAE_PRIOR_ZERO_MEAN && cfg.prior_kind != PVAE_PRIOR_NONE)
+        return fail(-1, "the PPO step supports the priors normal_zero_mean_one_std and False, got prior_kind %d", cfg.prior_kind);
+    if (cfg.mh_depth > 0) return fail(-1, "the PPO step does not run the motor decoder's helper");
+    if (p->log_std_kind != 0 && p->log_std_kind != 1) return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
+    if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
+    if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_ppo_bind)");
+    if (b->k != cfg.dim_action) return fail(-1, "batch k %d != dim_action %d", b->k, cfg.dim_action);
+    if (rows > cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, cfg.max_batch);
+    if (first < 0 || first + rows > b->n_rows) return fail(-1, "rows [%lld, +%d) outside the batch of %lld", first, rows, (long long)b->n_rows);
+    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
+    if (p->train_mask < 0 || p->train_mask > 7) return fail(-1, "train_mask names a net that does not exist (bits: 1 TE, 2 MD, 4 value)");
+    if ((rc = fc_value_stack(q.value, vs))) return rc;
+    if (vs->n_in != 2 * cfg.dim_body) return fail(-1, "the value stack reads %d inputs, the observation has %d", vs->n_in, 2 * cfg.dim_body);
+    if (rows > vs->max_batch) return fail(-1, "rows %d > max_batch %d of the value stack set", rows, vs->max_batch);
+    return 0;
+}
+
+// one minibatch (arguments checked by the caller)
+int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
+             const pvae_fc_ppo_params* p, int adam_t, const float* eps, int noise, uint64_t seed, uint64_t offset,
+             float* stats_out, hipStream_t st) {
+    const pvae_ctx::Ppo& q = c->ppo;
+    const pvae_config& cfg = c->L.cfg;
+    const int Db = cfg.dim_body, Z = cfg.latent;
+    const int mask = p->train_mask ? p->train_mask : 7;
+    const bool train_te = mask & kTrainTE, train_md = mask & kTrainMD, train_v = mask & kTrainValue;
+    const int rows_pad = pad32(rows);
+    const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    const NetLayout& MD = c->L.net[PVAE_NET_MD];
+    const NetWork& wte = c->W.net[PVAE_NET_TE];
+    const NetWork& wmd = c->W.net[PVAE_NET_MD];
+    float* w = c->ws;
+    int launches = 0, rc;
+    ppo_enter(c, rows);
+    {
+        PpoCopyIn a;
+        memset(&a, 0, sizeof(a));
+        a.obs = b->obs; a.index = index ? index + first : nullptr; a.row0 = first; a.n_rows = b->n_rows;
+        a.rows = rows; a.rows_pad = rows_pad; a.Db = Db;
+        const int te = cfg.te_inputs, md = cfg.md_inputs;
+        a.in_off = (te == PVAE_INPUT_TASK ? 1 : 0) | (te == PVAE_INPUT_BODY ? 2 : 0) | (md == PVAE_INPUT_TASK ? 4 : 0);
+        a.dst[0] = w + wte.in; a.ld[0] = TE.layers[0].ld;
+        a.dst[1] = w + wmd.in; a.ld[1] = MD.layers[0].ld;
+        a.dst[2] = vs.in; a.ld[2] = vs.ld_in;
+        const int ldmax = std::max(a.ld[0], std::max(a.ld[1], a.ld[2]));
+        int gx = (rows_pad * ldmax + 255) / 256;
+        if (gx > 256) gx = 256;
+        hipLaunchKernelGGL(ppo_copy_in_kernel, dim3(gx, 3), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    if (rows <= 4 && rows < rows_pad) {
+        PpoZeroRows z;
+        memset(&z, 0, sizeof(z));
+        int n = 0, wmax = 0;
+        auto add = [&](float* ptr, int ld) { z.p[n] = ptr; z.ld[n] = ld; if (ld > wmax) wmax = ld; ++n; };
+        for (const Layer& l : TE.layers) add(w + wte.act[l.index], l.n_out_pad);
+        for (const Layer& l : MD.layers) add(w + wmd.act[l.index], l.n_out_pad);
+        for (int i = 0; i < vs.n_panels; ++i) add(vs.panel[i], vs.panel_ld[i]);
+        z.r0 = rows; z.r1 = rows_pad;
+        int gx = ((z.r1 - z.r0) * wmax + 255) / 256;
+        if (gx > 64) gx = 64;
+        hipLaunchKernelGGL(ppo_zero_rows_kernel, dim3(gx, n), dim3(256), 0, st, z);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    if ((rc = ppo_forward_net(c, PVAE_NET_TE, rows, st, &launches))) return rc;
+    if ((rc = ppo_sampler(c, eps, rows, noise, seed, offset, st, &launches))) return rc;
+    if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
+    if ((rc = fc_value_forward(q.value, rows, st, &launches))) return rc;
+    const Layer& md_last = MD.layers.back();
+    const Layer& te_last = TE.layers.back();
+    const int colsum = p->log_std_kind == 1;
+    const bool md_back = train_md || train_te;           // the decoder's backward runs: for its own gradient, or to pass one on
+    {
+        PpoHeadIo io;
+        memset(&io, 0, sizeof(io));
+        io.mean = w + wmd.act.back(); io.ld_mean = md_last.n_out_pad;
+        io.ls = q.log_std;
+        io.value = vs.value; io.ld_value = vs.ld_value;
+        if (md_back) { io.d_mean = w + wmd.dz.back(); io.ld_dm = md_last.n_out_pad; io.width_dm = md_last.n_out_pad; }
+        if (train_v) { io.d_value = vs.d_value; io.ld_dv = vs.ld_dv; io.width_dv = vs.width_dv; }
+        io.part = q.scratch; io.colsum = colsum;
+        if ((rc = ppo_head_launch(b, p, index ? index + first : nullptr, first, rows, io, st))) return rc;
+        ++launches;
+    }
+    if (md_back && (rc = ppo_backward_net(c, PVAE_NET_MD, rows, train_md, train_te, q.grad, st, &launches))) return rc;
+    if (train_te) {
+        int gx = (rows_pad * te_last.n_out_pad + 255) / 256;
+        if (gx > 256) gx = 256;
+        hipLaunchKernelGGL(ppo_sampler_bwd_kernel, dim3(gx), dim3(256), 0, st, w + wte.act.back(), w + c->W.eps, w + wmd.d_in,
+                           MD.layers[0].ld, Db, Z, rows, rows_pad, cfg.prior_kind == PVAE_PRIOR_ZERO_MEAN ? 1 : 0, noise ? 1 : 0,
+                           w + wte.dz.back(), te_last.n_out_pad);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        if ((rc = ppo_backward_net(c, PVAE_NET_TE, rows, true, false, q.grad, st, &launches))) return rc;
+    }
+    if (train_v && (rc = fc_value_backward(q.value, rows, st, &launches))) return rc;
+    {
+        PpoAdamSegs sg;
+        memset((void*)&sg, 0, sizeof(sg));
+        auto add = [&](float* pp, const float* gg, float* mm, float* vv, long long n) {
+            sg.p[sg.n] = pp; sg.g[sg.n] = gg; sg.m[sg.n] = mm; sg.v[sg.n] = vv; sg.n4[sg.n] = n / 4; ++sg.n;
+        };
+        if (train_te) add(c->params + TE.off, q.grad + TE.off, q.m + TE.off, q.v + TE.off, TE.count);
+        if (train_md) add(c->params + MD.off, q.grad + MD.off, q.m + MD.off, q.v + MD.off, MD.count);
+        if (train_v) add(vs.params, vs.grad, vs.m, vs.v, vs.arena_floats);
+        if ((rc = ppo_adam_launch(sg, p, adam_t, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m, q.log_std_v, stats_out, st)))
+            return rc;
+        ++launches;
+    }
+    c->ppo.launches = launches;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pvae_ppo_workspace_bytes(const pvae_config* cfg) {
+    if (!cfg) return 0;
+    const Layout L = make_layout(*cfg);
+    if (!L.ok) { fail(-1, "bad config: %s", L.why); return 0; }
+    return scratch_bytes(*cfg);
+}
+
+int pvae_ppo_sizeof(int which) {
+    return which == 0 ? (int)sizeof(pvae_fc_ppo_params) : which == 1 ? (int)sizeof(pvae_fc_ppo_batch)
+         : which == 2 ? (int)sizeof(pvae_config) : fail(-1, "which must be 0, 1 or 2");
+}
+
+int pvae_ppo_bind(pvae_ctx* c, float* grad, float* m, float* v, void* scratch, size_t bytes, float* log_std,
+                  float* log_std_m, float* log_std_v, pvae_fc* value) {
+    if (!c || !grad || !m || !v || !scratch || !value) return fail(-1, "null argument");
+    if (!c->params) return fail(-2, "parameter arena not bound");
+    const size_t need = scratch_bytes(c->L.cfg);
+    if (bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, need);
+    if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch) & 15)
+        return fail(-1, "grad, m, v and scratch must be 16-byte aligned");
+    if ((log_std_m != nullptr) != (log_std_v != nullptr) || (log_std_m && !log_std))
+        return fail(-1, "log_std_m and log_std_v go together, with log_std");
+    FcValueStack vs;
+    int rc = fc_value_stack(value, &vs);
+    if (rc) return rc;
+    if (vs.n_in != 2 * c->L.cfg.dim_body)
+        return fail(-1, "the value stack reads %d inputs, the observation has %d", vs.n_in, 2 * c->L.cfg.dim_body);
+    pvae_ctx::Ppo& q = c->ppo;
+    q.grad = grad; q.m = m; q.v = v; q.scratch = (float*)scratch;
+    q.log_std = log_std; q.log_std_m = log_std_m; q.log_std_v = log_std_v;
+    q.value = value;
+    return 0;
+}
+
+int pvae_ppo_step(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
+                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                  float* stats_out, void* stream) {
+    FcValueStack vs;
+    int rc = check_ppo(c, b, p, first, rows, stats_out, &vs);
+    if (rc) return rc;
+    if ((rc = ppo_step(c, vs, b, index, first, rows, p, p->adam_t, eps, noise, rng_seed, rng_offset, stats_out, (hipStream_t)stream)))
+        return rc;
+    params_touched(c, (hipStream_t)stream);
+    return 0;
+}
+
+int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, int32_t minibatch, int32_t num_sgd_iter,
+                 const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                 float* stats_out, void* stream) {
+    if (minibatch < 1 || num_sgd_iter < 1) return fail(-1, "minibatch and num_sgd_iter must be positive");
+    FcValueStack vs;
+    int rc = check_ppo(c, b, p, 0, 1, stats_out, &vs);
+    if (rc) return rc;
+    if (minibatch > c->L.cfg.max_batch || minibatch > vs.max_batch)
+        return fail(-1, "minibatch %d > max_batch %d", minibatch, std::min(c->L.cfg.max_batch, vs.max_batch));
+    const size_t eps_step = (size_t)minibatch * c->L.cfg.latent;
+    int step = 0;
+    for (int pass = 0; pass < num_sgd_iter; ++pass)
+        for (long long first = 0; first < b->n_rows; first += minibatch, ++step) {
+            const int rows = (int)(b->n_rows - first < minibatch ? b->n_rows - first : minibatch);
+            rc = ppo_step(c, vs, b, perm ? perm + (size_t)pass * b->n_rows : nullptr, first, rows, p, p->adam_t + step,
+                          eps ? eps + eps_step * step : nullptr, noise, rng_seed, rng_offset + (uint64_t)step,
+                          stats_out + 5 * (size_t)step, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+    params_touched(c, (hipStream_t)stream);
+    return 0;
+}
+
+int pvae_ppo_launches(pvae_ctx* c, int32_t* per_step) {
+    if (!c || !per_step) return fail(-1, "null argument");
+    *per_step = c->ppo.launches;
+    return 0;
+}
+
+}  // extern "C"

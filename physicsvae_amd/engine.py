@@ -891,6 +891,95 @@ class HipEngine:
         return z
 
 
+    # -- PPO learner step (include/pvae.h "PPO learner step of PhysicsVAE") ----------------------------
+    def ppo_bind(self, value_engine, log_std, train_log_std=False):
+        """Allocate (once, lazily) the PPO step's gradient arena, Adam moments and scratch -- buffers of the parameter
+        arena's layout of their own, not the supervised trainer's `grads` / `exp_avg` / `exp_avg_sq` -- and bind them
+        together with the log-std vector (Da contiguous floats on the device; `train_log_std`: its moments live here too)
+        and the one-stack `StackSetEngine` that carries the value branch."""
+        self._need_gpu()
+        if getattr(self, "ppo_grad", None) is None:
+            z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)      # noqa: E731
+            self.ppo_grad, self.ppo_m, self.ppo_v = z(self.arena_floats), z(self.arena_floats), z(self.arena_floats)
+            self.ppo_scratch_bytes = int(self.lib.pvae_ppo_workspace_bytes(C.byref(self.cfg)))
+            self.ppo_scratch = z(self.ppo_scratch_bytes // 4 + 4)
+            self.ppo_ls_m = self.ppo_ls_v = None
+        assert log_std.dtype == torch.float32 and log_std.device == self.device and log_std.is_contiguous() \
+            and log_std.numel() == self.arch.Da, "log_std must be %d contiguous floats on %s" % (self.arch.Da, self.device)
+        if train_log_std and self.ppo_ls_m is None:
+            self.ppo_ls_m, self.ppo_ls_v = torch.zeros_like(log_std), torch.zeros_like(log_std)
+        value_engine.ppo_bind(None, False)
+        self._ppo_keep = (log_std, value_engine)           # (kept alive while bound)
+        moments = (self.ppo_ls_m, self.ppo_ls_v) if train_log_std else (None, None)
+        _lib.check(self.lib.pvae_ppo_bind(
+            self.ctx, self.ppo_grad.data_ptr(), self.ppo_m.data_ptr(), self.ppo_v.data_ptr(), self.ppo_scratch.data_ptr(),
+            self.ppo_scratch_bytes, log_std.data_ptr(), moments[0].data_ptr() if moments[0] is not None else None,
+            moments[1].data_ptr() if moments[1] is not None else None, value_engine.ctx), "pvae_ppo_bind")
+
+    def ppo_reset(self):
+        """Adam's moments of the PPO step back to zero (the gradient arena and the scratch are rewritten by every step)."""
+        for t in (getattr(self, "ppo_m", None), getattr(self, "ppo_v", None), getattr(self, "ppo_ls_m", None),
+                  getattr(self, "ppo_ls_v", None)):
+            if t is not None:
+                t.zero_()
+        keep = getattr(self, "_ppo_keep", None)
+        if keep is not None:
+            keep[1].ppo_reset()
+
+    def ppo_batch(self, batch):
+        """(pvae_fc_ppo_batch, the tensors it points to) from a dict of device tensors under the names of the loss's
+        specification; obs is [n, 2 Db]."""
+        return make_ppo_batch(batch, self.device, self.arch.Da, 2 * self.arch.Db)
+
+    def _ppo_eps(self, eps, shape):
+        if eps is None:
+            return None
+        eps = eps.to(self.device, torch.float32).contiguous()
+        assert tuple(eps.shape) == shape, "eps must be %s, got %s" % (shape, tuple(eps.shape))
+        return eps
+
+    def ppo_step(self, batch, params, first, rows, index=None, eps=None, noise=True, seed=0, offset=0, stats_out=None):
+        """`pvae_ppo_step`: one minibatch -- rows `index[first : first + rows]` of the batch (index None: rows first ..) --
+        forward, loss, backward and Adam in one call; `eps` [rows, Z] or None (Philox at (seed, offset)).  Returns the five
+        stats (a device tensor, nothing synchronises)."""
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        if stats_out is None:
+            stats_out = torch.empty(5, dtype=torch.float32, device=self.device)
+        _check_index(index, int(b.n_rows), self.device)
+        eps = self._ppo_eps(eps, (int(rows), self.arch.Z))
+        _lib.check(self.lib.pvae_ppo_step(self.ctx, C.byref(b), index.data_ptr() if index is not None else None, int(first),
+                                          int(rows), C.byref(params), eps.data_ptr() if eps is not None else None,
+                                          1 if noise else 0, int(seed), int(offset), stats_out.data_ptr(), self._stream()),
+                   "pvae_ppo_step")
+        return stats_out
+
+    def ppo_sgd(self, batch, params, minibatch, num_sgd_iter, perm=None, eps=None, noise=True, seed=0, offset=0):
+        """`pvae_ppo_sgd`: `num_sgd_iter` passes over the batch in minibatches of `minibatch` rows (the last one short), pass
+        p in the order `perm[p]`; step i uses `eps[i]` (eps [steps, minibatch, Z]) or Philox offset `offset + i`, and Adam
+        time step `params.adam_t + i`.  Returns stats [steps, 5] on the device; nothing synchronises."""
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        n = int(b.n_rows)
+        steps = int(num_sgd_iter) * ((n + int(minibatch) - 1) // int(minibatch))
+        stats = torch.empty(steps, 5, dtype=torch.float32, device=self.device)
+        if perm is not None:
+            assert tuple(perm.shape) == (int(num_sgd_iter), n), "perm must be [num_sgd_iter, n_rows]"
+        _check_index(perm, n, self.device)
+        eps = self._ppo_eps(eps, (steps, int(minibatch), self.arch.Z))
+        _lib.check(self.lib.pvae_ppo_sgd(self.ctx, C.byref(b), perm.data_ptr() if perm is not None else None, int(minibatch),
+                                         int(num_sgd_iter), C.byref(params), eps.data_ptr() if eps is not None else None,
+                                         1 if noise else 0, int(seed), int(offset), stats.data_ptr(), self._stream()),
+                   "pvae_ppo_sgd")
+        return stats
+
+    def ppo_launches(self):
+        """Kernel launches of the last PPO step."""
+        n = C.c_int32()
+        _lib.check(self.lib.pvae_ppo_launches(self.ctx, C.byref(n)), "pvae_ppo_launches")
+        return n.value
+
+
 def gemm_probe(kind, a, b, c, bias_or_mask=None, relu=False, m=0, n=0, k=0):
     """Kernel-level entry (tests / roofline probes).  Tensors are dense fp32 on the GPU."""
     lib = _lib.load()
