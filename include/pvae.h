@@ -859,6 +859,66 @@ int pvae_ppo_sgd(pvae_ctx* ctx, const pvae_fc_ppo_batch* batch, const int32_t* p
 int pvae_ppo_launches(pvae_ctx* ctx, int32_t* per_step);
 int pvae_ppo_sizeof(int which);
 
+/* ---- Train-batch preparation for PhysicsVAE: evaluate, bootstrap, GAE, standardisation -------------------------------
+ * "Train-batch preparation for the PPO learner" above, with PhysicsVAE as the policy: from a device-resident rollout to the
+ * seven columns pvae_ppo_sgd reads, on one stream.  The rollout, the parameters and the outputs are the structs of that
+ * section: pvae_fc_rollout with obs [n_rows][2 Db], k = Da and boot_obs [n_segs][2 Db]; pvae_gae_params with log_std_kind
+ * 0 or 1; pvae_fc_prepared.  The action distribution of a row depends on a latent draw, which pvae_ppo_draws names:
+ *   eps        device [n_rows][Z] draws, row-aligned: the chunk that starts at row f reads eps + f Z, so the result does not
+ *              depend on the chunking.  NULL: Philox (rng_seed, rng_offset + i) for chunk i, as step i of pvae_ppo_sgd
+ *   eps_out    optional, device [n_rows][Z]: receives the draws actually used (workspace panel 6 of each chunk), so that a
+ *              learner or a test can replay them; zeros with noise = 0 and with the prior False
+ *   noise      0: z = mu
+ *
+ * Launches.  Evaluate, per chunk of at most max_batch rows, in order:
+ *   copy-in            rows f .. f + rows - 1 of obs into the encoder's, the decoder's and the value stack's input panel
+ *                      (whole padded panels; an input subset's left-out block is zeros)
+ *   TE layers          one per layer -> [mu | logvar]
+ *   sampler            z into the decoder's input panel, the draws used into workspace panel 6
+ *   MD layers          one per layer -> a_hat
+ *   value layers       the stack set's forward, one per layer
+ *   epilogue           ONE launch: reads a_hat, the bound log-std vector and the value where they lie in their panels and
+ *                      writes vf_preds[r], old_dist[r] = [a_hat | log_std] and old_logp[r] of actions[r] (the loss head's
+ *                      logp, term for term: the learner's first step sees a ratio of exactly 1 under the same draws) and,
+ *                      eps_out given, the chunk's draws
+ * No backward follows, so a chunk of <= 4 rows (the GEMV forward, which writes the live rows only) needs no launch that
+ * zeroes pad rows: nothing reads them.  Bootstrap, per chunk of at most max_batch segments: the boot copy-in (never reads
+ * the row of a done segment), the value layers alone, the epilogue in its bootstrap mode (last_value[s] = 0 where
+ * seg_done[s]).  GAE: ONE launch; standardise: ONE launch, skipped when standardize == 0 -- the launches of the section
+ * above, with pvae_fc_gae_workspace_bytes(n_segs) for the scratch.  With T / M / V layers in the encoder, the decoder
+ * and the value stack: evaluate = ceil(n_rows / max_batch) (T + M + V + 3), rest = ceil(n_segs / max_batch) (V + 2) + 1 +
+ * standardize.  No atomics, no host synchronisation, no allocation, fixed summation order: the same inputs give the same
+ * bits.  The parameters are not written (a running rollout server is not disturbed); the input and output panels of the
+ * three stacks and workspace panel 6 are.
+ *
+ *   pvae_ppo_evaluate      the evaluate pass alone: the rows (when out->vf_preds is given; then old_dist and old_logp too,
+ *                          and `draws`) and / or the bootstrap values (when out->last_value is given; `draws` may be NULL
+ *                          when only they are asked for).
+ *   pvae_ppo_prepare       all of it: evaluate -- or, when the rollout carries the sampler's own vf_preds, old_dist and
+ *                          old_logp (all three or none), those as they are, no launch over the rows and `draws` not read
+ *                          (may be NULL) --, bootstrap, GAE, standardise.
+ *   pvae_ppo_gae_launches  launches of the last pvae_ppo_prepare / pvae_ppo_evaluate on this context: the evaluate pass over
+ *                          the rows, and the rest (bootstrap + GAE + standardise).  Both counters are zeroed on entry of
+ *                          either call, so after a refused call they read 0, 0 (after one that a HIP error cut short: 0, 0 too).
+ * pvae_ppo_sizeof does not cover pvae_ppo_draws (which = 3 stays refused): a binding checks that struct against this header.
+ * pvae_ppo_bind must have been called (the log-std vector and the [value] stack set are the ones bound there).  Needs
+ * lookahead 1, prior ZERO_MEAN or NONE, no helper stack, log_std_kind 0 or 1.  Every kernel bound is clamped: a seg_start
+ * that breaks its contract gives wrong numbers, never an access outside the columns.  Bad arguments, an unbound buffer, a
+ * short scratch or ends of seg_start that are not 0 and n_rows return a negative code and launch nothing. */
+typedef struct pvae_ppo_draws {
+    const float* eps;             /* [n_rows][Z], or NULL: Philox */
+    float* eps_out;               /* [n_rows][Z], or NULL: not wanted */
+    int32_t noise;                /* 0: z = mu */
+    int32_t reserved;
+    uint64_t rng_seed, rng_offset;
+} pvae_ppo_draws;
+int pvae_ppo_evaluate(pvae_ctx* ctx, const pvae_fc_rollout* rollout, const pvae_gae_params* params,
+                      const pvae_ppo_draws* draws, const pvae_fc_prepared* out, void* stream);
+int pvae_ppo_prepare(pvae_ctx* ctx, const pvae_fc_rollout* rollout, const pvae_gae_params* params,
+                     const pvae_ppo_draws* draws, const pvae_fc_prepared* out, void* scratch, size_t scratch_bytes,
+                     void* stream);
+int pvae_ppo_gae_launches(pvae_ctx* ctx, int32_t* evaluate, int32_t* rest);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

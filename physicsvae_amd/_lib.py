@@ -111,6 +111,12 @@ class FcPrepared(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("vf_preds", "old_dist", "old_logp", "last_value", "advantages", "value_targets")]
 
 
+class PpoDraws(C.Structure):
+    """pvae_ppo_draws: the latent draws of PhysicsVAE's evaluate pass -- supplied, or Philox at (rng_seed, rng_offset + chunk)."""
+    _fields_ = [("eps", C.c_void_p), ("eps_out", C.c_void_p), ("noise", C.c_int32), ("reserved", C.c_int32),
+                ("rng_seed", C.c_uint64), ("rng_offset", C.c_uint64)]
+
+
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
 
 _P = C.c_void_p
@@ -220,6 +226,11 @@ _SIGS = {
                                C.c_uint64, C.c_uint64, _P, _P]),
     "pvae_ppo_launches": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "pvae_ppo_sizeof": (C.c_int, [C.c_int]),
+    "pvae_ppo_evaluate": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(FcPrepared),
+                                    _P]),
+    "pvae_ppo_prepare": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(FcPrepared),
+                                   _P, C.c_size_t, _P]),
+    "pvae_ppo_gae_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),

@@ -467,7 +467,8 @@ fc_boot_copy_kernel(const float* __restrict__ src, int n, int rows, float* __res
 // The epilogue of one evaluated chunk: a wave per row reads the stacks' outputs in their panels and writes vf[r],
 // dist[r] = [mean | log_std] and logp[r] of actions[r] -- the arithmetic of fc_ppo_head_kernel's logp, term for term, so
 // that the learner's first step sees a ratio of exactly 1.  mean == NULL: the bootstrap use -- the value stack ran alone;
-// vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.
+// vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.  eps_dst (PhysicsVAE's evaluate
+// pass): the latent draws of the chunk, eps_src [rows][Z], copied to the caller's rows.
 constexpr int kEvalMaxBlocks = 1024;
 struct FcEval {
     const float* mean; const float* ls; const float* value;
@@ -477,6 +478,7 @@ struct FcEval {
     const uint8_t* done;
     int rows, k;
     float* vf; float* dist; float* logp;
+    const float* eps_src; float* eps_dst; int Z;
 };
 __global__ void __launch_bounds__(256)
 fc_eval_epilogue_kernel(FcEval e) {
@@ -506,6 +508,8 @@ fc_eval_epilogue_kernel(FcEval e) {
             e.logp[r] = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                  // log(2 pi)
             e.vf[r] = e.value[r * e.ld_value];
         }
+        if (e.eps_dst)
+            for (int j = lane; j < e.Z; j += 64) e.eps_dst[(size_t)r * e.Z + j] = e.eps_src[(size_t)r * e.Z + j];
     }
 }
 
@@ -1183,13 +1187,11 @@ int eval_boot(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_fc_prepared* out
         Run r{c, st, rows, pad32(rows)};
         r.want[1] = true;
         set_range(r, L.S);
-        int grid = (r.rows_pad * L.ld0 + 255) / 256;
-        if (grid > 1024) grid = 1024;
-        hipLaunchKernelGGL(fc_boot_copy_kernel, dim3(grid), dim3(256), 0, st, ro->boot_obs + (size_t)first * L.cfg.n_in,
-                           L.cfg.n_in, rows, c->ws + c->W.in, L.ld0, r.rows_pad, ro->seg_done + first);
-        HIP_TRY(hipGetLastError());
-        ++r.launches;
         int rc;
+        if ((rc = ppo_boot_copy_launch(ro->boot_obs + (size_t)first * L.cfg.n_in, L.cfg.n_in, rows, c->ws + c->W.in, L.ld0,
+                                       r.rows_pad, ro->seg_done + first, st)))
+            return rc;
+        ++r.launches;
         if ((rc = run_forward(r, nullptr))) return rc;
         FcEval e;
         memset(&e, 0, sizeof(e));
@@ -1246,6 +1248,37 @@ int fc_value_backward(pvae_fc* c, int rows, hipStream_t st, int* launches) {
     const int rc = run_backward_layers<EpiGradStore>(r, false, c->grad, 1);
     *launches += r.launches;
     return rc;
+}
+
+int ppo_eval_launch(const PpoEvalIo& io, hipStream_t st) {
+    FcEval e;
+    memset(&e, 0, sizeof(e));
+    e.mean = io.mean; e.ld_mean = io.ld_mean; e.ls = io.ls; e.ld_ls = 0; e.value = io.value; e.ld_value = io.ld_value;
+    e.actions = io.actions; e.done = io.done; e.rows = io.rows; e.k = io.k;
+    e.vf = io.vf; e.dist = io.dist; e.logp = io.logp;
+    e.eps_src = io.eps_src; e.eps_dst = io.eps_dst; e.Z = io.Z;
+    Run r{nullptr, st, io.rows, pad32(io.rows)};
+    return launch_eval_epilogue(r, e);
+}
+
+int ppo_boot_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const uint8_t* done, hipStream_t st) {
+    int grid = (rows_pad * ld + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(fc_boot_copy_kernel, dim3(grid), dim3(256), 0, st, src, n, rows, dst, ld, rows_pad, done);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int gae_check_params(const pvae_gae_params* p) { return check_gae_params(p); }
+int gae_check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) { return check_boot(ro, out); }
+int gae_check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last) {
+    return check_segments(n_rows, n_segs, seg_first, seg_last);
+}
+int gae_check_scratch(const void* scratch, size_t bytes, int n_segs) { return check_gae_scratch(scratch, bytes, n_segs); }
+
+int gae_launch(const float* rewards, const float* vpred, const float* last_value, const int32_t* seg_start, long long n_rows,
+               int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st, int* launches) {
+    return run_gae(rewards, vpred, last_value, nullptr, seg_start, n_rows, n_segs, p, adv, vtarg, scratch, st, *launches);
 }
 
 size_t ppo_head_scratch_floats(int max_batch, int k) { return (size_t)head_waves(pad32(max_batch)) * part_stride(k, true); }

@@ -5,7 +5,7 @@
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
 //   pvae_fc.hip              the stack set and the PPO learner step on it
-//   pvae_ppo.hip             the PPO learner step of PhysicsVAE: joins the launches of pvae.hip and pvae_fc.hip
+//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae.hip and pvae_fc.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -243,6 +243,7 @@ struct pvae_ctx {
         float* log_std = nullptr; float* log_std_m = nullptr; float* log_std_v = nullptr;
         pvae_fc* value = nullptr;
         int launches = 0;
+        int eval_launches = 0, gae_launches = 0;         // pvae_ppo_prepare / pvae_ppo_evaluate (pvae_ppo_gae_launches)
     } ppo;
 };
 static inline void params_touched(pvae_ctx* c, hipStream_t st, bool queued = true) {
@@ -377,3 +378,27 @@ struct PpoAdamSegs {
 };
 int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
                     int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);
+// pvae_fc.hip: the launches and argument checks of train-batch preparation, for pvae_ppo_evaluate / pvae_ppo_prepare.
+// The evaluate epilogue of one chunk on any panels: vf[r], dist[r] = [mean | ls] and logp[r] of actions[r] for rows
+// r < rows (pointers: the chunk's first row), and, eps_dst given, the chunk's draws eps_src [rows][Z] copied out.
+// mean == NULL: the bootstrap use, vf[r] = done[r] ? 0 : value[r].
+struct PpoEvalIo {
+    const float* mean; long long ld_mean;
+    const float* ls;                            // one vector of k values for all rows
+    const float* value; long long ld_value;
+    const float* actions;
+    const uint8_t* done;
+    int rows, k;
+    float* vf; float* dist; float* logp;
+    const float* eps_src; float* eps_dst; int Z;
+};
+int ppo_eval_launch(const PpoEvalIo& io, hipStream_t st);
+// rows of boot_obs [rows][n] into a [rows_pad][ld] panel: zeros in the pads and in the row of a done segment, never read
+int ppo_boot_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const uint8_t* done, hipStream_t st);
+int gae_check_params(const pvae_gae_params* p);
+int gae_check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out);
+int gae_check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last);
+int gae_check_scratch(const void* scratch, size_t bytes, int n_segs);
+// the GAE launch and, with params->standardize, the rescale launch (last_value already 0 where a segment is done)
+int gae_launch(const float* rewards, const float* vpred, const float* last_value, const int32_t* seg_start, long long n_rows,
+               int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st, int* launches);

@@ -6,6 +6,10 @@
 // (the three stacks share no panel).  Launch order of a step:
 //   copy-in | [rows <= 4: zero pad rows] | TE layers | sampler | MD layers | value layers | loss head |
 //   MD backward (input gradient when the encoder is trained) | sampler backward | TE backward | value backward | Adam + stats
+// and its first half, train-batch preparation (pvae_ppo_evaluate / pvae_ppo_prepare): the step's forward launches in chunks of
+// max_batch rows with the stack set's evaluate epilogue in place of the loss head, then that path's bootstrap, GAE and
+// standardise launches.  Launch order of a chunk:
+//   copy-in | TE layers | sampler | MD layers | value layers | epilogue
 #include "pvae_internal.h"
 
 namespace {
@@ -81,8 +85,42 @@ ppo_sampler_bwd_kernel(const float* __restrict__ te_out, const float* __restrict
 
 enum { kTrainTE = 1, kTrainMD = 2, kTrainValue = 4 };
 
+// the copy-in launch: rows `index[r]` (index NULL: row0 + r) of obs [n_rows][2 Db] into the three input panels
+int ppo_copy_in(pvae_ctx* c, const FcValueStack& vs, const float* obs, const int32_t* index, long long row0, long long n_rows,
+                int rows, hipStream_t st) {
+    const pvae_config& cfg = c->L.cfg;
+    const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    const NetLayout& MD = c->L.net[PVAE_NET_MD];
+    const int rows_pad = pad32(rows);
+    float* w = c->ws;
+    PpoCopyIn a;
+    memset(&a, 0, sizeof(a));
+    a.obs = obs; a.index = index; a.row0 = row0; a.n_rows = n_rows;
+    a.rows = rows; a.rows_pad = rows_pad; a.Db = cfg.dim_body;
+    const int te = cfg.te_inputs, md = cfg.md_inputs;
+    a.in_off = (te == PVAE_INPUT_TASK ? 1 : 0) | (te == PVAE_INPUT_BODY ? 2 : 0) | (md == PVAE_INPUT_TASK ? 4 : 0);
+    a.dst[0] = w + c->W.net[PVAE_NET_TE].in; a.ld[0] = TE.layers[0].ld;
+    a.dst[1] = w + c->W.net[PVAE_NET_MD].in; a.ld[1] = MD.layers[0].ld;
+    a.dst[2] = vs.in; a.ld[2] = vs.ld_in;
+    const int ldmax = std::max(a.ld[0], std::max(a.ld[1], a.ld[2]));
+    int gx = (rows_pad * ldmax + 255) / 256;
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(ppo_copy_in_kernel, dim3(gx, 3), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 size_t scratch_bytes(const pvae_config& cfg) {
     return (ppo_head_scratch_floats(cfg.max_batch, cfg.dim_action) * sizeof(float) + 15) / 16 * 16;
+}
+
+// what neither the step nor the evaluate pass runs: lookahead > 1, the learned and the sphere prior, the helper
+int check_ppo_config(const pvae_config& cfg) {
+    if (cfg.lookahead != 1) return fail(-1, "the PPO step needs a lookahead 1 context, got %d", cfg.lookahead);
+    if (cfg.prior_kind != PVAE_PRIOR_ZERO_MEAN && cfg.prior_kind != PVAE_PRIOR_NONE)
+        return fail(-1, "the PPO step supports the priors normal_zero_mean_one_std and False, got prior_kind %d", cfg.prior_kind);
+    if (cfg.mh_depth > 0) return fail(-1, "the PPO step does not run the motor decoder's helper");
+    return 0;
 }
 
 int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows,
@@ -95,10 +133,7 @@ int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params*
     if (!b->obs) return fail(-1, "batch obs is null");
     if (!stats) return fail(-1, "stats_out is null");
     const pvae_config& cfg = c->L.cfg;
-    if (cfg.lookahead != 1) return fail(-1, "the PPO step needs a lookahead 1 context, got %d", cfg.lookahead);
-    if (cfg.prior_kind != PVAE_PRIOR_ZERO_MEAN && cfg.prior_kind != PVAE_PRIOR_NONE)
-        return fail(-1, "the PPO step supports the priors normal_zero_mean_one_std and False, got prior_kind %d", cfg.prior_kind);
-    if (cfg.mh_depth > 0) return fail(-1, "the PPO step does not run the motor decoder's helper");
+    if ((rc = check_ppo_config(cfg))) return rc;
     if (p->log_std_kind != 0 && p->log_std_kind != 1) return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
     if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
     if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_ppo_bind)");
@@ -130,23 +165,8 @@ int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, co
     float* w = c->ws;
     int launches = 0, rc;
     ppo_enter(c, rows);
-    {
-        PpoCopyIn a;
-        memset(&a, 0, sizeof(a));
-        a.obs = b->obs; a.index = index ? index + first : nullptr; a.row0 = first; a.n_rows = b->n_rows;
-        a.rows = rows; a.rows_pad = rows_pad; a.Db = Db;
-        const int te = cfg.te_inputs, md = cfg.md_inputs;
-        a.in_off = (te == PVAE_INPUT_TASK ? 1 : 0) | (te == PVAE_INPUT_BODY ? 2 : 0) | (md == PVAE_INPUT_TASK ? 4 : 0);
-        a.dst[0] = w + wte.in; a.ld[0] = TE.layers[0].ld;
-        a.dst[1] = w + wmd.in; a.ld[1] = MD.layers[0].ld;
-        a.dst[2] = vs.in; a.ld[2] = vs.ld_in;
-        const int ldmax = std::max(a.ld[0], std::max(a.ld[1], a.ld[2]));
-        int gx = (rows_pad * ldmax + 255) / 256;
-        if (gx > 256) gx = 256;
-        hipLaunchKernelGGL(ppo_copy_in_kernel, dim3(gx, 3), dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        ++launches;
-    }
+    if ((rc = ppo_copy_in(c, vs, b->obs, index ? index + first : nullptr, first, b->n_rows, rows, st))) return rc;
+    ++launches;
     if (rows <= 4 && rows < rows_pad) {
         PpoZeroRows z;
         memset(&z, 0, sizeof(z));
@@ -208,6 +228,94 @@ int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, co
         ++launches;
     }
     c->ppo.launches = launches;
+    return 0;
+}
+
+// ---- train-batch preparation (include/pvae.h "Train-batch preparation for PhysicsVAE") ----
+// what evaluate and prepare ask of the context; `rows_pass`: the policy's distribution is evaluated over the rows
+int check_eval(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
+               const pvae_fc_prepared* out, bool rows_pass, FcValueStack* vs) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!ro || !p || !out) return fail(-1, "null rollout, params or outputs");
+    const pvae_ctx::Ppo& q = c->ppo;
+    if (!q.value) return fail(-2, "pvae_ppo_bind has not been called");
+    const pvae_config& cfg = c->L.cfg;
+    if ((rc = check_ppo_config(cfg))) return rc;
+    if (ro->n_rows < 1 || ro->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)ro->n_rows);
+    if (rows_pass) {
+        if (p->log_std_kind != 0 && p->log_std_kind != 1)
+            return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
+        if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
+        if (ro->k != cfg.dim_action) return fail(-1, "rollout k %d != dim_action %d", ro->k, cfg.dim_action);
+        if (!ro->obs || !ro->actions) return fail(-1, "rollout obs or actions is null");
+        if (!out->vf_preds || !out->old_dist || !out->old_logp) return fail(-1, "an evaluate output (vf_preds, old_dist, old_logp) is null");
+        if (!d) return fail(-1, "draws is null");
+        if (d->noise != 0 && d->noise != 1) return fail(-1, "draws noise must be 0 or 1, got %d", d->noise);
+    }
+    if ((rc = fc_value_stack(q.value, vs))) return rc;
+    if (vs->n_in != 2 * cfg.dim_body) return fail(-1, "the value stack reads %d inputs, the observation has %d", vs->n_in, 2 * cfg.dim_body);
+    return 0;
+}
+
+int eval_chunk(const pvae_ctx* c, const FcValueStack& vs) { return std::min(c->L.cfg.max_batch, vs.max_batch); }
+
+// rows of the rollout through encoder, sampler, decoder and value stack in chunks of max_batch:
+// copy-in | TE layers | sampler | MD layers | value layers | epilogue
+int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_ppo_draws* d,
+              const pvae_fc_prepared* out, hipStream_t st, int& launches) {
+    const pvae_config& cfg = c->L.cfg;
+    const int Z = cfg.latent, k = ro->k, chunk = eval_chunk(c, vs);
+    const Layer& md_last = c->L.net[PVAE_NET_MD].layers.back();
+    uint64_t i = 0;
+    for (long long first = 0; first < ro->n_rows; first += chunk, ++i) {
+        const int rows = (int)(ro->n_rows - first < chunk ? ro->n_rows - first : chunk);
+        int rc;
+        ppo_enter(c, rows);
+        if ((rc = ppo_copy_in(c, vs, ro->obs, nullptr, first, ro->n_rows, rows, st))) return rc;
+        ++launches;
+        if ((rc = ppo_forward_net(c, PVAE_NET_TE, rows, st, &launches))) return rc;
+        if ((rc = ppo_sampler(c, d->eps ? d->eps + (size_t)first * Z : nullptr, rows, d->noise, d->rng_seed, d->rng_offset + i, st,
+                              &launches)))
+            return rc;
+        if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
+        if ((rc = fc_value_forward(c->ppo.value, rows, st, &launches))) return rc;
+        PpoEvalIo e;
+        memset(&e, 0, sizeof(e));
+        e.mean = c->ws + c->W.net[PVAE_NET_MD].act.back(); e.ld_mean = md_last.n_out_pad;
+        e.ls = c->ppo.log_std;
+        e.value = vs.value; e.ld_value = vs.ld_value;
+        e.actions = ro->actions + (size_t)first * k;
+        e.rows = rows; e.k = k;
+        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
+        if (d->eps_out) { e.eps_src = c->ws + c->W.eps; e.eps_dst = d->eps_out + (size_t)first * Z; e.Z = Z; }
+        if ((rc = ppo_eval_launch(e, st))) return rc;
+        ++launches;
+    }
+    return 0;
+}
+
+// last_value[s] = seg_done[s] ? 0 : value(boot_obs[s]): the value stack alone, in chunks of max_batch segments
+int eval_boot(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st,
+              int& launches) {
+    const int chunk = eval_chunk(c, vs);
+    for (int first = 0; first < ro->n_segs; first += chunk) {
+        const int rows = ro->n_segs - first < chunk ? ro->n_segs - first : chunk;
+        int rc;
+        if ((rc = ppo_boot_copy_launch(ro->boot_obs + (size_t)first * vs.n_in, vs.n_in, rows, vs.in, vs.ld_in, pad32(rows),
+                                       ro->seg_done + first, st)))
+            return rc;
+        ++launches;
+        if ((rc = fc_value_forward(c->ppo.value, rows, st, &launches))) return rc;
+        PpoEvalIo e;
+        memset(&e, 0, sizeof(e));
+        e.value = vs.value; e.ld_value = vs.ld_value;
+        e.done = ro->seg_done + first;
+        e.rows = rows; e.k = ro->k;
+        e.vf = out->last_value + first;
+        if ((rc = ppo_eval_launch(e, st))) return rc;
+        ++launches;
+    }
     return 0;
 }
 
@@ -287,6 +395,56 @@ int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, i
 int pvae_ppo_launches(pvae_ctx* c, int32_t* per_step) {
     if (!c || !per_step) return fail(-1, "null argument");
     *per_step = c->ppo.launches;
+    return 0;
+}
+
+int pvae_ppo_evaluate(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
+                      const pvae_fc_prepared* out, void* stream) {
+    const bool rows_pass = out && out->vf_preds, boot = out && out->last_value;
+    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
+    FcValueStack vs;
+    int rc = check_eval(c, ro, p, d, out, rows_pass, &vs);
+    if (rc) return rc;
+    if (!rows_pass && !boot) return fail(-1, "neither vf_preds nor last_value: nothing to compute");
+    if (boot && (rc = gae_check_boot(ro, out))) return rc;
+    int ev = 0, rest = 0;
+    if (rows_pass && (rc = eval_rows(c, vs, ro, d, out, (hipStream_t)stream, ev))) return rc;
+    if (boot && (rc = eval_boot(c, vs, ro, out, (hipStream_t)stream, rest))) return rc;
+    c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
+    return 0;
+}
+
+int pvae_ppo_prepare(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
+                     const pvae_fc_prepared* out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
+    int rc = gae_check_params(p);
+    if (rc) return rc;
+    if (!ro || !out) return fail(-1, "null rollout or outputs");
+    const int given = (ro->vf_preds != nullptr) + (ro->old_dist != nullptr) + (ro->old_logp != nullptr);
+    if (given != 0 && given != 3) return fail(-1, "the sampler's vf_preds, old_dist and old_logp go together: all three or none");
+    FcValueStack vs;
+    if ((rc = check_eval(c, ro, p, d, out, given == 0, &vs))) return rc;
+    if ((rc = gae_check_boot(ro, out))) return rc;
+    if (!ro->rewards || !ro->seg_start) return fail(-1, "rollout rewards or seg_start is null");
+    if (!out->advantages || !out->value_targets) return fail(-1, "advantages or value_targets is null");
+    if ((rc = gae_check_segments(ro->n_rows, ro->n_segs, ro->seg_first, ro->seg_last))) return rc;
+    if ((rc = gae_check_scratch(scratch, scratch_bytes, ro->n_segs))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int ev = 0, rest = 0;
+    if (given == 0 && (rc = eval_rows(c, vs, ro, d, out, st, ev))) return rc;
+    if ((rc = eval_boot(c, vs, ro, out, st, rest))) return rc;
+    // (last_value already holds the zeros of the done segments)
+    if ((rc = gae_launch(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, ro->seg_start, ro->n_rows, ro->n_segs,
+                         p, out->advantages, out->value_targets, scratch, st, &rest)))
+        return rc;
+    c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
+    return 0;
+}
+
+int pvae_ppo_gae_launches(pvae_ctx* c, int32_t* evaluate, int32_t* rest) {
+    if (!c) return fail(-1, "null ctx");
+    if (evaluate) *evaluate = c->ppo.eval_launches;
+    if (rest) *rest = c->ppo.gae_launches;
     return 0;
 }
 

@@ -979,6 +979,69 @@ class HipEngine:
         _lib.check(self.lib.pvae_ppo_launches(self.ctx, C.byref(n)), "pvae_ppo_launches")
         return n.value
 
+    # -- train-batch preparation (include/pvae.h "Train-batch preparation for PhysicsVAE") ------------
+    def _ppo_draws(self, n, eps, noise, seed, offset, out, want):
+        """(pvae_ppo_draws, eps kept alive, latent_eps or None): `eps` [n, Z] supplied draws or None (Philox); `want`: the
+        rows are evaluated, so the draws used are written to out["latent_eps"] (allocated when not given)."""
+        d = _lib.PpoDraws()
+        eps = self._ppo_eps(eps, (n, self.arch.Z))
+        used = None
+        if want:
+            used = (out or {}).get("latent_eps")
+            if used is None:
+                used = torch.empty(n, self.arch.Z, dtype=torch.float32, device=self.device)
+            assert used.dtype == torch.float32 and used.device == self.device and used.is_contiguous() \
+                and tuple(used.shape) == (n, self.arch.Z), "out['latent_eps'] must be contiguous float32 [%d, %d]" % (n, self.arch.Z)
+            d.eps_out = used.data_ptr()
+        d.eps = eps.data_ptr() if eps is not None else None
+        d.noise, d.rng_seed, d.rng_offset = 1 if noise else 0, int(seed), int(offset)
+        return d, eps, used
+
+    def ppo_evaluate(self, rollout, params, eps=None, noise=True, seed=0, offset=0, out=None):
+        """`pvae_ppo_evaluate`: the current policy and value function over a device-resident rollout, in chunks of
+        `max_batch` rows -- vf_preds [N], old_dist [N, 2 Da] = [a_hat | log_std], old_logp [N] of `actions` and latent_eps
+        [N, Z], the draws used (when the rollout has obs and actions), and last_value [S], the bootstrap values (when it has
+        seg_done and boot_obs; 0 for a done segment, whose boot_obs row is never read).  `eps` [N, Z]: the draws, row by row
+        (None: Philox, chunk i at (seed, offset + i)); `noise` False: z = mu.  `ppo_bind` must have been called.  Returns
+        the dict of what was computed; nothing synchronises."""
+        self._need_gpu()
+        ro, need, names = evaluate_plan(rollout, self.device)
+        r, keep = make_rollout(ro, need, self.device, 2 * self.arch.Db, self.arch.Da)
+        o, res = make_prepared(int(r.n_rows), int(r.n_segs), names, out, self.device, self.arch.Da)
+        d, eps, used = self._ppo_draws(int(r.n_rows), eps, noise, seed, offset, out, "vf_preds" in names)
+        _lib.check(self.lib.pvae_ppo_evaluate(self.ctx, C.byref(r), C.byref(params), C.byref(d), C.byref(o), self._stream()),
+                   "pvae_ppo_evaluate")
+        if used is not None:
+            res["latent_eps"] = used
+        return res
+
+    def ppo_prepare(self, rollout, params, eps=None, noise=True, seed=0, offset=0, out=None):
+        """`pvae_ppo_prepare`: evaluate (unless the rollout carries the sampler's own vf_preds, old_dist and old_logp: all
+        three or none), bootstrap, GAE and -- with `params.standardize` -- the standardisation, all enqueued on the current
+        stream; nothing synchronises.  Returns {vf_preds, old_dist, old_logp, latent_eps, last_value, advantages,
+        value_targets}; the sampler's columns, when given, come back as they are (and latent_eps is None: nothing was
+        drawn).  Draws as `ppo_evaluate`; `out`: tensors to write into, by those names."""
+        self._need_gpu()
+        r, keep = make_rollout(rollout, ("obs", "actions", "rewards", "seg_start", "boot_obs"), self.device, 2 * self.arch.Db,
+                               self.arch.Da)
+        names, given = prepare_plan(rollout)
+        o, res = make_prepared(int(r.n_rows), int(r.n_segs), names, out, self.device, self.arch.Da)
+        d, eps, used = self._ppo_draws(int(r.n_rows), None if given else eps, noise, seed, offset, out, not given)
+        scratch, nbytes = gae_scratch_for(self, r.n_segs)
+        _lib.check(self.lib.pvae_ppo_prepare(self.ctx, C.byref(r), C.byref(params), C.byref(d), C.byref(o), scratch.data_ptr(),
+                                             nbytes, self._stream()), "pvae_ppo_prepare")
+        if given:
+            res.update({name: rollout[name] for name in ("vf_preds", "old_dist", "old_logp")})
+        res["latent_eps"] = used
+        return res
+
+    def gae_launches(self):
+        """(evaluate, rest): kernel launches of the last ppo_prepare / ppo_evaluate -- the pass over the rows, and bootstrap +
+        GAE + standardisation."""
+        e, r = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.pvae_ppo_gae_launches(self.ctx, C.byref(e), C.byref(r)), "pvae_ppo_gae_launches")
+        return e.value, r.value
+
 
 def gemm_probe(kind, a, b, c, bias_or_mask=None, relu=False, m=0, n=0, k=0):
     """Kernel-level entry (tests / roofline probes).  Tensors are dense fp32 on the GPU."""
@@ -1172,61 +1235,13 @@ class StackSetEngine:
 
     # -- train-batch preparation (include/pvae.h "Train-batch preparation") --------------------------
     def _rollout(self, ro, need):
-        """(pvae_fc_rollout, [tensors kept alive]) from a dict of device tensors: obs, actions, rewards, seg_start (int32
-        [S + 1]), seg_done (bool / uint8 [S]), boot_obs ([S, n_in]) and, optionally, the sampler's vf_preds / old_dist /
-        old_logp.  `need`: the names that must be there.  A `seg_start` given on the host is checked (its ends) and
-        uploaded; one on the device is taken under the caller's contract: it runs from 0 to the number of rows."""
-        k, f32 = self.n_outs[0], torch.float32
-        r, keep = _lib.FcRollout(), []
-        n = next((int(ro[c].shape[0]) for c in ("actions", "rewards", "obs") if ro.get(c) is not None), 1)
-        s = int(ro["seg_done"].shape[0])
-        shapes = {"obs": (n, self.n_in), "actions": (n, k), "rewards": (n,), "boot_obs": (s, self.n_in), "vf_preds": (n,),
-                  "old_dist": (n, 2 * k), "old_logp": (n,)}
-        for name in need:
-            if ro.get(name) is None:
-                raise KeyError("rollout lacks %s" % name)
-        for name, shape in shapes.items():
-            t = ro.get(name)
-            if t is None:
-                continue
-            t = t.reshape(t.shape[0], -1) if name in ("obs", "boot_obs") else t
-            t = t.to(self.device, f32).contiguous()
-            assert tuple(t.shape) == shape, "%s must be %s, got %s" % (name, shape, tuple(t.shape))
-            keep.append(t)
-            setattr(r, name, t.data_ptr())
-        done = ro["seg_done"]
-        done = done.to(self.device).contiguous()
-        assert done.dtype in (torch.bool, torch.uint8) and done.dim() == 1, "seg_done must be bool or uint8 [S]"
-        keep.append(done)
-        r.seg_done = done.data_ptr()
-        r.n_rows, r.n_segs, r.k = n, s, k
-        r.seg_first, r.seg_last = 0, n
-        if ro.get("seg_start") is not None:
-            seg, (r.seg_first, r.seg_last) = _seg_start(ro["seg_start"], s, n, self.device)
-            keep.append(seg)
-            r.seg_start = seg.data_ptr()
-        return r, keep
+        return make_rollout(ro, need, self.device, self.n_in, self.n_outs[0])
 
     def _prepared(self, n, s, names, out):
-        k = self.n_outs[0]
-        shapes = {"vf_preds": (n,), "old_dist": (n, 2 * k), "old_logp": (n,), "last_value": (s,), "advantages": (n,),
-                  "value_targets": (n,)}
-        o, res = _lib.FcPrepared(), {}
-        for name in names:
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shapes[name], dtype=torch.float32, device=self.device)
-            assert t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) == shapes[name], \
-                "out[%r] must be contiguous float32 %s on %s" % (name, shapes[name], self.device)
-            res[name] = t
-            setattr(o, name, t.data_ptr())
-        return o, res
+        return make_prepared(n, s, names, out, self.device, self.n_outs[0])
 
     def _gae_scratch(self, n_segs):
-        need = int(self.lib.pvae_fc_gae_workspace_bytes(int(n_segs)))
-        if getattr(self, "gae_scratch", None) is None or self.gae_scratch.numel() * 8 < need:
-            self.gae_scratch = torch.zeros(need // 8 + 2, dtype=torch.float64, device=self.device)
-        return self.gae_scratch, need
+        return gae_scratch_for(self, n_segs)
 
     def ppo_evaluate(self, rollout, params, out=None):
         """`pvae_fc_ppo_evaluate`: the current policy and value function over a device-resident rollout, in chunks of
@@ -1235,13 +1250,8 @@ class StackSetEngine:
         segment, whose boot_obs row is never read).  `params`: `PPOConfig.gae_params(kind, base)`; the log-std vector of a
         constant / state-independent kind is the one `ppo_bind` bound.  Returns the dict of what was computed."""
         self._need_gpu()
-        rows = rollout.get("obs") is not None
-        boot = rollout.get("boot_obs") is not None
-        ro = {c: rollout.get(c) for c in ("obs", "actions", "seg_done", "boot_obs")}
-        if not boot:
-            ro["seg_done"] = torch.zeros(1, dtype=torch.uint8, device=self.device)
-        r, keep = self._rollout(ro, (("obs", "actions") if rows else ()) + (("boot_obs",) if boot else ()))
-        names = (("vf_preds", "old_dist", "old_logp") if rows else ()) + (("last_value",) if boot else ())
+        ro, need, names = evaluate_plan(rollout, self.device)
+        r, keep = self._rollout(ro, need)
         o, res = self._prepared(int(r.n_rows), int(r.n_segs), names, out)
         _lib.check(self.lib.pvae_fc_ppo_evaluate(self.ctx, C.byref(r), C.byref(params), C.byref(o), self._stream()),
                    "pvae_fc_ppo_evaluate")
@@ -1254,15 +1264,12 @@ class StackSetEngine:
         sampler's columns, when given, come back as they are.  `out`: tensors to write into, by those names."""
         self._need_gpu()
         r, keep = self._rollout(rollout, ("obs", "actions", "rewards", "seg_start", "boot_obs"))
-        given = [rollout.get(name) is not None for name in ("vf_preds", "old_dist", "old_logp")]
-        if any(given) and not all(given):
-            raise ValueError("the sampler's vf_preds, old_dist and old_logp go together: all three or none")
-        names = (() if all(given) else ("vf_preds", "old_dist", "old_logp")) + ("last_value", "advantages", "value_targets")
+        names, given = prepare_plan(rollout)
         o, res = self._prepared(int(r.n_rows), int(r.n_segs), names, out)
         scratch, nbytes = self._gae_scratch(r.n_segs)
         _lib.check(self.lib.pvae_fc_ppo_prepare(self.ctx, C.byref(r), C.byref(params), C.byref(o), scratch.data_ptr(), nbytes,
                                                 self._stream()), "pvae_fc_ppo_prepare")
-        if all(given):
+        if given:
             res.update({name: rollout[name] for name in ("vf_preds", "old_dist", "old_logp")})
         return res
 
@@ -1278,6 +1285,90 @@ class StackSetEngine:
         f, b = C.c_int32(), C.c_int32()
         _lib.check(self.lib.pvae_fc_launches(self.ctx, C.byref(f), C.byref(b)), "pvae_fc_launches")
         return f.value, b.value
+
+
+def make_rollout(ro, need, device, n_in, k):
+    """(pvae_fc_rollout, [tensors kept alive]) from a dict of device tensors: obs, actions, rewards, seg_start (int32
+    [S + 1]), seg_done (bool / uint8 [S]), boot_obs ([S, n_in]) and, optionally, the sampler's vf_preds / old_dist /
+    old_logp.  `need`: the names that must be there.  A `seg_start` given on the host is checked (its ends) and
+    uploaded; one on the device is taken under the caller's contract: it runs from 0 to the number of rows.  Shared by
+    the stack set's and PhysicsVAE's train-batch preparation (`n_in` inputs per observation, `k` actions per row)."""
+    f32 = torch.float32
+    r, keep = _lib.FcRollout(), []
+    n = next((int(ro[c].shape[0]) for c in ("actions", "rewards", "obs") if ro.get(c) is not None), 1)
+    s = int(ro["seg_done"].shape[0])
+    shapes = {"obs": (n, n_in), "actions": (n, k), "rewards": (n,), "boot_obs": (s, n_in), "vf_preds": (n,),
+              "old_dist": (n, 2 * k), "old_logp": (n,)}
+    for name in need:
+        if ro.get(name) is None:
+            raise KeyError("rollout lacks %s" % name)
+    for name, shape in shapes.items():
+        t = ro.get(name)
+        if t is None:
+            continue
+        t = t.reshape(t.shape[0], -1) if name in ("obs", "boot_obs") else t
+        t = t.to(device, f32).contiguous()
+        assert tuple(t.shape) == shape, "%s must be %s, got %s" % (name, shape, tuple(t.shape))
+        keep.append(t)
+        setattr(r, name, t.data_ptr())
+    done = ro["seg_done"]
+    done = done.to(device).contiguous()
+    assert done.dtype in (torch.bool, torch.uint8) and done.dim() == 1, "seg_done must be bool or uint8 [S]"
+    keep.append(done)
+    r.seg_done = done.data_ptr()
+    r.n_rows, r.n_segs, r.k = n, s, k
+    r.seg_first, r.seg_last = 0, n
+    if ro.get("seg_start") is not None:
+        seg, (r.seg_first, r.seg_last) = _seg_start(ro["seg_start"], s, n, device)
+        keep.append(seg)
+        r.seg_start = seg.data_ptr()
+    return r, keep
+
+
+def make_prepared(n, s, names, out, device, k):
+    """(pvae_fc_prepared, {name: tensor}) for the columns `names` of n rows and s segments: taken from `out` where it has
+    them, allocated otherwise."""
+    shapes = {"vf_preds": (n,), "old_dist": (n, 2 * k), "old_logp": (n,), "last_value": (s,), "advantages": (n,),
+              "value_targets": (n,)}
+    o, res = _lib.FcPrepared(), {}
+    for name in names:
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(shapes[name], dtype=torch.float32, device=device)
+        assert t.dtype == torch.float32 and t.device == device and t.is_contiguous() and tuple(t.shape) == shapes[name], \
+            "out[%r] must be contiguous float32 %s on %s" % (name, shapes[name], device)
+        res[name] = t
+        setattr(o, name, t.data_ptr())
+    return o, res
+
+
+def gae_scratch_for(engine, n_segs):
+    """(the engine's GAE scratch, grown when n_segs asks for more; the bytes `pvae_fc_gae_workspace_bytes` wants)"""
+    need = int(engine.lib.pvae_fc_gae_workspace_bytes(int(n_segs)))
+    if getattr(engine, "gae_scratch", None) is None or engine.gae_scratch.numel() * 8 < need:
+        engine.gae_scratch = torch.zeros(need // 8 + 2, dtype=torch.float64, device=engine.device)
+    return engine.gae_scratch, need
+
+
+def evaluate_plan(rollout, device):
+    """What an evaluate call computes from what the rollout holds: (rollout dict, needed names, output names)."""
+    rows = rollout.get("obs") is not None
+    boot = rollout.get("boot_obs") is not None
+    ro = {c: rollout.get(c) for c in ("obs", "actions", "seg_done", "boot_obs")}
+    if not boot:
+        ro["seg_done"] = torch.zeros(1, dtype=torch.uint8, device=device)
+    need = (("obs", "actions") if rows else ()) + (("boot_obs",) if boot else ())
+    names = (("vf_preds", "old_dist", "old_logp") if rows else ()) + (("last_value",) if boot else ())
+    return ro, need, names
+
+
+def prepare_plan(rollout):
+    """The output names of a prepare call, and whether the sampler's own columns are given (all three or none)."""
+    given = [rollout.get(name) is not None for name in ("vf_preds", "old_dist", "old_logp")]
+    if any(given) and not all(given):
+        raise ValueError("the sampler's vf_preds, old_dist and old_logp go together: all three or none")
+    names = (() if all(given) else ("vf_preds", "old_dist", "old_logp")) + ("last_value", "advantages", "value_targets")
+    return names, all(given)
 
 
 def set_fc_per_stack(on):

@@ -807,6 +807,49 @@ class PhysicsVAE(nn.Module):
             self.__dict__.pop("_vb_layers", None)
         return ve
 
+    def ppo_prepare(self, rollout, config, eps=None):
+        """The first half of a learner iteration, on the device (`pvae_ppo_prepare`): from a device-resident rollout to the
+        train batch `ppo_learn` takes.  `rollout`: device tensors under `ppo.ROLLOUT_KEYS` -- obs [N, 2 Db], actions [N, Da],
+        rewards [N], seg_start (int32 [S + 1], from 0 to N), seg_done (bool / uint8 [S]) and next_obs_last [S, 2 Db], see
+        `ppo.segment_table` -- and optionally the sampler's own columns (`ppo.SAMPLER_KEYS`: used as given when all three
+        are there, and then nothing is drawn; otherwise the current policy is evaluated over the rows in chunks of
+        `max_batch`).  Then the bootstrap value of every segment that did not end its episode, GAE with `config.gamma` /
+        `config.lambda_`, the value targets, and (`config.standardize`) the advantages standardised over the batch.  `eps`:
+        [N, Z] latent draws, row by row (None: Philox from the module's seed, one offset of the `_rng_calls` counter per
+        chunk; `latent_prior_noise` False: z = mu).  Whenever the rows are evaluated `_rng_calls` advances by the number of
+        chunks -- also when `eps` is supplied or the noise is off and no Philox draw is made, as `ppo_learn` takes one offset
+        per step either way: a learner that replays `latent_eps` sees its seed stream moved by as much as one that drew
+        them; with the sampler's columns given it does not move.  Returns a dict under RLlib's sample-batch keys that `ppo_learn` accepts
+        unchanged, plus `last_value` [S] and `latent_eps` [N, Z], the draws used (None when the sampler's columns were
+        given); nothing synchronises.  Frozen nets make no difference here, and a state_independent log-std is read, not
+        trained.  The first call re-homes the value branch into a stack set (`_ppo_value_engine`)."""
+        from . import ppo as P
+        eng = self.engine
+        self._ppo_refusals()
+        eng._need_gpu()
+        missing = [k for k in P.ROLLOUT_KEYS if rollout.get(k) is None]
+        if missing:
+            raise KeyError("rollout lacks %s" % ", ".join(missing))
+        als = self.__dict__["_als"]
+        train_ls = als.type == "state_independent" and als.log_std.requires_grad
+        eng.ppo_bind(self._ppo_value_engine(), als.on_device(eng.device), train_ls)
+        ro = {k: rollout[k] for k in ("obs", "actions", "rewards", "seg_start", "seg_done")}
+        ro["boot_obs"] = rollout["next_obs_last"]
+        given = [rollout.get(k) is not None for k in P.SAMPLER_KEYS]
+        if any(given):
+            ro.update(vf_preds=rollout.get("vf_preds"), old_dist=rollout.get("action_dist_inputs"),
+                      old_logp=rollout.get("action_logp"))
+        st = self._st
+        res = eng.ppo_prepare(ro, config.gae_params("state_independent" if als.type == "state_independent" else "constant"),
+                              eps=eps, noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
+        if not all(given):
+            n = int(rollout["actions"].shape[0])
+            st._rng_calls += (n + eng.max_batch - 1) // eng.max_batch
+        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
+        return {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
+                "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
+                "value_targets": res["value_targets"], "last_value": res["last_value"], "latent_eps": res["latent_eps"]}
+
     def ppo_learn(self, batch, config, perm=None, eps=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step the

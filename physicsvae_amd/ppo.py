@@ -25,8 +25,9 @@ in time order (what RLlib postprocesses as one trajectory), rows seg_start[s] ..
     value_targets[t] = adv[t] + vf_preds[t]
     advantages       = (adv - mean(adv)) / max(1e-4, std(adv))   over the whole train batch, population std
 
-On the device: `FullyConnectedPolicy.ppo_prepare` (`pvae_fc_ppo_prepare`); `segment_table` builds the segment table on
-the host from RLlib's eps_id / dones / new_obs columns.
+On the device: `FullyConnectedPolicy.ppo_prepare` (`pvae_fc_ppo_prepare`) and `PhysicsVAE.ppo_prepare` (`pvae_ppo_prepare`,
+whose evaluate pass also names the latent draws); `segment_table` builds the segment table on the host from RLlib's
+eps_id / dones / new_obs columns.
 """
 import math
 
@@ -148,7 +149,8 @@ def segment_table(eps_id, dones, new_obs, unroll_id=None):
     return seg_start, dones[last].astype(np.uint8), np.ascontiguousarray(new_obs[last].reshape(len(last), -1), dtype=np.float32)
 
 
-# what `FullyConnectedPolicy.ppo_prepare` reads from a rollout, and the sampler's own columns it takes as given
+# what `FullyConnectedPolicy.ppo_prepare` and `PhysicsVAE.ppo_prepare` read from a rollout, and the sampler's own columns
+# they take as given
 ROLLOUT_KEYS = ("obs", "actions", "rewards", "seg_start", "seg_done", "next_obs_last")
 SAMPLER_KEYS = ("vf_preds", "action_dist_inputs", "action_logp")
 
