@@ -11,10 +11,11 @@
 // gradient bodies, the bias sums), on (pointer, ld) operands into the arena of pvae_fc_layout.h; a group launch only
 // decides which body a workgroup runs and on which operands.  A problem's tile geometry depends on the problem alone,
 // never on what shares its launch, so the per-stack schedule (option "fc_per_stack") gives the same bits.
+// Below the stack set itself: its PPO learner step and train-batch preparation (pvae_fc_ppo_*), which run the forward
+// and backward launches above with the loss head, Adam, epilogue and GAE launches of pvae_ppo_core.hip between them, and
+// the value stack alone as PhysicsVAE's learner (pvae_ppo.hip) runs it.
 #include "pvae_internal.h"
 #include "pvae_fc_layout.h"
-
-#include <mutex>
 
 struct pvae_fc {
     FcLayout L;
@@ -39,26 +40,8 @@ namespace {
 constexpr int kS = PVAE_FC_MAX_STACKS;
 
 // ---------------------------------------------------------------------------------------
-// glue kernels
+// glue kernels (the padded copy-in is pad_copy_launch, pvae_ppo_core.hip)
 // ---------------------------------------------------------------------------------------
-// batch row of minibatch row r: index[r] clamped into [0, n_rows) (a bad entry must not read out of bounds), or row0 + r
-__device__ inline long long batch_row(const int32_t* __restrict__ index, long long row0, long long n_rows, int r) {
-    if (!index) return row0 + r;
-    const long long i = index[r];
-    return i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
-}
-
-// dst[rows_pad][ld] = zero-padded copy of dense src[rows][n]; with `index` (the PPO step) of the rows src[index[r]]
-__global__ void __launch_bounds__(256)
-fc_pad_copy_kernel(const float* __restrict__ src, int n, int rows, float* __restrict__ dst, int ld, int rows_pad,
-                   const int32_t* __restrict__ index, long long n_rows) {
-    const int total = rows_pad * ld;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-        const int r = idx / ld, c = idx - r * ld;
-        dst[idx] = (r < rows && c < n) ? src[(size_t)batch_row(index, 0, n_rows, r) * n + c] : 0.f;
-    }
-}
-
 // dst[rows][n] (dense) = src[rows][0:n] of a panel with row stride ld
 __global__ void __launch_bounds__(256)
 fc_copy_out_kernel(const float* __restrict__ src, int ld, float* __restrict__ dst, int n, int rows) {
@@ -89,27 +72,6 @@ fc_seed_kernel(FcSeed a) {
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
         const int r = idx / width, c = idx - r * width;
         dz[(size_t)r * ld + c] = (dy && r < a.rows && c < n) ? dy[(size_t)r * n + c] : 0.f;
-    }
-}
-
-// Rows [r0, r1) of the layer-output panels set to zero: a <= 4-row forward runs on the GEMV kernels, which write the live
-// rows only, while the backward contractions read whole 32-row tiles (a stale NaN in a pad row would meet a zero gradient
-// row and the product is NaN).  blockIdx.y = panel.
-constexpr int kZeroPanels = 1 + kS * PVAE_MAX_HIDDEN;
-struct FcZeroRows {
-    float* p[kZeroPanels];
-    int ld[kZeroPanels], width[kZeroPanels];
-    int r0, r1;
-};
-__global__ void __launch_bounds__(256)
-fc_zero_rows_kernel(FcZeroRows z) {
-    const int k = blockIdx.y;
-    float* __restrict__ p = z.p[k];
-    const int ld = z.ld[k], width = z.width[k];
-    const int total = (z.r1 - z.r0) * width;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-        const int r = idx / width, c = idx - r * width;
-        p[(size_t)(z.r0 + r) * ld + c] = 0.f;
     }
 }
 
@@ -256,352 +218,6 @@ fc_backward_group_kernel(FcBwdGroup<EpiW> g) {
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// PPO learner step: the loss head and the Adam + stats launch (include/pvae.h "PPO learner step")
-// ---------------------------------------------------------------------------------------
-// A wave works on one row at a time, lanes over the k actions, butterfly reductions (every lane ends with the same sum, in
-// an order that depends on nothing but k).  The launch has one wave for every two padded rows (head_waves): wave w takes
-// rows w, w + waves, ... one after the other: its sums of the five per-row terms and,
-// for a state-independent log-std, of the log-std gradient columns go to partial row w of the scratch buffer -- no
-// atomics, so the finishing reduction (ppo_finish) adds them in a fixed order.
-constexpr int kHeadMaxBlocks = 1024;
-constexpr int kPartStats = 8;             // floats reserved for the stats at the head of a partial row
-struct PpoHead {
-    const float* mean; const float* ls; const float* value;       // row r at r * ld_*: panels or dense tensors
-    long long ld_mean, ld_ls, ld_value;
-    float ls_base;
-    const float* actions; const float* old_dist; const float* old_logp;
-    const float* adv; const float* vtarg; const float* vpred;
-    const int32_t* index; long long row0, n_rows;
-    int rows, rows_pad, k;
-    float clip, vf_clip, vf_coeff, kl_coeff, ent_coeff, inv_rows;
-    float* d_mean; float* d_ls; float* d_value;                  // [rows_pad][width_*] blocks, row stride ld_d* (null: none)
-    int ld_dm, ld_dls, ld_dv, width_dm, width_dls, width_dv;
-    float* part; int part_stride; int colsum;                    // partial rows [waves][part_stride]; colsum: + the log-std columns
-};
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__global__ void __launch_bounds__(256)
-fc_ppo_head_kernel(PpoHead h) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
-    const int k = h.k;
-    float* __restrict__ part = h.part + (size_t)wave * h.part_stride;
-    if (h.colsum)
-        for (int j = lane; j < k; j += 64) part[kPartStats + j] = 0.f;
-    float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r = wave; r < h.rows_pad; r += waves) {
-        const bool live = r < h.rows;
-        float dlogp = 0.f, dval = 0.f;
-        const float* mu = nullptr; const float* ls = nullptr; const float* act = nullptr; const float* od = nullptr;
-        if (live) {
-            const long long br = batch_row(h.index, h.row0, h.n_rows, r);
-            mu = h.mean + r * h.ld_mean; ls = h.ls + r * h.ld_ls;
-            act = h.actions + br * k; od = h.old_dist + br * 2 * k;
-            float zz = 0.f, lss = 0.f, kl = 0.f;
-            for (int j = lane; j < k; j += 64) {
-                const float l = h.ls_base + ls[j], inv_sig = expf(-l);
-                const float z = (act[j] - mu[j]) * inv_sig, d = od[j] - mu[j], lo = od[k + j];
-                zz = fmaf(z, z, zz);
-                lss += l;
-                kl += l - lo + (expf(2.f * lo) + d * d) * (0.5f * inv_sig * inv_sig) - 0.5f;
-            }
-            zz = wave_sum(zz); lss = wave_sum(lss); kl = wave_sum(kl);
-            const float logp = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;          // log(2 pi)
-            const float adv = h.adv[br], ratio = expf(logp - h.old_logp[br]);
-            const float lo_r = 1.f - h.clip, hi_r = 1.f + h.clip;
-            const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, lo_r), hi_r);
-            const float surr = fminf(s1, s2);
-            if (s1 < s2 || (ratio >= lo_r && ratio <= hi_r)) dlogp = -h.inv_rows * s1;
-            const float ent = lss + 0.5f * k * 2.8378770664093453f;                       // log(2 pi e)
-            const float val = h.value[r * h.ld_value], vt = h.vtarg[br], vp = h.vpred[br];
-            const float dv = val - vp, e1 = val - vt;
-            const float e2 = vp + fminf(fmaxf(dv, -h.vf_clip), h.vf_clip) - vt;
-            const float vf1 = e1 * e1, vf2 = e2 * e2, vf = fmaxf(vf1, vf2);
-            if (vf1 >= vf2 || fabsf(dv) <= h.vf_clip) dval = h.vf_coeff * h.inv_rows * 2.f * e1;
-            st[0] += -surr + h.kl_coeff * kl + h.vf_coeff * vf - h.ent_coeff * ent;
-            st[1] += -surr; st[2] += vf; st[3] += kl; st[4] += ent;
-        }
-        // the gradients, over the whole padded width of the row: zeros in pad rows and pad columns
-        const int wmax = max(h.d_mean ? h.width_dm : k, h.d_ls ? h.width_dls : k);
-        const float klc = h.kl_coeff * h.inv_rows, entc = h.ent_coeff * h.inv_rows;
-        for (int j = lane; j < wmax; j += 64) {
-            float gm = 0.f, gl = 0.f;
-            if (live && j < k) {
-                const float l = h.ls_base + ls[j], inv_sig = expf(-l), inv_var = inv_sig * inv_sig;
-                const float am = act[j] - mu[j], z = am * inv_sig, d = od[j] - mu[j];
-                gm = dlogp * am * inv_var - klc * d * inv_var;
-                gl = dlogp * (z * z - 1.f) + klc * (1.f - (expf(2.f * od[k + j]) + d * d) * inv_var) - entc;
-                if (h.colsum) part[kPartStats + j] += gl;
-            }
-            if (h.d_mean && j < h.width_dm) h.d_mean[(size_t)r * h.ld_dm + j] = gm;
-            if (h.d_ls && j < h.width_dls) h.d_ls[(size_t)r * h.ld_dls + j] = gl;
-        }
-        if (h.d_value)
-            for (int j = lane; j < h.width_dv; j += 64) h.d_value[(size_t)r * h.ld_dv + j] = j == 0 ? dval : 0.f;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int t = 0; t < 5; ++t) part[t] = st[t];
-    }
-}
-
-// The partial rows summed in a fixed order by ONE wave: stats_out[5] (means over the rows)
-__device__ inline void ppo_finish(const float* __restrict__ part, int nparts, int stride, float inv_rows, float* __restrict__ out,
-                                  int lane) {
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        float s = 0.f;
-        for (int i = lane; i < nparts; i += 64) s += part[(size_t)i * stride + t];
-        s = wave_sum(s) * inv_rows;
-        if (lane == 0) out[t] = s;
-    }
-}
-__global__ void __launch_bounds__(64)
-ppo_finish_kernel(const float* part, int nparts, int stride, float inv_rows, float* out) {
-    ppo_finish(part, nparts, stride, inv_rows, out, threadIdx.x);
-}
-
-// Adam over the trained segments of the arena (adam_update4 with the AdamScalars the trainer's adam_flat_kernel gets:
-// the same bits) + ONE extra workgroup, the last: the stats and, for a state-independent log-std, that vector's gradient
-// (the column sums, added in partial-row order) and its Adam update.
-constexpr int kAdamSegs = 3 * kS;
-struct FcAdam {
-    float* p; const float* g; float* m; float* v;
-    int nseg;
-    long long off4[kAdamSegs], end4[kAdamSegs];     // float4 offset of segment i; running float4 count through segment i
-    AdamScalars s;
-    const float* part; int nparts, part_stride; float inv_rows; float* stats_out;
-    int k; float* ls; float* ls_m; float* ls_v;     // ls null: no trained log-std vector
-};
-__global__ void __launch_bounds__(256)
-fc_adam_kernel(FcAdam a) {
-    if (blockIdx.x == gridDim.x - 1) {
-        if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
-        if (a.ls)
-            for (int j = threadIdx.x; j < a.k; j += 256) {
-                double gs = 0.0;               // (a few hundred signed terms per column: in double, so that the order does not show)
-                for (int i = 0; i < a.nparts; ++i) gs += (double)a.part[(size_t)i * a.part_stride + kPartStats + j];
-                const float g = (float)gs;
-                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
-                adam_update(g, p, m, v, a.s);
-                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
-            }
-        return;
-    }
-    const long long n4 = a.nseg ? a.end4[a.nseg - 1] : 0;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
-        int k = 0;
-        while (i >= a.end4[k]) ++k;
-        const long long q = a.off4[k] + (i - (k ? a.end4[k - 1] : 0));
-        v4f pp = reinterpret_cast<v4f*>(a.p)[q];
-        const v4f gg = reinterpret_cast<const v4f*>(a.g)[q];
-        v4f mm = reinterpret_cast<v4f*>(a.m)[q];
-        v4f vv = reinterpret_cast<v4f*>(a.v)[q];
-        adam_update4(gg, pp, mm, vv, a.s);
-        reinterpret_cast<v4f*>(a.p)[q] = pp;
-        reinterpret_cast<v4f*>(a.m)[q] = mm;
-        reinterpret_cast<v4f*>(a.v)[q] = vv;
-    }
-}
-
-// fc_adam_kernel over segments of up to three DIFFERENT arenas (the PhysicsVAE step: the encoder's and the decoder's
-// segments of the five-net arena and the value stack set's arena, each with its own gradient and moment buffers): the
-// same adam_update4 per element, the same last workgroup for the stats and the log-std vector.
-struct PpoAdam {
-    PpoAdamSegs seg;
-    long long end4[3];                              // running float4 count through segment i
-    AdamScalars s;
-    const float* part; int nparts, part_stride; float inv_rows; float* stats_out;
-    int k; float* ls; float* ls_m; float* ls_v;
-};
-__global__ void __launch_bounds__(256)
-ppo_adam_kernel(PpoAdam a) {
-    if (blockIdx.x == gridDim.x - 1) {
-        if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
-        if (a.ls)
-            for (int j = threadIdx.x; j < a.k; j += 256) {
-                double gs = 0.0;
-                for (int i = 0; i < a.nparts; ++i) gs += (double)a.part[(size_t)i * a.part_stride + kPartStats + j];
-                const float g = (float)gs;
-                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
-                adam_update(g, p, m, v, a.s);
-                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
-            }
-        return;
-    }
-    const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
-        int k = 0;
-        while (i >= a.end4[k]) ++k;
-        const long long q = i - (k ? a.end4[k - 1] : 0);
-        v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
-        const v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
-        v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
-        v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
-        adam_update4(gg, pp, mm, vv, a.s);
-        reinterpret_cast<v4f*>(a.seg.p[k])[q] = pp;
-        reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
-        reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// train-batch preparation: evaluate epilogue, GAE, standardisation (include/pvae.h "Train-batch preparation")
-// ---------------------------------------------------------------------------------------
-// input panel of the bootstrap pass: fc_pad_copy_kernel, except that row r of a segment that ended its episode (done[r])
-// is zeros and its source row is never read
-__global__ void __launch_bounds__(256)
-fc_boot_copy_kernel(const float* __restrict__ src, int n, int rows, float* __restrict__ dst, int ld, int rows_pad,
-                    const uint8_t* __restrict__ done) {
-    const int total = rows_pad * ld;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-        const int r = idx / ld, c = idx - r * ld;
-        dst[idx] = (r < rows && c < n && !done[r]) ? src[(size_t)r * n + c] : 0.f;
-    }
-}
-
-// The epilogue of one evaluated chunk: a wave per row reads the stacks' outputs in their panels and writes vf[r],
-// dist[r] = [mean | log_std] and logp[r] of actions[r] -- the arithmetic of fc_ppo_head_kernel's logp, term for term, so
-// that the learner's first step sees a ratio of exactly 1.  mean == NULL: the bootstrap use -- the value stack ran alone;
-// vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.  eps_dst (PhysicsVAE's evaluate
-// pass): the latent draws of the chunk, eps_src [rows][Z], copied to the caller's rows.
-constexpr int kEvalMaxBlocks = 1024;
-struct FcEval {
-    const float* mean; const float* ls; const float* value;
-    long long ld_mean, ld_ls, ld_value;
-    float ls_base;
-    const float* actions;
-    const uint8_t* done;
-    int rows, k;
-    float* vf; float* dist; float* logp;
-    const float* eps_src; float* eps_dst; int Z;
-};
-__global__ void __launch_bounds__(256)
-fc_eval_epilogue_kernel(FcEval e) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
-    const int k = e.k;
-    for (int r = wave; r < e.rows; r += waves) {
-        if (!e.mean) {
-            if (lane == 0) e.vf[r] = e.done[r] ? 0.f : e.value[r * e.ld_value];
-            continue;
-        }
-        const float* mu = e.mean + r * e.ld_mean;
-        const float* ls = e.ls + r * e.ld_ls;
-        const float* act = e.actions + (size_t)r * k;
-        float* dist = e.dist + (size_t)r * 2 * k;
-        float zz = 0.f, lss = 0.f;
-        for (int j = lane; j < k; j += 64) {
-            const float l = e.ls_base + ls[j], inv_sig = expf(-l);
-            const float z = (act[j] - mu[j]) * inv_sig;
-            zz = fmaf(z, z, zz);
-            lss += l;
-            dist[j] = mu[j];
-            dist[k + j] = l;
-        }
-        zz = wave_sum(zz); lss = wave_sum(lss);
-        if (lane == 0) {
-            e.logp[r] = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                  // log(2 pi)
-            e.vf[r] = e.value[r * e.ld_value];
-        }
-        if (e.eps_dst)
-            for (int j = lane; j < e.Z; j += 64) e.eps_dst[(size_t)r * e.Z + j] = e.eps_src[(size_t)r * e.Z + j];
-    }
-}
-
-// GAE: adv[t] = delta[t] + gamma lambda adv[t + 1] inside a segment, a reverse linear recurrence.  One wavefront per
-// segment (wave w takes segments w, w + waves, ...) walks it from its end in 64-row pieces: lane l holds the row l places
-// before the piece's last one, the piece is an inclusive wave scan of the pairs (c, delta) under
-// (a2, b2) o (a1, b1) = (a1 a2, b2 + a2 b1), and the advantage of the row after the piece is the carry into it.  Segment
-// bounds are clamped into [0, n_rows]: a bad table cannot make the kernel touch memory outside the columns.  Every
-// workgroup leaves the sums of adv and adv^2 over its waves' rows, in double, in part[block][2]: no atomics, the
-// standardisation adds them in block order.
-constexpr int kGaeMaxBlocks = 1024;
-struct GaeArgs {
-    const float* rewards; const float* vpred; const float* last_value;
-    const uint8_t* done;                  // null: last_value as given
-    const int32_t* seg_start;
-    long long n_rows;
-    int n_segs;
-    float gamma, c;                       // c = gamma lambda
-    float* adv; float* vtarg;
-    double* part;
-};
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__global__ void __launch_bounds__(256)
-fc_gae_kernel(GaeArgs g) {
-    __shared__ double red[4][2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int wave = blockIdx.x * 4 + wv, waves = gridDim.x * 4;
-    double s1 = 0.0, s2 = 0.0;
-    for (int s = wave; s < g.n_segs; s += waves) {
-        long long a = g.seg_start[s], b = g.seg_start[s + 1];
-        a = a < 0 ? 0 : (a > g.n_rows ? g.n_rows : a);
-        b = b < a ? a : (b > g.n_rows ? g.n_rows : b);
-        if (b <= a) continue;             // (the same for every lane of the wave)
-        const float last = (g.done && g.done[s]) ? 0.f : g.last_value[s];
-        float carry = 0.f;
-        for (long long hi = b; hi > a; hi -= 64) {
-            const long long t = hi - 1 - lane;
-            const bool live = t >= a;
-            float pa = 1.f, pb = 0.f, v = 0.f;
-            if (live) {
-                v = g.vpred[t];
-                const float vn = t + 1 < b ? g.vpred[t + 1] : last;
-                pb = g.rewards[t] + g.gamma * vn - v;
-                pa = g.c;
-            }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float qa = __shfl_up(pa, o, 64), qb = __shfl_up(pb, o, 64);
-                if (lane >= o) { pb = fmaf(pa, qb, pb); pa *= qa; }
-            }
-            const float x = fmaf(pa, carry, pb);
-            carry = __shfl(x, 63, 64);
-            if (live) {
-                g.adv[t] = x;
-                g.vtarg[t] = x + v;
-                s1 += (double)x;
-                s2 += (double)x * (double)x;
-            }
-        }
-    }
-    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-    if (lane == 0) { red[wv][0] = s1; red[wv][1] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        g.part[(size_t)blockIdx.x * 2 + threadIdx.x] =
-            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
-// advantages = (adv - mean) / max(1e-4, std), population std: every workgroup adds the GAE launch's partial sums in the
-// same order (thread i the partials i, i + 256, ..., then a tree over the threads) and rescales its slice in place
-__global__ void __launch_bounds__(256)
-fc_standardize_kernel(float* __restrict__ adv, long long n, const double* __restrict__ part, int nparts) {
-    __shared__ double sh[2][256];
-    const int tid = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int i = tid; i < nparts; i += 256) { a += part[2 * (size_t)i]; b += part[2 * (size_t)i + 1]; }
-    sh[0][tid] = a; sh[1][tid] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { sh[0][tid] += sh[0][tid + o]; sh[1][tid] += sh[1][tid + o]; }
-        __syncthreads();
-    }
-    const double mean = sh[0][0] / (double)n;
-    double var = sh[1][0] / (double)n - mean * mean;
-    if (!(var > 0.0)) var = 0.0;
-    const double sd = sqrt(var), inv = 1.0 / (sd > 1e-4 ? sd : 1e-4);
-    for (long long i = blockIdx.x * 256ll + tid; i < n; i += gridDim.x * 256ll) adv[i] = (float)(((double)adv[i] - mean) * inv);
-}
 
 // ---------------------------------------------------------------------------------------
 // host side
@@ -674,13 +290,10 @@ int launch_gemv(Run& r, const std::vector<FcGemvProb>& probs, const std::vector<
     return 0;
 }
 
-int copy_in(Run& r, const float* x, const int32_t* index = nullptr, long long n_rows = 0) {
+int copy_in(Run& r, const float* x, const int32_t* index = nullptr, long long n_rows = 0, const uint8_t* done = nullptr) {
     const pvae_fc* c = r.c;
-    int grid = (r.rows_pad * c->L.ld0 + 255) / 256;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(fc_pad_copy_kernel, dim3(grid), dim3(256), 0, r.st, x, c->L.cfg.n_in, r.rows, c->ws + c->W.in,
-                       c->L.ld0, r.rows_pad, index, n_rows);
-    HIP_TRY(hipGetLastError());
+    const int rc = pad_copy_launch(x, c->L.cfg.n_in, r.rows, c->ws + c->W.in, c->L.ld0, r.rows_pad, index, n_rows, done, r.st);
+    if (rc) return rc;
     ++r.launches;
     return 0;
 }
@@ -849,26 +462,17 @@ int run_backward_layers(Run& r, bool want_dx, float* grad, int grad_mask) {
 int zero_pad_rows(Run& r) {
     pvae_fc* c = r.c;
     const FcLayout& L = c->L;
-    const int rows = r.rows;
-    if (!(rows <= 4 && rows < r.rows_pad)) return 0;
-    {
-        FcZeroRows z;
-        memset(&z, 0, sizeof(z));
-        int n = 0, wmax = L.n0;
-        z.p[n] = c->ws + c->W.act0; z.ld[n] = L.n0; z.width[n] = L.n0; ++n;
-        for (int s = 0; s < L.S; ++s)
-            for (int i = 1; r.want[s] && i < (int)L.stack[s].size(); ++i) {
-                z.p[n] = act_ptr(c, s, i); z.ld[n] = z.width[n] = L.stack[s][i].n_out_pad;
-                if (z.width[n] > wmax) wmax = z.width[n];
-                ++n;
-            }
-        z.r0 = rows; z.r1 = r.rows_pad;
-        int gx = ((z.r1 - z.r0) * wmax + 255) / 256;
-        if (gx > 64) gx = 64;
-        hipLaunchKernelGGL(fc_zero_rows_kernel, dim3(gx, n), dim3(256), 0, r.st, z);
-        HIP_TRY(hipGetLastError());
-        ++r.launches;
-    }
+    if (!(r.rows <= 4 && r.rows < r.rows_pad)) return 0;
+    ZeroRows z;
+    memset(&z, 0, sizeof(z));
+    z.add(c->ws + c->W.act0, L.n0, L.n0);
+    for (int s = 0; s < L.S; ++s)
+        for (int i = 1; r.want[s] && i < (int)L.stack[s].size(); ++i)
+            z.add(act_ptr(c, s, i), L.stack[s][i].n_out_pad, L.stack[s][i].n_out_pad);
+    z.r0 = r.rows; z.r1 = r.rows_pad;
+    const int rc = zero_rows_launch(z, r.st);
+    if (rc) return rc;
+    ++r.launches;
     return 0;
 }
 
@@ -886,68 +490,7 @@ void set_range(Run& r, int S) {
         if (r.want[s]) { if (r.s_lo < 0) r.s_lo = s; r.s_hi = s; }
 }
 
-
 // ---- PPO learner step, host side ----
-int head_waves(int rows_pad) {
-    int w = (rows_pad + 1) / 2;                       // two rows per wave
-    w = (w + 3) / 4 * 4;
-    return w > 4 * kHeadMaxBlocks ? 4 * kHeadMaxBlocks : w;
-}
-int part_stride(int k, bool colsum) { return kPartStats + (colsum ? (k + 3) / 4 * 4 : 0); }
-size_t ppo_scratch_floats(const FcLayout& L) {
-    return (size_t)head_waves(pad32(L.cfg.max_batch)) * part_stride(L.cfg.n_out[0], true);
-}
-
-int check_loss_args(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows) {
-    if (!b || !p) return fail(-1, "null batch or params");
-    if (!b->actions || !b->old_dist || !b->old_logp || !b->advantages || !b->value_targets || !b->vf_preds)
-        return fail(-1, "a batch column is null");
-    if (b->n_rows < 1 || b->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)b->n_rows);
-    if (b->k < 1) return fail(-1, "k must be positive");
-    if (rows < 1) return fail(-1, "rows must be positive");
-    if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
-    if (!(p->clip_param >= 0.f) || !(p->vf_clip_param >= 0.f)) return fail(-1, "clip_param and vf_clip_param must be >= 0");
-    return 0;
-}
-
-void fill_head(PpoHead& h, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0,
-               int rows, int rows_pad) {
-    memset(&h, 0, sizeof(h));
-    h.actions = b->actions; h.old_dist = b->old_dist; h.old_logp = b->old_logp;
-    h.adv = b->advantages; h.vtarg = b->value_targets; h.vpred = b->vf_preds;
-    h.index = index; h.row0 = row0; h.n_rows = b->n_rows;
-    h.rows = rows; h.rows_pad = rows_pad; h.k = b->k;
-    h.clip = p->clip_param; h.vf_clip = p->vf_clip_param; h.vf_coeff = p->vf_loss_coeff;
-    h.kl_coeff = p->kl_coeff; h.ent_coeff = p->entropy_coeff;
-    h.inv_rows = (float)(1.0 / rows);
-}
-
-AdamScalars ppo_adam_scalars(const pvae_fc_ppo_params* p, int t) {
-    pvae_step_params sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.lr = p->lr; sp.beta1 = p->beta1; sp.beta2 = p->beta2; sp.adam_eps = p->adam_eps; sp.weight_decay = p->weight_decay;
-    sp.adam_t[0] = t;
-    return adam_scalars(&sp, 0);
-}
-
-// scratch of pvae_ppo_loss (no context to hold one): one small buffer per (device, stream), made at the first call on that
-// stream and kept -- calls on one stream are ordered, so they can share it
-struct LossScratch { int dev; hipStream_t st; float* p; };
-std::vector<LossScratch> g_loss_scratch;
-std::mutex g_loss_scratch_mu;
-int loss_scratch(hipStream_t st, float** out) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_loss_scratch_mu);
-    for (const LossScratch& e : g_loss_scratch)
-        if (e.dev == dev && e.st == st) { *out = e.p; return 0; }
-    float* p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, (size_t)4 * kHeadMaxBlocks * kPartStats * sizeof(float)));
-    g_loss_scratch.push_back(LossScratch{dev, st, p});
-    *out = p;
-    return 0;
-}
-
 int check_ppo(pvae_fc* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows, const float* stats) {
     if (!c) return fail(-1, "null stack set");
     if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
@@ -987,7 +530,6 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
     if ((rc = zero_pad_rows(r))) return rc;
     if ((rc = run_forward(r, nullptr))) return rc;
     const bool colsum = p->log_std_kind == 1;
-    const int waves = head_waves(r.rows_pad), stride = part_stride(b->k, colsum);
     {
         PpoHead h;
         fill_head(h, b, p, index ? index + first : nullptr, first, rows, r.rows_pad);
@@ -1003,17 +545,13 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
         }
         if (mask & 1) { h.d_mean = dz_ptr(c, 0, lp); h.ld_dm = panel_ld(c, 0, lp); h.width_dm = L.stack[0][lp].n_out_pad; }
         if (mask & 2) { h.d_value = dz_ptr(c, 1, lv); h.ld_dv = panel_ld(c, 1, lv); h.width_dv = L.stack[1][lv].n_out_pad; }
-        h.part = c->scratch; h.part_stride = stride; h.colsum = colsum;
-        hipLaunchKernelGGL(fc_ppo_head_kernel, dim3(waves / 4), dim3(256), 0, st, h);
-        HIP_TRY(hipGetLastError());
+        h.part = c->scratch; h.part_stride = part_stride(b->k, colsum); h.colsum = colsum;
+        if ((rc = ppo_head_launch(h, st))) return rc;
         ++r.launches;
     }
     for (int s = 0; s < L.S; ++s) r.want[s] = (mask >> s) & 1;
     if ((rc = run_backward_layers<EpiGradStore>(r, false, c->grad, mask))) return rc;
     {
-        FcAdam a;
-        memset((void*)&a, 0, sizeof(a));
-        a.p = c->params; a.g = c->grad; a.m = c->m; a.v = c->v;
         // the trained stacks' parts of the arena, in arena order, adjacent ones merged
         std::vector<std::pair<long long, long long>> seg;
         auto add = [&](long long off, long long n) {
@@ -1029,21 +567,15 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
                 add(L.stack[s][i].w_off, (long long)L.stack[s][i].n_out_pad * L.stack[s][i].ld);
                 add(L.stack[s][i].b_off, L.stack[s][i].n_out_pad);
             }
-        long long total4 = 0;
-        for (const auto& sg : seg) {
-            if (a.nseg == kAdamSegs) return fail(-3, "the trained parts of the arena form more than %d segments", kAdamSegs);
-            a.off4[a.nseg] = sg.first / 4;
-            total4 += sg.second / 4;
-            a.end4[a.nseg++] = total4;
+        PpoAdamSegs sg;
+        memset((void*)&sg, 0, sizeof(sg));
+        for (const auto& e : seg) {
+            if (sg.n == kAdamSegs) return fail(-3, "the trained parts of the arena form more than %d segments", kAdamSegs);
+            sg.p[sg.n] = c->params + e.first; sg.g[sg.n] = c->grad + e.first; sg.m[sg.n] = c->m + e.first; sg.v[sg.n] = c->v + e.first;
+            sg.n4[sg.n++] = e.second / 4;
         }
-        a.s = ppo_adam_scalars(p, adam_t);
-        a.part = c->scratch; a.nparts = waves; a.part_stride = stride; a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
-        a.k = b->k;
-        if (colsum) { a.ls = c->log_std; a.ls_m = c->log_std_m; a.ls_v = c->log_std_v; }
-        long long grid = (total4 + 255) / 256;
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(fc_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
+        if ((rc = ppo_adam_launch(sg, p, adam_t, rows, b->k, c->scratch, colsum, c->log_std, c->log_std_m, c->log_std_v, stats_out, st)))
+            return rc;
         ++r.launches;
     }
     c->ppo_launches = r.launches;
@@ -1051,58 +583,6 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
 }
 
 // ---- train-batch preparation, host side ----
-int gae_blocks(int n_segs) {
-    const int b = (n_segs + 3) / 4;
-    return b > kGaeMaxBlocks ? kGaeMaxBlocks : (b < 1 ? 1 : b);
-}
-size_t gae_scratch_bytes(int n_segs) { return (size_t)gae_blocks(n_segs) * 2 * sizeof(double); }
-
-int check_gae_params(const pvae_gae_params* p) {
-    if (!p) return fail(-1, "null params");
-    if (!(p->gamma >= 0.f && p->gamma <= 1.f) || !(p->lambda >= 0.f && p->lambda <= 1.f))
-        return fail(-1, "gamma and lambda must lie in [0, 1]");
-    return 0;
-}
-
-int check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last) {
-    if (n_rows < 1 || n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", n_rows);
-    if (n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", n_segs);
-    if (n_segs > n_rows) return fail(-1, "n_segs %d > n_rows %lld: a segment has at least one row", n_segs, n_rows);
-    if (seg_first != 0 || seg_last != n_rows)
-        return fail(-1, "seg_start must run from 0 to n_rows %lld, got %lld .. %lld", n_rows, seg_first, seg_last);
-    return 0;
-}
-
-int check_gae_scratch(const void* scratch, size_t bytes, int n_segs) {
-    if (!scratch) return fail(-1, "scratch is null");
-    if ((uintptr_t)scratch & 15) return fail(-1, "scratch must be 16-byte aligned");
-    if (bytes < gae_scratch_bytes(n_segs)) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, gae_scratch_bytes(n_segs));
-    return 0;
-}
-
-// the GAE launch and, with `standardize`, the rescale launch (arguments checked by the caller); `launches` counts them
-int run_gae(const float* rewards, const float* vpred, const float* last_value, const uint8_t* done, const int32_t* seg_start,
-            long long n_rows, int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st,
-            int& launches) {
-    GaeArgs g;
-    memset(&g, 0, sizeof(g));
-    g.rewards = rewards; g.vpred = vpred; g.last_value = last_value; g.done = done; g.seg_start = seg_start;
-    g.n_rows = n_rows; g.n_segs = n_segs; g.gamma = p->gamma; g.c = p->gamma * p->lambda;
-    g.adv = adv; g.vtarg = vtarg; g.part = (double*)scratch;
-    const int blocks = gae_blocks(n_segs);
-    hipLaunchKernelGGL(fc_gae_kernel, dim3(blocks), dim3(256), 0, st, g);
-    HIP_TRY(hipGetLastError());
-    ++launches;
-    if (p->standardize) {
-        long long grid = (n_rows + 255) / 256;
-        if (grid > 1024) grid = 1024;
-        hipLaunchKernelGGL(fc_standardize_kernel, dim3((int)grid), dim3(256), 0, st, adv, n_rows, (const double*)scratch, blocks);
-        HIP_TRY(hipGetLastError());
-        ++launches;
-    }
-    return 0;
-}
-
 // what evaluate and prepare ask of the stack set; `rows_pass`: the policy's distribution is evaluated (its log-std is needed)
 int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) {
     if (!c) return fail(-1, "null stack set");
@@ -1125,27 +605,6 @@ int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, 
     return 0;
 }
 
-int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) {
-    if (ro->n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", ro->n_segs);
-    if (!ro->boot_obs || !ro->seg_done) return fail(-1, "rollout boot_obs or seg_done is null");
-    if (!out->last_value) return fail(-1, "last_value is null");
-    return 0;
-}
-
-void fill_eval_value(FcEval& e, const pvae_fc* c) {
-    const int lv = (int)c->L.stack[1].size() - 1;
-    e.value = act_ptr(c, 1, lv); e.ld_value = panel_ld(c, 1, lv);
-}
-
-int launch_eval_epilogue(Run& r, const FcEval& e) {
-    int blocks = (e.rows + 3) / 4;
-    if (blocks > kEvalMaxBlocks) blocks = kEvalMaxBlocks;
-    hipLaunchKernelGGL(fc_eval_epilogue_kernel, dim3(blocks), dim3(256), 0, r.st, e);
-    HIP_TRY(hipGetLastError());
-    ++r.launches;
-    return 0;
-}
-
 // rows of the rollout through all stacks in chunks of max_batch: copy-in, one launch per depth, the epilogue
 int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, hipStream_t st,
               int& launches) {
@@ -1159,11 +618,11 @@ int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, c
         int rc;
         if ((rc = copy_in(r, ro->obs + (size_t)first * L.cfg.n_in))) return rc;
         if ((rc = run_forward(r, nullptr))) return rc;
-        FcEval e;
+        PpoEval e;
         memset(&e, 0, sizeof(e));
-        const int lp = (int)L.stack[0].size() - 1;
+        const int lp = (int)L.stack[0].size() - 1, lv = (int)L.stack[1].size() - 1;
         e.mean = act_ptr(c, 0, lp); e.ld_mean = panel_ld(c, 0, lp);
-        fill_eval_value(e, c);
+        e.value = act_ptr(c, 1, lv); e.ld_value = panel_ld(c, 1, lv);
         if (p->log_std_kind == 2) {
             const int ll = (int)L.stack[2].size() - 1;
             e.ls = act_ptr(c, 2, ll); e.ld_ls = panel_ld(c, 2, ll); e.ls_base = p->log_std_base;
@@ -1173,42 +632,24 @@ int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, c
         e.actions = ro->actions + (size_t)first * k;
         e.rows = rows; e.k = k;
         e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
-        if ((rc = launch_eval_epilogue(r, e))) return rc;
-        launches += r.launches;
+        if ((rc = ppo_eval_launch(e, st))) return rc;
+        launches += r.launches + 1;
     }
     return 0;
 }
 
-// last_value[s] = seg_done[s] ? 0 : value(boot_obs[s]): the value stack alone, in chunks of max_batch
-int eval_boot(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st, int& launches) {
-    const FcLayout& L = c->L;
-    for (int first = 0; first < ro->n_segs; first += L.cfg.max_batch) {
-        const int rows = ro->n_segs - first < L.cfg.max_batch ? ro->n_segs - first : L.cfg.max_batch;
-        Run r{c, st, rows, pad32(rows)};
-        r.want[1] = true;
-        set_range(r, L.S);
-        int rc;
-        if ((rc = ppo_boot_copy_launch(ro->boot_obs + (size_t)first * L.cfg.n_in, L.cfg.n_in, rows, c->ws + c->W.in, L.ld0,
-                                       r.rows_pad, ro->seg_done + first, st)))
-            return rc;
-        ++r.launches;
-        if ((rc = run_forward(r, nullptr))) return rc;
-        FcEval e;
-        memset(&e, 0, sizeof(e));
-        fill_eval_value(e, c);
-        e.done = ro->seg_done + first;
-        e.rows = rows; e.k = ro->k;
-        e.vf = out->last_value + first;
-        if ((rc = launch_eval_epilogue(r, e))) return rc;
-        launches += r.launches;
-    }
-    return 0;
+// one stack alone, as PhysicsVAE's learner and the bootstrap pass run the value function
+Run value_run(pvae_fc* c, int s, int rows, hipStream_t st) {
+    Run r{c, st, rows, pad32(rows)};
+    r.want[s] = true;
+    set_range(r, c->L.S);
+    return r;
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
-// what the PPO learner step of PhysicsVAE (pvae_ppo.hip) runs of this unit (pvae_internal.h)
+// the value stack alone: what PhysicsVAE's learner (pvae_ppo.hip) and the bootstrap pass run of this unit (pvae_internal.h)
 // ---------------------------------------------------------------------------------------
 int fc_value_stack(pvae_fc* c, FcValueStack* out) {
     if (!c) return fail(-1, "null value stack set");
@@ -1232,89 +673,38 @@ int fc_value_stack(pvae_fc* c, FcValueStack* out) {
     return 0;
 }
 
-int fc_value_forward(pvae_fc* c, int rows, hipStream_t st, int* launches) {
-    Run r{c, st, rows, pad32(rows)};
-    r.want[0] = true;
-    set_range(r, 1);
+int fc_value_forward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches) {
+    Run r = value_run(c, s, rows, st);
     const int rc = run_forward(r, nullptr);
     *launches += r.launches;
     return rc;
 }
 
-int fc_value_backward(pvae_fc* c, int rows, hipStream_t st, int* launches) {
-    Run r{c, st, rows, pad32(rows)};
-    r.want[0] = true;
-    set_range(r, 1);
-    const int rc = run_backward_layers<EpiGradStore>(r, false, c->grad, 1);
+int fc_value_backward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches) {
+    Run r = value_run(c, s, rows, st);
+    const int rc = run_backward_layers<EpiGradStore>(r, false, c->grad, 1 << s);
     *launches += r.launches;
     return rc;
 }
 
-int ppo_eval_launch(const PpoEvalIo& io, hipStream_t st) {
-    FcEval e;
-    memset(&e, 0, sizeof(e));
-    e.mean = io.mean; e.ld_mean = io.ld_mean; e.ls = io.ls; e.ld_ls = 0; e.value = io.value; e.ld_value = io.ld_value;
-    e.actions = io.actions; e.done = io.done; e.rows = io.rows; e.k = io.k;
-    e.vf = io.vf; e.dist = io.dist; e.logp = io.logp;
-    e.eps_src = io.eps_src; e.eps_dst = io.eps_dst; e.Z = io.Z;
-    Run r{nullptr, st, io.rows, pad32(io.rows)};
-    return launch_eval_epilogue(r, e);
-}
-
-int ppo_boot_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const uint8_t* done, hipStream_t st) {
-    int grid = (rows_pad * ld + 255) / 256;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(fc_boot_copy_kernel, dim3(grid), dim3(256), 0, st, src, n, rows, dst, ld, rows_pad, done);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int gae_check_params(const pvae_gae_params* p) { return check_gae_params(p); }
-int gae_check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) { return check_boot(ro, out); }
-int gae_check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last) {
-    return check_segments(n_rows, n_segs, seg_first, seg_last);
-}
-int gae_check_scratch(const void* scratch, size_t bytes, int n_segs) { return check_gae_scratch(scratch, bytes, n_segs); }
-
-int gae_launch(const float* rewards, const float* vpred, const float* last_value, const int32_t* seg_start, long long n_rows,
-               int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st, int* launches) {
-    return run_gae(rewards, vpred, last_value, nullptr, seg_start, n_rows, n_segs, p, adv, vtarg, scratch, st, *launches);
-}
-
-size_t ppo_head_scratch_floats(int max_batch, int k) { return (size_t)head_waves(pad32(max_batch)) * part_stride(k, true); }
-
-int ppo_head_check(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows) { return check_loss_args(b, p, rows); }
-
-int ppo_head_launch(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0, int rows,
-                    const PpoHeadIo& io, hipStream_t st) {
-    const int rows_pad = pad32(rows);
-    PpoHead h;
-    fill_head(h, b, p, index, row0, rows, rows_pad);
-    h.mean = io.mean; h.ld_mean = io.ld_mean; h.ls = io.ls; h.ld_ls = 0; h.value = io.value; h.ld_value = io.ld_value;
-    h.d_mean = io.d_mean; h.ld_dm = io.ld_dm; h.width_dm = io.width_dm;
-    h.d_value = io.d_value; h.ld_dv = io.ld_dv; h.width_dv = io.width_dv;
-    h.part = io.part; h.part_stride = part_stride(b->k, io.colsum != 0); h.colsum = io.colsum;
-    hipLaunchKernelGGL(fc_ppo_head_kernel, dim3(head_waves(rows_pad) / 4), dim3(256), 0, st, h);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
-    PpoAdam a;
-    memset((void*)&a, 0, sizeof(a));
-    a.seg = segs;
-    long long total4 = 0;
-    for (int i = 0; i < segs.n; ++i) { total4 += segs.n4[i]; a.end4[i] = total4; }
-    a.s = ppo_adam_scalars(p, adam_t);
-    a.part = part; a.nparts = head_waves(pad32(rows)); a.part_stride = part_stride(k, colsum != 0);
-    a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
-    a.k = k;
-    if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
-    long long grid = (total4 + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
+int fc_eval_boot(pvae_fc* c, int s, int chunk, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st,
+                 int& launches) {
+    const int n_in = c->L.cfg.n_in, lv = (int)c->L.stack[s].size() - 1;
+    for (int first = 0; first < ro->n_segs; first += chunk) {
+        const int rows = ro->n_segs - first < chunk ? ro->n_segs - first : chunk;
+        Run r = value_run(c, s, rows, st);
+        int rc;
+        if ((rc = copy_in(r, ro->boot_obs + (size_t)first * n_in, nullptr, 0, ro->seg_done + first))) return rc;
+        if ((rc = run_forward(r, nullptr))) return rc;
+        PpoEval e;
+        memset(&e, 0, sizeof(e));
+        e.value = act_ptr(c, s, lv); e.ld_value = panel_ld(c, s, lv);
+        e.done = ro->seg_done + first;
+        e.rows = rows; e.k = ro->k;
+        e.vf = out->last_value + first;
+        if ((rc = ppo_eval_launch(e, st))) return rc;
+        launches += r.launches + 1;
+    }
     return 0;
 }
 
@@ -1461,7 +851,7 @@ size_t pvae_fc_ppo_workspace_bytes(const pvae_fc_config* cfg) {
     if (!cfg) return 0;
     const FcLayout L = make_fc_layout(*cfg);
     if (!L.ok) { fail(-1, "bad stack-set config: %s", L.why); return 0; }
-    return (ppo_scratch_floats(L) * sizeof(float) + 15) / 16 * 16;
+    return ppo_scratch_bytes(L.cfg.max_batch, L.cfg.n_out[0]);
 }
 
 int pvae_fc_ppo_sizeof(int which) {
@@ -1472,43 +862,15 @@ int pvae_fc_ppo_bind(pvae_fc* c, float* grad, float* m, float* v, void* scratch,
                      float* log_std_m, float* log_std_v) {
     if (!c || !grad || !m || !v || !scratch) return fail(-1, "null argument");
     if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
-    const size_t need = (ppo_scratch_floats(c->L) * sizeof(float) + 15) / 16 * 16;
+    const size_t need = ppo_scratch_bytes(c->L.cfg.max_batch, c->L.cfg.n_out[0]);
     if (scratch_bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
-    if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch) & 15)
-        return fail(-1, "grad, m, v and scratch must be 16-byte aligned");
-    if ((log_std_m != nullptr) != (log_std_v != nullptr) || (log_std_m && !log_std))
-        return fail(-1, "log_std_m and log_std_v go together, with log_std");
+    const int rc = check_ppo_buffers(grad, m, v, scratch, log_std, log_std_m, log_std_v);
+    if (rc) return rc;
     c->grad = grad; c->m = m; c->v = v; c->scratch = (float*)scratch;
     c->log_std = log_std; c->log_std_m = log_std_m; c->log_std_v = log_std_v;
     return 0;
 }
 
-int pvae_ppo_loss(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
-                  const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
-                  float* d_mean, float* d_log_std, float* d_value, float* stats_out, void* stream) {
-    int rc = check_loss_args(b, p, rows);
-    if (rc) return rc;
-    if (!mean || !log_std || !value) return fail(-1, "mean, log_std or value is null");
-    if (!d_mean || !d_log_std || !d_value || !stats_out) return fail(-1, "an output is null");
-    if (log_std_row_stride < 0) return fail(-1, "log_std_row_stride must be >= 0");
-    if (!index && rows > b->n_rows) return fail(-1, "rows %d > n_rows %lld without an index", rows, (long long)b->n_rows);
-    hipStream_t st = (hipStream_t)stream;
-    float* part = nullptr;
-    if ((rc = loss_scratch(st, &part))) return rc;
-    const int k = b->k, waves = head_waves(pad32(rows));      // (the fused step's row -> wave map: the same stats bits)
-    PpoHead h;
-    fill_head(h, b, p, index, 0, rows, rows);
-    h.mean = mean; h.ld_mean = k; h.ls = log_std; h.ld_ls = log_std_row_stride; h.value = value; h.ld_value = 1;
-    h.d_mean = d_mean; h.ld_dm = k; h.width_dm = k;
-    h.d_ls = d_log_std; h.ld_dls = k; h.width_dls = k;
-    h.d_value = d_value; h.ld_dv = 1; h.width_dv = 1;
-    h.part = part; h.part_stride = kPartStats; h.colsum = 0;
-    hipLaunchKernelGGL(fc_ppo_head_kernel, dim3(waves / 4), dim3(256), 0, st, h);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, waves, kPartStats, h.inv_rows, stats_out);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 
 int pvae_fc_ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                      const pvae_fc_ppo_params* p, float* stats_out, void* stream) {
@@ -1540,32 +902,6 @@ int pvae_fc_ppo_launches(pvae_fc* c, int32_t* per_step) {
     return 0;
 }
 
-size_t pvae_fc_gae_workspace_bytes(int32_t n_segs) {
-    if (n_segs < 1) { fail(-1, "n_segs must be >= 1, got %d", n_segs); return 0; }
-    return (gae_scratch_bytes(n_segs) + 15) / 16 * 16;
-}
-
-int pvae_gae_sizeof(int which) {
-    return which == 0 ? (int)sizeof(pvae_gae_params) : which == 1 ? (int)sizeof(pvae_fc_rollout)
-         : which == 2 ? (int)sizeof(pvae_fc_prepared) : fail(-1, "which must be 0, 1 or 2");
-}
-
-int pvae_gae(const float* rewards, const float* vf_preds, const float* last_values, const int32_t* seg_start,
-             const uint8_t* seg_done, int64_t n_rows, int32_t n_segs, int64_t seg_first, int64_t seg_last,
-             const pvae_gae_params* p, float* advantages, float* value_targets, void* scratch, size_t scratch_bytes,
-             void* stream) {
-    int rc = check_gae_params(p);
-    if (rc) return rc;
-    if (!rewards || !vf_preds || !last_values || !seg_start) return fail(-1, "rewards, vf_preds, last_values or seg_start is null");
-    if (!advantages || !value_targets) return fail(-1, "an output is null");
-    if ((rc = check_segments(n_rows, n_segs, seg_first, seg_last))) return rc;
-    if ((rc = check_gae_scratch(scratch, scratch_bytes, n_segs))) return rc;
-    int launches = 0;
-    if ((rc = run_gae(rewards, vf_preds, last_values, seg_done, seg_start, n_rows, n_segs, p, advantages, value_targets, scratch,
-                      (hipStream_t)stream, launches)))
-        return rc;
-    return launches;
-}
 
 int pvae_fc_ppo_evaluate(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
                          void* stream) {
@@ -1576,28 +912,21 @@ int pvae_fc_ppo_evaluate(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_p
     if (boot && (rc = check_boot(ro, out))) return rc;
     int ev = 0, rest = 0;
     if (rows_pass && (rc = eval_rows(c, ro, p, out, (hipStream_t)stream, ev))) return rc;
-    if (boot && (rc = eval_boot(c, ro, out, (hipStream_t)stream, rest))) return rc;
+    if (boot && (rc = fc_eval_boot(c, 1, c->L.cfg.max_batch, ro, out, (hipStream_t)stream, rest))) return rc;
     c->eval_launches = ev; c->gae_launches = rest;
     return 0;
 }
 
 int pvae_fc_ppo_prepare(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
                         void* scratch, size_t scratch_bytes, void* stream) {
-    int rc = check_gae_params(p);
+    int given = 0;
+    int rc = check_prepare(ro, p, out, scratch, scratch_bytes, &given,
+                           [&](bool rows_pass) { return check_eval(c, ro, p, out, rows_pass); });
     if (rc) return rc;
-    if (!ro || !out) return fail(-1, "null rollout or outputs");
-    const int given = (ro->vf_preds != nullptr) + (ro->old_dist != nullptr) + (ro->old_logp != nullptr);
-    if (given != 0 && given != 3) return fail(-1, "the sampler's vf_preds, old_dist and old_logp go together: all three or none");
-    if ((rc = check_eval(c, ro, p, out, given == 0))) return rc;
-    if ((rc = check_boot(ro, out))) return rc;
-    if (!ro->rewards || !ro->seg_start) return fail(-1, "rollout rewards or seg_start is null");
-    if (!out->advantages || !out->value_targets) return fail(-1, "advantages or value_targets is null");
-    if ((rc = check_segments(ro->n_rows, ro->n_segs, ro->seg_first, ro->seg_last))) return rc;
-    if ((rc = check_gae_scratch(scratch, scratch_bytes, ro->n_segs))) return rc;
     hipStream_t st = (hipStream_t)stream;
     int ev = 0, rest = 0;
     if (given == 0 && (rc = eval_rows(c, ro, p, out, st, ev))) return rc;
-    if ((rc = eval_boot(c, ro, out, st, rest))) return rc;
+    if ((rc = fc_eval_boot(c, 1, c->L.cfg.max_batch, ro, out, st, rest))) return rc;
     // (last_value already holds the zeros of the done segments)
     if ((rc = run_gae(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, nullptr, ro->seg_start, ro->n_rows,
                       ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))

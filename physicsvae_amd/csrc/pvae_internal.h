@@ -4,8 +4,11 @@
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
-//   pvae_fc.hip              the stack set and the PPO learner step on it
-//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae.hip and pvae_fc.hip
+//   pvae_fc.hip              the stack set, and its PPO learner step and train-batch preparation on the launches of pvae_ppo_core.hip
+//   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats, evaluate
+//                            epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
+//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae.hip,
+//                            pvae_fc.hip and pvae_ppo_core.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -336,6 +339,104 @@ int64_t auto_bucket_bytes(const pvae_ctx* c, int phase);
 std::vector<Bucket> exchange_buckets(const pvae_ctx* c, int net);
 int exchange_bucket(pvae_ctx* c, int net, const Bucket& b, const pvae_step_params* sp, hipStream_t st, hipStream_t cs, int& n_events);
 
+// ---- the PPO learner: what is model-independent (pvae_ppo_core.hip), one struct and one launch per kernel ----
+// batch row of minibatch row r: index[r] clamped into [0, n_rows) (a bad entry must not read out of bounds), or row0 + r
+__device__ inline long long batch_row(const int32_t* __restrict__ index, long long row0, long long n_rows, int r) {
+    if (!index) return row0 + r;
+    const long long i = index[r];
+    return i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
+}
+// The loss head on any panels or dense tensors.  fill_head sets the batch / params part and zeroes the rest; the caller
+// sets the panel fields, `part`, `part_stride` (= part_stride(k, colsum)) and `colsum`.
+struct PpoHead {
+    const float* mean; const float* ls; const float* value;       // row r at r * ld_*: panels or dense tensors
+    long long ld_mean, ld_ls, ld_value;
+    float ls_base;
+    const float* actions; const float* old_dist; const float* old_logp;
+    const float* adv; const float* vtarg; const float* vpred;
+    const int32_t* index; long long row0, n_rows;
+    int rows, rows_pad, k;
+    float clip, vf_clip, vf_coeff, kl_coeff, ent_coeff, inv_rows;
+    float* d_mean; float* d_ls; float* d_value;                  // [rows_pad][width_*] blocks, row stride ld_d* (null: none)
+    int ld_dm, ld_dls, ld_dv, width_dm, width_dls, width_dv;
+    float* part; int part_stride; int colsum;                    // partial rows [waves][part_stride]; colsum: + the log-std columns
+};
+int head_waves(int rows_pad);                                    // partial rows a head launch over rows_pad rows leaves
+int part_stride(int k, bool colsum);
+size_t ppo_scratch_bytes(int max_batch, int k);                  // the partial rows of the largest step, 16-byte rounded
+int check_loss_args(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows);
+void fill_head(PpoHead& h, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0,
+               int rows, int rows_pad);
+int ppo_head_launch(const PpoHead& h, hipStream_t st);
+// Adam over up to kAdamSegs segments, each with its own parameter, gradient and moment base pointers, + the stats and the
+// log-std vector's update (colsum) in the launch's last workgroup
+constexpr int kAdamSegs = 3 * PVAE_FC_MAX_STACKS;
+struct PpoAdamSegs {
+    int n;
+    float* p[kAdamSegs]; const float* g[kAdamSegs]; float* m[kAdamSegs]; float* v[kAdamSegs];
+    long long n4[kAdamSegs];                    // float4 elements of segment i
+};
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);
+int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
+                      const float* log_std_m, const float* log_std_v);      // the alignment and pairing rules of *_ppo_bind
+// Rows [r0, r1) of up to kZeroPanels panels (columns [0, width) of row stride ld) set to zero: a <= 4-row forward runs on
+// the GEMV kernels, which write the live rows only, while the backward contractions read whole 32-row tiles (a stale NaN
+// in a pad row would meet a zero gradient row and the product is NaN).
+constexpr int kZeroPanels = 1 + PVAE_FC_MAX_STACKS * PVAE_MAX_HIDDEN;       // a stack set: the shared first panel + the deeper ones
+static_assert(kZeroPanels >= 3 * (PVAE_MAX_HIDDEN + 1), "kZeroPanels must also hold PhysicsVAE's encoder, decoder and value panels");
+struct ZeroRows {
+    int n;
+    float* p[kZeroPanels];
+    int ld[kZeroPanels], width[kZeroPanels];
+    int r0, r1;
+    void add(float* ptr, int ld_, int width_) { p[n] = ptr; ld[n] = ld_; width[n] = width_; ++n; }
+};
+int zero_rows_launch(const ZeroRows& z, hipStream_t st);
+// dst[rows_pad][ld] = zero-padded copy of src[rows][n]; `index`: of the rows src[index[r]] (clamped into n_rows);
+// `done`: row r with done[r] is zeros and its source row is never read
+int pad_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const int32_t* index, long long n_rows,
+                    const uint8_t* done, hipStream_t st);
+// The evaluate epilogue of one chunk on any panels: vf[r], dist[r] = [mean | ls] and logp[r] of actions[r] for rows
+// r < rows (pointers: the chunk's first row), and, eps_dst given, the chunk's draws eps_src [rows][Z] copied out.
+// mean == NULL: the bootstrap use, vf[r] = done[r] ? 0 : value[r].
+struct PpoEval {
+    const float* mean; const float* ls; const float* value;
+    long long ld_mean, ld_ls, ld_value;
+    float ls_base;
+    const float* actions;
+    const uint8_t* done;
+    int rows, k;
+    float* vf; float* dist; float* logp;
+    const float* eps_src; float* eps_dst; int Z;
+};
+int ppo_eval_launch(const PpoEval& e, hipStream_t st);
+// GAE: the argument checks, and the GAE launch + (params->standardize) the rescale launch; `launches` counts them
+int check_gae_params(const pvae_gae_params* p);
+int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out);
+int check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last);
+int check_gae_scratch(const void* scratch, size_t bytes, int n_segs);
+int run_gae(const float* rewards, const float* vpred, const float* last_value, const uint8_t* done, const int32_t* seg_start,
+            long long n_rows, int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st,
+            int& launches);
+// What *_ppo_prepare checks before it launches, in order; `check_eval(rows_pass)` is the caller's own check of its model.
+// *given: 3 when the sampler's columns came with the rollout, 0 when the rows pass computes them.
+template <class CheckEval>
+int check_prepare(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, const void* scratch,
+                  size_t scratch_bytes, int* given, CheckEval&& check_eval) {
+    int rc = check_gae_params(p);
+    if (rc) return rc;
+    if (!ro || !out) return fail(-1, "null rollout or outputs");
+    *given = (ro->vf_preds != nullptr) + (ro->old_dist != nullptr) + (ro->old_logp != nullptr);
+    if (*given != 0 && *given != 3) return fail(-1, "the sampler's vf_preds, old_dist and old_logp go together: all three or none");
+    if ((rc = check_eval(*given == 0))) return rc;
+    if ((rc = check_boot(ro, out))) return rc;
+    if (!ro->rewards || !ro->seg_start) return fail(-1, "rollout rewards or seg_start is null");
+    if (!out->advantages || !out->value_targets) return fail(-1, "advantages or value_targets is null");
+    if ((rc = check_segments(ro->n_rows, ro->n_segs, ro->seg_first, ro->seg_last))) return rc;
+    return check_gae_scratch(scratch, scratch_bytes, ro->n_segs);
+}
+
 // ---- the PPO learner step of PhysicsVAE (pvae_ppo.hip) and what it runs of pvae.hip and pvae_fc.hip ----
 // pvae.hip: a stack's forward on the panels as they are, the sampler into the decoder's input panel, a stack's backward plan
 // with a gradient store into `grad_arena` (arena layout); `launches` counts what went out
@@ -356,49 +457,9 @@ struct FcValueStack {
     int panel_ld[PVAE_MAX_HIDDEN + 1];
 };
 int fc_value_stack(pvae_fc* c, FcValueStack* out);                                   // < 0: not a bound [value] set
-int fc_value_forward(pvae_fc* c, int rows, hipStream_t st, int* launches);           // on the input panel as it is
-int fc_value_backward(pvae_fc* c, int rows, hipStream_t st, int* launches);          // from d_value, into `grad`
-// pvae_fc.hip: the loss head on any panels, and the Adam + stats launch over up to three arena segments
-struct PpoHeadIo {
-    const float* mean; long long ld_mean;
-    const float* ls;                            // one vector of k values for all rows
-    const float* value; long long ld_value;
-    float* d_mean; int ld_dm, width_dm;         // null: not wanted
-    float* d_value; int ld_dv, width_dv;
-    float* part; int colsum;
-};
-size_t ppo_head_scratch_floats(int max_batch, int k);
-int ppo_head_check(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows);
-int ppo_head_launch(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0, int rows,
-                    const PpoHeadIo& io, hipStream_t st);
-struct PpoAdamSegs {
-    int n;
-    float* p[3]; const float* g[3]; float* m[3]; float* v[3];
-    long long n4[3];                            // float4 elements of segment i
-};
-int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);
-// pvae_fc.hip: the launches and argument checks of train-batch preparation, for pvae_ppo_evaluate / pvae_ppo_prepare.
-// The evaluate epilogue of one chunk on any panels: vf[r], dist[r] = [mean | ls] and logp[r] of actions[r] for rows
-// r < rows (pointers: the chunk's first row), and, eps_dst given, the chunk's draws eps_src [rows][Z] copied out.
-// mean == NULL: the bootstrap use, vf[r] = done[r] ? 0 : value[r].
-struct PpoEvalIo {
-    const float* mean; long long ld_mean;
-    const float* ls;                            // one vector of k values for all rows
-    const float* value; long long ld_value;
-    const float* actions;
-    const uint8_t* done;
-    int rows, k;
-    float* vf; float* dist; float* logp;
-    const float* eps_src; float* eps_dst; int Z;
-};
-int ppo_eval_launch(const PpoEvalIo& io, hipStream_t st);
-// rows of boot_obs [rows][n] into a [rows_pad][ld] panel: zeros in the pads and in the row of a done segment, never read
-int ppo_boot_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const uint8_t* done, hipStream_t st);
-int gae_check_params(const pvae_gae_params* p);
-int gae_check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out);
-int gae_check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last);
-int gae_check_scratch(const void* scratch, size_t bytes, int n_segs);
-// the GAE launch and, with params->standardize, the rescale launch (last_value already 0 where a segment is done)
-int gae_launch(const float* rewards, const float* vpred, const float* last_value, const int32_t* seg_start, long long n_rows,
-               int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st, int* launches);
+// pvae_fc.hip: stack s of a set as the value function (1 of an fcnn set, 0 of PhysicsVAE's one-stack set), alone
+int fc_value_forward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches);    // on the input panel as it is
+int fc_value_backward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches);   // from its output gradient block, into `grad`
+// last_value[i] = seg_done[i] ? 0 : value(boot_obs[i]) in chunks of `chunk` segments: copy | the value layers | epilogue
+int fc_eval_boot(pvae_fc* c, int s, int chunk, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st,
+                 int& launches);

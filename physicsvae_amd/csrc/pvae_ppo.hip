@@ -1,25 +1,20 @@
 // pvae_ppo.hip -- the PPO learner step of PhysicsVAE (include/pvae.h pvae_ppo_*; `run: DDPPO`, `custom_model: physics_vae`):
 // one minibatch update -- rmt:742-771 without the world model, the clipped-surrogate loss, backward, Adam -- as ONE
 // library call with no host synchronisation.  It joins launches that exist: the stacks' forward and backward plans of
-// pvae.hip, the stack set's grouped launches (the value branch) and the loss head of pvae_fc.hip.  No forward is
+// pvae.hip, the stack set's grouped launches (the value branch, pvae_fc.hip) and the learner's model-independent launches
+// (loss head, Adam + stats, evaluate epilogue, GAE: pvae_ppo_core.hip).  What is PhysicsVAE's own stays here: the copy-in
+// into three input panels, the sampler's backward, and the order of the launches.  No forward is
 // recomputed: the encoder's, the decoder's and the value stack's panels stay live from the forward to their backward
 // (the three stacks share no panel).  Launch order of a step:
 //   copy-in | [rows <= 4: zero pad rows] | TE layers | sampler | MD layers | value layers | loss head |
 //   MD backward (input gradient when the encoder is trained) | sampler backward | TE backward | value backward | Adam + stats
 // and its first half, train-batch preparation (pvae_ppo_evaluate / pvae_ppo_prepare): the step's forward launches in chunks of
-// max_batch rows with the stack set's evaluate epilogue in place of the loss head, then that path's bootstrap, GAE and
+// max_batch rows with the evaluate epilogue in place of the loss head, then the value stack's bootstrap pass and the GAE and
 // standardise launches.  Launch order of a chunk:
 //   copy-in | TE layers | sampler | MD layers | value layers | epilogue
 #include "pvae_internal.h"
 
 namespace {
-
-// batch row of minibatch row r: index[r] clamped into [0, n_rows) (a bad entry must not read out of bounds), or row0 + r
-__device__ inline long long ppo_batch_row(const int32_t* __restrict__ index, long long row0, long long n_rows, int r) {
-    if (!index) return row0 + r;
-    const long long i = index[r];
-    return i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
-}
 
 // obs[index[r]] = [s_body (Db) | s_task (Db)] into the three input panels, each written over its WHOLE [rows_pad][ld]
 // block: zeros in pad rows, in pad columns and in the blocks an input subset leaves out (StageArgs::in_off).  The decoder's
@@ -41,24 +36,8 @@ ppo_copy_in_kernel(PpoCopyIn a) {
         if (k == 0) on = on && c < 2 * Db && !(a.in_off & (c < Db ? 1 : 2));
         else if (k == 1) on = on && c < Db && !(a.in_off & 4);
         else on = on && c < 2 * Db;
-        dst[idx] = on ? a.obs[(size_t)ppo_batch_row(a.index, a.row0, a.n_rows, r) * (2 * Db) + c] : 0.f;
+        dst[idx] = on ? a.obs[(size_t)batch_row(a.index, a.row0, a.n_rows, r) * (2 * Db) + c] : 0.f;
     }
-}
-
-// Rows [r0, r1) of the layer-output panels set to zero: a <= 4-row forward runs on the GEMV kernels, which write the live
-// rows only, while the backward contractions read whole 32-row tiles.  blockIdx.y = panel.
-constexpr int kPpoZeroPanels = 3 * (PVAE_MAX_HIDDEN + 1);
-struct PpoZeroRows {
-    float* p[kPpoZeroPanels];
-    int ld[kPpoZeroPanels];
-    int r0, r1;
-};
-__global__ void __launch_bounds__(256)
-ppo_zero_rows_kernel(PpoZeroRows z) {
-    const int k = blockIdx.y;
-    float* __restrict__ p = z.p[k] + (size_t)z.r0 * z.ld[k];
-    const int total = (z.r1 - z.r0) * z.ld[k];
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) p[idx] = 0.f;
 }
 
 // Backward of the sampler on the panels (sampler_bwd_kernel's arithmetic, pvae.hip; autograd of rmt:734-740, no KL term:
@@ -110,9 +89,7 @@ int ppo_copy_in(pvae_ctx* c, const FcValueStack& vs, const float* obs, const int
     return 0;
 }
 
-size_t scratch_bytes(const pvae_config& cfg) {
-    return (ppo_head_scratch_floats(cfg.max_batch, cfg.dim_action) * sizeof(float) + 15) / 16 * 16;
-}
+size_t scratch_bytes(const pvae_config& cfg) { return ppo_scratch_bytes(cfg.max_batch, cfg.dim_action); }
 
 // what neither the step nor the evaluate pass runs: lookahead > 1, the learned and the sphere prior, the helper
 int check_ppo_config(const pvae_config& cfg) {
@@ -129,7 +106,7 @@ int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params*
     if (rc) return rc;
     const pvae_ctx::Ppo& q = c->ppo;
     if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
-    if ((rc = ppo_head_check(b, p, rows))) return rc;
+    if ((rc = check_loss_args(b, p, rows))) return rc;
     if (!b->obs) return fail(-1, "batch obs is null");
     if (!stats) return fail(-1, "stats_out is null");
     const pvae_config& cfg = c->L.cfg;
@@ -168,38 +145,33 @@ int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, co
     if ((rc = ppo_copy_in(c, vs, b->obs, index ? index + first : nullptr, first, b->n_rows, rows, st))) return rc;
     ++launches;
     if (rows <= 4 && rows < rows_pad) {
-        PpoZeroRows z;
+        ZeroRows z;
         memset(&z, 0, sizeof(z));
-        int n = 0, wmax = 0;
-        auto add = [&](float* ptr, int ld) { z.p[n] = ptr; z.ld[n] = ld; if (ld > wmax) wmax = ld; ++n; };
-        for (const Layer& l : TE.layers) add(w + wte.act[l.index], l.n_out_pad);
-        for (const Layer& l : MD.layers) add(w + wmd.act[l.index], l.n_out_pad);
-        for (int i = 0; i < vs.n_panels; ++i) add(vs.panel[i], vs.panel_ld[i]);
+        for (const Layer& l : TE.layers) z.add(w + wte.act[l.index], l.n_out_pad, l.n_out_pad);
+        for (const Layer& l : MD.layers) z.add(w + wmd.act[l.index], l.n_out_pad, l.n_out_pad);
+        for (int i = 0; i < vs.n_panels; ++i) z.add(vs.panel[i], vs.panel_ld[i], vs.panel_ld[i]);
         z.r0 = rows; z.r1 = rows_pad;
-        int gx = ((z.r1 - z.r0) * wmax + 255) / 256;
-        if (gx > 64) gx = 64;
-        hipLaunchKernelGGL(ppo_zero_rows_kernel, dim3(gx, n), dim3(256), 0, st, z);
-        HIP_TRY(hipGetLastError());
+        if ((rc = zero_rows_launch(z, st))) return rc;
         ++launches;
     }
     if ((rc = ppo_forward_net(c, PVAE_NET_TE, rows, st, &launches))) return rc;
     if ((rc = ppo_sampler(c, eps, rows, noise, seed, offset, st, &launches))) return rc;
     if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
-    if ((rc = fc_value_forward(q.value, rows, st, &launches))) return rc;
+    if ((rc = fc_value_forward(q.value, 0, rows, st, &launches))) return rc;
     const Layer& md_last = MD.layers.back();
     const Layer& te_last = TE.layers.back();
     const int colsum = p->log_std_kind == 1;
     const bool md_back = train_md || train_te;           // the decoder's backward runs: for its own gradient, or to pass one on
     {
-        PpoHeadIo io;
-        memset(&io, 0, sizeof(io));
-        io.mean = w + wmd.act.back(); io.ld_mean = md_last.n_out_pad;
-        io.ls = q.log_std;
-        io.value = vs.value; io.ld_value = vs.ld_value;
-        if (md_back) { io.d_mean = w + wmd.dz.back(); io.ld_dm = md_last.n_out_pad; io.width_dm = md_last.n_out_pad; }
-        if (train_v) { io.d_value = vs.d_value; io.ld_dv = vs.ld_dv; io.width_dv = vs.width_dv; }
-        io.part = q.scratch; io.colsum = colsum;
-        if ((rc = ppo_head_launch(b, p, index ? index + first : nullptr, first, rows, io, st))) return rc;
+        PpoHead h;
+        fill_head(h, b, p, index ? index + first : nullptr, first, rows, rows_pad);
+        h.mean = w + wmd.act.back(); h.ld_mean = md_last.n_out_pad;
+        h.ls = q.log_std;
+        h.value = vs.value; h.ld_value = vs.ld_value;
+        if (md_back) { h.d_mean = w + wmd.dz.back(); h.ld_dm = md_last.n_out_pad; h.width_dm = md_last.n_out_pad; }
+        if (train_v) { h.d_value = vs.d_value; h.ld_dv = vs.ld_dv; h.width_dv = vs.width_dv; }
+        h.part = q.scratch; h.part_stride = part_stride(b->k, colsum != 0); h.colsum = colsum;
+        if ((rc = ppo_head_launch(h, st))) return rc;
         ++launches;
     }
     if (md_back && (rc = ppo_backward_net(c, PVAE_NET_MD, rows, train_md, train_te, q.grad, st, &launches))) return rc;
@@ -213,7 +185,7 @@ int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, co
         ++launches;
         if ((rc = ppo_backward_net(c, PVAE_NET_TE, rows, true, false, q.grad, st, &launches))) return rc;
     }
-    if (train_v && (rc = fc_value_backward(q.value, rows, st, &launches))) return rc;
+    if (train_v && (rc = fc_value_backward(q.value, 0, rows, st, &launches))) return rc;
     {
         PpoAdamSegs sg;
         memset((void*)&sg, 0, sizeof(sg));
@@ -279,8 +251,8 @@ int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, co
                               &launches)))
             return rc;
         if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
-        if ((rc = fc_value_forward(c->ppo.value, rows, st, &launches))) return rc;
-        PpoEvalIo e;
+        if ((rc = fc_value_forward(c->ppo.value, 0, rows, st, &launches))) return rc;
+        PpoEval e;
         memset(&e, 0, sizeof(e));
         e.mean = c->ws + c->W.net[PVAE_NET_MD].act.back(); e.ld_mean = md_last.n_out_pad;
         e.ls = c->ppo.log_std;
@@ -289,30 +261,6 @@ int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, co
         e.rows = rows; e.k = k;
         e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
         if (d->eps_out) { e.eps_src = c->ws + c->W.eps; e.eps_dst = d->eps_out + (size_t)first * Z; e.Z = Z; }
-        if ((rc = ppo_eval_launch(e, st))) return rc;
-        ++launches;
-    }
-    return 0;
-}
-
-// last_value[s] = seg_done[s] ? 0 : value(boot_obs[s]): the value stack alone, in chunks of max_batch segments
-int eval_boot(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st,
-              int& launches) {
-    const int chunk = eval_chunk(c, vs);
-    for (int first = 0; first < ro->n_segs; first += chunk) {
-        const int rows = ro->n_segs - first < chunk ? ro->n_segs - first : chunk;
-        int rc;
-        if ((rc = ppo_boot_copy_launch(ro->boot_obs + (size_t)first * vs.n_in, vs.n_in, rows, vs.in, vs.ld_in, pad32(rows),
-                                       ro->seg_done + first, st)))
-            return rc;
-        ++launches;
-        if ((rc = fc_value_forward(c->ppo.value, rows, st, &launches))) return rc;
-        PpoEvalIo e;
-        memset(&e, 0, sizeof(e));
-        e.value = vs.value; e.ld_value = vs.ld_value;
-        e.done = ro->seg_done + first;
-        e.rows = rows; e.k = ro->k;
-        e.vf = out->last_value + first;
         if ((rc = ppo_eval_launch(e, st))) return rc;
         ++launches;
     }
@@ -341,13 +289,10 @@ int pvae_ppo_bind(pvae_ctx* c, float* grad, float* m, float* v, void* scratch, s
     if (!c->params) return fail(-2, "parameter arena not bound");
     const size_t need = scratch_bytes(c->L.cfg);
     if (bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, need);
-    if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch) & 15)
-        return fail(-1, "grad, m, v and scratch must be 16-byte aligned");
-    if ((log_std_m != nullptr) != (log_std_v != nullptr) || (log_std_m && !log_std))
-        return fail(-1, "log_std_m and log_std_v go together, with log_std");
-    FcValueStack vs;
-    int rc = fc_value_stack(value, &vs);
+    int rc = check_ppo_buffers(grad, m, v, scratch, log_std, log_std_m, log_std_v);
     if (rc) return rc;
+    FcValueStack vs;
+    if ((rc = fc_value_stack(value, &vs))) return rc;
     if (vs.n_in != 2 * c->L.cfg.dim_body)
         return fail(-1, "the value stack reads %d inputs, the observation has %d", vs.n_in, 2 * c->L.cfg.dim_body);
     pvae_ctx::Ppo& q = c->ppo;
@@ -406,10 +351,10 @@ int pvae_ppo_evaluate(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_par
     int rc = check_eval(c, ro, p, d, out, rows_pass, &vs);
     if (rc) return rc;
     if (!rows_pass && !boot) return fail(-1, "neither vf_preds nor last_value: nothing to compute");
-    if (boot && (rc = gae_check_boot(ro, out))) return rc;
+    if (boot && (rc = check_boot(ro, out))) return rc;
     int ev = 0, rest = 0;
     if (rows_pass && (rc = eval_rows(c, vs, ro, d, out, (hipStream_t)stream, ev))) return rc;
-    if (boot && (rc = eval_boot(c, vs, ro, out, (hipStream_t)stream, rest))) return rc;
+    if (boot && (rc = fc_eval_boot(c->ppo.value, 0, eval_chunk(c, vs), ro, out, (hipStream_t)stream, rest))) return rc;
     c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
     return 0;
 }
@@ -417,25 +362,18 @@ int pvae_ppo_evaluate(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_par
 int pvae_ppo_prepare(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
                      const pvae_fc_prepared* out, void* scratch, size_t scratch_bytes, void* stream) {
     if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
-    int rc = gae_check_params(p);
-    if (rc) return rc;
-    if (!ro || !out) return fail(-1, "null rollout or outputs");
-    const int given = (ro->vf_preds != nullptr) + (ro->old_dist != nullptr) + (ro->old_logp != nullptr);
-    if (given != 0 && given != 3) return fail(-1, "the sampler's vf_preds, old_dist and old_logp go together: all three or none");
     FcValueStack vs;
-    if ((rc = check_eval(c, ro, p, d, out, given == 0, &vs))) return rc;
-    if ((rc = gae_check_boot(ro, out))) return rc;
-    if (!ro->rewards || !ro->seg_start) return fail(-1, "rollout rewards or seg_start is null");
-    if (!out->advantages || !out->value_targets) return fail(-1, "advantages or value_targets is null");
-    if ((rc = gae_check_segments(ro->n_rows, ro->n_segs, ro->seg_first, ro->seg_last))) return rc;
-    if ((rc = gae_check_scratch(scratch, scratch_bytes, ro->n_segs))) return rc;
+    int given = 0;
+    int rc = check_prepare(ro, p, out, scratch, scratch_bytes, &given,
+                           [&](bool rows_pass) { return check_eval(c, ro, p, d, out, rows_pass, &vs); });
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     int ev = 0, rest = 0;
     if (given == 0 && (rc = eval_rows(c, vs, ro, d, out, st, ev))) return rc;
-    if ((rc = eval_boot(c, vs, ro, out, st, rest))) return rc;
+    if ((rc = fc_eval_boot(c->ppo.value, 0, eval_chunk(c, vs), ro, out, st, rest))) return rc;
     // (last_value already holds the zeros of the done segments)
-    if ((rc = gae_launch(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, ro->seg_start, ro->n_rows, ro->n_segs,
-                         p, out->advantages, out->value_targets, scratch, st, &rest)))
+    if ((rc = run_gae(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, nullptr, ro->seg_start, ro->n_rows,
+                      ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))
         return rc;
     c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
     return 0;

@@ -1,0 +1,551 @@
+// pvae_ppo_core.hip -- what the on-device PPO learner holds that no model owns (include/pvae.h "PPO learner step",
+// "Train-batch preparation"): the loss head and its finishing reduction, the Adam + stats launch, the evaluate epilogue,
+// the pad copy, the zero-rows launch, GAE and standardisation, their argument checks, and the entry points that need no
+// model at all (pvae_ppo_loss, pvae_gae).  The stack set's learner (pvae_fc.hip) and PhysicsVAE's (pvae_ppo.hip) fill the
+// argument structs of pvae_internal.h from their own panels and call the launch functions here: one kernel per job.
+#include "pvae_internal.h"
+
+#include <mutex>
+
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// PPO learner step: the loss head and the Adam + stats launch (include/pvae.h "PPO learner step")
+// ---------------------------------------------------------------------------------------
+// A wave works on one row at a time, lanes over the k actions, butterfly reductions (every lane ends with the same sum, in
+// an order that depends on nothing but k).  The launch has one wave for every two padded rows (head_waves): wave w takes
+// rows w, w + waves, ... one after the other: its sums of the five per-row terms and,
+// for a state-independent log-std, of the log-std gradient columns go to partial row w of the scratch buffer -- no
+// atomics, so the finishing reduction (ppo_finish) adds them in a fixed order.
+constexpr int kHeadMaxBlocks = 1024;
+constexpr int kPartStats = 8;             // floats reserved for the stats at the head of a partial row
+__device__ inline float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ void __launch_bounds__(256)
+ppo_head_kernel(PpoHead h) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int k = h.k;
+    float* __restrict__ part = h.part + (size_t)wave * h.part_stride;
+    if (h.colsum)
+        for (int j = lane; j < k; j += 64) part[kPartStats + j] = 0.f;
+    float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int r = wave; r < h.rows_pad; r += waves) {
+        const bool live = r < h.rows;
+        float dlogp = 0.f, dval = 0.f;
+        const float* mu = nullptr; const float* ls = nullptr; const float* act = nullptr; const float* od = nullptr;
+        if (live) {
+            const long long br = batch_row(h.index, h.row0, h.n_rows, r);
+            mu = h.mean + r * h.ld_mean; ls = h.ls + r * h.ld_ls;
+            act = h.actions + br * k; od = h.old_dist + br * 2 * k;
+            float zz = 0.f, lss = 0.f, kl = 0.f;
+            for (int j = lane; j < k; j += 64) {
+                const float l = h.ls_base + ls[j], inv_sig = expf(-l);
+                const float z = (act[j] - mu[j]) * inv_sig, d = od[j] - mu[j], lo = od[k + j];
+                zz = fmaf(z, z, zz);
+                lss += l;
+                kl += l - lo + (expf(2.f * lo) + d * d) * (0.5f * inv_sig * inv_sig) - 0.5f;
+            }
+            zz = wave_sum(zz); lss = wave_sum(lss); kl = wave_sum(kl);
+            const float logp = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;          // log(2 pi)
+            const float adv = h.adv[br], ratio = expf(logp - h.old_logp[br]);
+            const float lo_r = 1.f - h.clip, hi_r = 1.f + h.clip;
+            const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, lo_r), hi_r);
+            const float surr = fminf(s1, s2);
+            if (s1 < s2 || (ratio >= lo_r && ratio <= hi_r)) dlogp = -h.inv_rows * s1;
+            const float ent = lss + 0.5f * k * 2.8378770664093453f;                       // log(2 pi e)
+            const float val = h.value[r * h.ld_value], vt = h.vtarg[br], vp = h.vpred[br];
+            const float dv = val - vp, e1 = val - vt;
+            const float e2 = vp + fminf(fmaxf(dv, -h.vf_clip), h.vf_clip) - vt;
+            const float vf1 = e1 * e1, vf2 = e2 * e2, vf = fmaxf(vf1, vf2);
+            if (vf1 >= vf2 || fabsf(dv) <= h.vf_clip) dval = h.vf_coeff * h.inv_rows * 2.f * e1;
+            st[0] += -surr + h.kl_coeff * kl + h.vf_coeff * vf - h.ent_coeff * ent;
+            st[1] += -surr; st[2] += vf; st[3] += kl; st[4] += ent;
+        }
+        // the gradients, over the whole padded width of the row: zeros in pad rows and pad columns
+        const int wmax = max(h.d_mean ? h.width_dm : k, h.d_ls ? h.width_dls : k);
+        const float klc = h.kl_coeff * h.inv_rows, entc = h.ent_coeff * h.inv_rows;
+        for (int j = lane; j < wmax; j += 64) {
+            float gm = 0.f, gl = 0.f;
+            if (live && j < k) {
+                const float l = h.ls_base + ls[j], inv_sig = expf(-l), inv_var = inv_sig * inv_sig;
+                const float am = act[j] - mu[j], z = am * inv_sig, d = od[j] - mu[j];
+                gm = dlogp * am * inv_var - klc * d * inv_var;
+                gl = dlogp * (z * z - 1.f) + klc * (1.f - (expf(2.f * od[k + j]) + d * d) * inv_var) - entc;
+                if (h.colsum) part[kPartStats + j] += gl;
+            }
+            if (h.d_mean && j < h.width_dm) h.d_mean[(size_t)r * h.ld_dm + j] = gm;
+            if (h.d_ls && j < h.width_dls) h.d_ls[(size_t)r * h.ld_dls + j] = gl;
+        }
+        if (h.d_value)
+            for (int j = lane; j < h.width_dv; j += 64) h.d_value[(size_t)r * h.ld_dv + j] = j == 0 ? dval : 0.f;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int t = 0; t < 5; ++t) part[t] = st[t];
+    }
+}
+
+// The partial rows summed in a fixed order by ONE wave: stats_out[5] (means over the rows)
+__device__ inline void ppo_finish(const float* __restrict__ part, int nparts, int stride, float inv_rows, float* __restrict__ out,
+                                  int lane) {
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+        float s = 0.f;
+        for (int i = lane; i < nparts; i += 64) s += part[(size_t)i * stride + t];
+        s = wave_sum(s) * inv_rows;
+        if (lane == 0) out[t] = s;
+    }
+}
+__global__ void __launch_bounds__(64)
+ppo_finish_kernel(const float* part, int nparts, int stride, float inv_rows, float* out) {
+    ppo_finish(part, nparts, stride, inv_rows, out, threadIdx.x);
+}
+
+// Adam over the trained segments (adam_update4 with the AdamScalars the trainer's adam_flat_kernel gets: the same bits)
+// + ONE extra workgroup, the last: the stats and, for a state-independent log-std, that vector's gradient (the column
+// sums, added in partial-row order) and its Adam update.  A segment is a run of float4 elements with its own parameter,
+// gradient and moment base pointers: the trained stacks' parts of one stack-set arena, or the encoder's and the decoder's
+// parts of PhysicsVAE's arena and the value stack set's arena.
+struct PpoAdam {
+    PpoAdamSegs seg;
+    long long end4[kAdamSegs];                      // running float4 count through segment i
+    AdamScalars s;
+    const float* part; int nparts, part_stride; float inv_rows; float* stats_out;
+    int k; float* ls; float* ls_m; float* ls_v;
+};
+__global__ void __launch_bounds__(256)
+ppo_adam_kernel(PpoAdam a) {
+    if (blockIdx.x == gridDim.x - 1) {
+        if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
+        if (a.ls)
+            for (int j = threadIdx.x; j < a.k; j += 256) {
+                double gs = 0.0;               // (a few hundred signed terms per column: in double, so that the order does not show)
+                for (int i = 0; i < a.nparts; ++i) gs += (double)a.part[(size_t)i * a.part_stride + kPartStats + j];
+                const float g = (float)gs;
+                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
+                adam_update(g, p, m, v, a.s);
+                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
+            }
+        return;
+    }
+    const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
+        int k = 0;
+        while (i >= a.end4[k]) ++k;
+        const long long q = i - (k ? a.end4[k - 1] : 0);
+        v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
+        const v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
+        v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
+        v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
+        adam_update4(gg, pp, mm, vv, a.s);
+        reinterpret_cast<v4f*>(a.seg.p[k])[q] = pp;
+        reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
+        reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// glue: the pad copy and the zero-rows launch (pvae_internal.h)
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+ppo_pad_copy_kernel(const float* __restrict__ src, int n, int rows, float* __restrict__ dst, int ld, int rows_pad,
+                    const int32_t* __restrict__ index, long long n_rows, const uint8_t* __restrict__ done) {
+    const int total = rows_pad * ld;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / ld, c = idx - r * ld;
+        dst[idx] = (r < rows && c < n && !(done && done[r])) ? src[(size_t)batch_row(index, 0, n_rows, r) * n + c] : 0.f;
+    }
+}
+
+// blockIdx.y = panel
+__global__ void __launch_bounds__(256)
+ppo_zero_rows_kernel(ZeroRows z) {
+    const int k = blockIdx.y;
+    float* __restrict__ p = z.p[k];
+    const int ld = z.ld[k], width = z.width[k];
+    const int total = (z.r1 - z.r0) * width;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int r = idx / width, c = idx - r * width;
+        p[(size_t)(z.r0 + r) * ld + c] = 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// train-batch preparation: evaluate epilogue, GAE, standardisation (include/pvae.h "Train-batch preparation")
+// ---------------------------------------------------------------------------------------
+// The epilogue of one evaluated chunk: a wave per row reads the stacks' outputs in their panels and writes vf[r],
+// dist[r] = [mean | log_std] and logp[r] of actions[r] -- the arithmetic of ppo_head_kernel's logp, term for term, so
+// that the learner's first step sees a ratio of exactly 1.  mean == NULL: the bootstrap use -- the value stack ran alone;
+// vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.  eps_dst (PhysicsVAE's evaluate
+// pass): the latent draws of the chunk, eps_src [rows][Z], copied to the caller's rows.
+constexpr int kEvalMaxBlocks = 1024;
+__global__ void __launch_bounds__(256)
+ppo_eval_epilogue_kernel(PpoEval e) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int k = e.k;
+    for (int r = wave; r < e.rows; r += waves) {
+        if (!e.mean) {
+            if (lane == 0) e.vf[r] = e.done[r] ? 0.f : e.value[r * e.ld_value];
+            continue;
+        }
+        const float* mu = e.mean + r * e.ld_mean;
+        const float* ls = e.ls + r * e.ld_ls;
+        const float* act = e.actions + (size_t)r * k;
+        float* dist = e.dist + (size_t)r * 2 * k;
+        float zz = 0.f, lss = 0.f;
+        for (int j = lane; j < k; j += 64) {
+            const float l = e.ls_base + ls[j], inv_sig = expf(-l);
+            const float z = (act[j] - mu[j]) * inv_sig;
+            zz = fmaf(z, z, zz);
+            lss += l;
+            dist[j] = mu[j];
+            dist[k + j] = l;
+        }
+        zz = wave_sum(zz); lss = wave_sum(lss);
+        if (lane == 0) {
+            e.logp[r] = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                  // log(2 pi)
+            e.vf[r] = e.value[r * e.ld_value];
+        }
+        if (e.eps_dst)
+            for (int j = lane; j < e.Z; j += 64) e.eps_dst[(size_t)r * e.Z + j] = e.eps_src[(size_t)r * e.Z + j];
+    }
+}
+
+// GAE: adv[t] = delta[t] + gamma lambda adv[t + 1] inside a segment, a reverse linear recurrence.  One wavefront per
+// segment (wave w takes segments w, w + waves, ...) walks it from its end in 64-row pieces: lane l holds the row l places
+// before the piece's last one, the piece is an inclusive wave scan of the pairs (c, delta) under
+// (a2, b2) o (a1, b1) = (a1 a2, b2 + a2 b1), and the advantage of the row after the piece is the carry into it.  Segment
+// bounds are clamped into [0, n_rows]: a bad table cannot make the kernel touch memory outside the columns.  Every
+// workgroup leaves the sums of adv and adv^2 over its waves' rows, in double, in part[block][2]: no atomics, the
+// standardisation adds them in block order.
+constexpr int kGaeMaxBlocks = 1024;
+struct GaeArgs {
+    const float* rewards; const float* vpred; const float* last_value;
+    const uint8_t* done;                  // null: last_value as given
+    const int32_t* seg_start;
+    long long n_rows;
+    int n_segs;
+    float gamma, c;                       // c = gamma lambda
+    float* adv; float* vtarg;
+    double* part;
+};
+__device__ inline double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ void __launch_bounds__(256)
+gae_kernel(GaeArgs g) {
+    __shared__ double red[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wave = blockIdx.x * 4 + wv, waves = gridDim.x * 4;
+    double s1 = 0.0, s2 = 0.0;
+    for (int s = wave; s < g.n_segs; s += waves) {
+        long long a = g.seg_start[s], b = g.seg_start[s + 1];
+        a = a < 0 ? 0 : (a > g.n_rows ? g.n_rows : a);
+        b = b < a ? a : (b > g.n_rows ? g.n_rows : b);
+        if (b <= a) continue;             // (the same for every lane of the wave)
+        const float last = (g.done && g.done[s]) ? 0.f : g.last_value[s];
+        float carry = 0.f;
+        for (long long hi = b; hi > a; hi -= 64) {
+            const long long t = hi - 1 - lane;
+            const bool live = t >= a;
+            float pa = 1.f, pb = 0.f, v = 0.f;
+            if (live) {
+                v = g.vpred[t];
+                const float vn = t + 1 < b ? g.vpred[t + 1] : last;
+                pb = g.rewards[t] + g.gamma * vn - v;
+                pa = g.c;
+            }
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float qa = __shfl_up(pa, o, 64), qb = __shfl_up(pb, o, 64);
+                if (lane >= o) { pb = fmaf(pa, qb, pb); pa *= qa; }
+            }
+            const float x = fmaf(pa, carry, pb);
+            carry = __shfl(x, 63, 64);
+            if (live) {
+                g.adv[t] = x;
+                g.vtarg[t] = x + v;
+                s1 += (double)x;
+                s2 += (double)x * (double)x;
+            }
+        }
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    if (lane == 0) { red[wv][0] = s1; red[wv][1] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        g.part[(size_t)blockIdx.x * 2 + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// advantages = (adv - mean) / max(1e-4, std), population std: every workgroup adds the GAE launch's partial sums in the
+// same order (thread i the partials i, i + 256, ..., then a tree over the threads) and rescales its slice in place
+__global__ void __launch_bounds__(256)
+gae_standardize_kernel(float* __restrict__ adv, long long n, const double* __restrict__ part, int nparts) {
+    __shared__ double sh[2][256];
+    const int tid = threadIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int i = tid; i < nparts; i += 256) { a += part[2 * (size_t)i]; b += part[2 * (size_t)i + 1]; }
+    sh[0][tid] = a; sh[1][tid] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { sh[0][tid] += sh[0][tid + o]; sh[1][tid] += sh[1][tid + o]; }
+        __syncthreads();
+    }
+    const double mean = sh[0][0] / (double)n;
+    double var = sh[1][0] / (double)n - mean * mean;
+    if (!(var > 0.0)) var = 0.0;
+    const double sd = sqrt(var), inv = 1.0 / (sd > 1e-4 ? sd : 1e-4);
+    for (long long i = blockIdx.x * 256ll + tid; i < n; i += gridDim.x * 256ll) adv[i] = (float)(((double)adv[i] - mean) * inv);
+}
+
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
+AdamScalars ppo_adam_scalars(const pvae_fc_ppo_params* p, int t) {
+    pvae_step_params sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.lr = p->lr; sp.beta1 = p->beta1; sp.beta2 = p->beta2; sp.adam_eps = p->adam_eps; sp.weight_decay = p->weight_decay;
+    sp.adam_t[0] = t;
+    return adam_scalars(&sp, 0);
+}
+
+// scratch of pvae_ppo_loss (no context to hold one): one small buffer per (device, stream), made at the first call on that
+// stream and kept -- calls on one stream are ordered, so they can share it
+struct LossScratch { int dev; hipStream_t st; float* p; };
+std::vector<LossScratch> g_loss_scratch;
+std::mutex g_loss_scratch_mu;
+int loss_scratch(hipStream_t st, float** out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_loss_scratch_mu);
+    for (const LossScratch& e : g_loss_scratch)
+        if (e.dev == dev && e.st == st) { *out = e.p; return 0; }
+    float* p = nullptr;
+    HIP_TRY(hipMalloc((void**)&p, (size_t)4 * kHeadMaxBlocks * kPartStats * sizeof(float)));
+    g_loss_scratch.push_back(LossScratch{dev, st, p});
+    *out = p;
+    return 0;
+}
+
+int gae_blocks(int n_segs) {
+    const int b = (n_segs + 3) / 4;
+    return b > kGaeMaxBlocks ? kGaeMaxBlocks : (b < 1 ? 1 : b);
+}
+size_t gae_scratch_bytes(int n_segs) { return (size_t)gae_blocks(n_segs) * 2 * sizeof(double); }
+
+}  // namespace
+
+// ---- PPO learner step ----
+int head_waves(int rows_pad) {
+    int w = (rows_pad + 1) / 2;                       // two rows per wave
+    w = (w + 3) / 4 * 4;
+    return w > 4 * kHeadMaxBlocks ? 4 * kHeadMaxBlocks : w;
+}
+int part_stride(int k, bool colsum) { return kPartStats + (colsum ? (k + 3) / 4 * 4 : 0); }
+size_t ppo_scratch_bytes(int max_batch, int k) {
+    return ((size_t)head_waves(pad32(max_batch)) * part_stride(k, true) * sizeof(float) + 15) / 16 * 16;
+}
+
+int check_loss_args(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, int rows) {
+    if (!b || !p) return fail(-1, "null batch or params");
+    if (!b->actions || !b->old_dist || !b->old_logp || !b->advantages || !b->value_targets || !b->vf_preds)
+        return fail(-1, "a batch column is null");
+    if (b->n_rows < 1 || b->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)b->n_rows);
+    if (b->k < 1) return fail(-1, "k must be positive");
+    if (rows < 1) return fail(-1, "rows must be positive");
+    if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
+    if (!(p->clip_param >= 0.f) || !(p->vf_clip_param >= 0.f)) return fail(-1, "clip_param and vf_clip_param must be >= 0");
+    return 0;
+}
+
+void fill_head(PpoHead& h, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, const int32_t* index, long long row0,
+               int rows, int rows_pad) {
+    memset(&h, 0, sizeof(h));
+    h.actions = b->actions; h.old_dist = b->old_dist; h.old_logp = b->old_logp;
+    h.adv = b->advantages; h.vtarg = b->value_targets; h.vpred = b->vf_preds;
+    h.index = index; h.row0 = row0; h.n_rows = b->n_rows;
+    h.rows = rows; h.rows_pad = rows_pad; h.k = b->k;
+    h.clip = p->clip_param; h.vf_clip = p->vf_clip_param; h.vf_coeff = p->vf_loss_coeff;
+    h.kl_coeff = p->kl_coeff; h.ent_coeff = p->entropy_coeff;
+    h.inv_rows = (float)(1.0 / rows);
+}
+
+int ppo_head_launch(const PpoHead& h, hipStream_t st) {
+    hipLaunchKernelGGL(ppo_head_kernel, dim3(head_waves(pad32(h.rows)) / 4), dim3(256), 0, st, h);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
+    PpoAdam a;
+    memset((void*)&a, 0, sizeof(a));
+    a.seg = segs;
+    long long total4 = 0;
+    for (int i = 0; i < segs.n; ++i) { total4 += segs.n4[i]; a.end4[i] = total4; }
+    a.s = ppo_adam_scalars(p, adam_t);
+    a.part = part; a.nparts = head_waves(pad32(rows)); a.part_stride = part_stride(k, colsum != 0);
+    a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
+    a.k = k;
+    if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
+    long long grid = (total4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
+                      const float* log_std_m, const float* log_std_v) {
+    if (((uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch) & 15)
+        return fail(-1, "grad, m, v and scratch must be 16-byte aligned");
+    if ((log_std_m != nullptr) != (log_std_v != nullptr) || (log_std_m && !log_std))
+        return fail(-1, "log_std_m and log_std_v go together, with log_std");
+    return 0;
+}
+
+int zero_rows_launch(const ZeroRows& z, hipStream_t st) {
+    int wmax = 0;
+    for (int i = 0; i < z.n; ++i) wmax = std::max(wmax, z.width[i]);
+    int gx = ((z.r1 - z.r0) * wmax + 255) / 256;
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(ppo_zero_rows_kernel, dim3(gx, z.n), dim3(256), 0, st, z);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int pad_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const int32_t* index, long long n_rows,
+                    const uint8_t* done, hipStream_t st) {
+    int grid = (rows_pad * ld + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(ppo_pad_copy_kernel, dim3(grid), dim3(256), 0, st, src, n, rows, dst, ld, rows_pad, index, n_rows, done);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- train-batch preparation ----
+int ppo_eval_launch(const PpoEval& e, hipStream_t st) {
+    int blocks = (e.rows + 3) / 4;
+    if (blocks > kEvalMaxBlocks) blocks = kEvalMaxBlocks;
+    hipLaunchKernelGGL(ppo_eval_epilogue_kernel, dim3(blocks), dim3(256), 0, st, e);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int check_gae_params(const pvae_gae_params* p) {
+    if (!p) return fail(-1, "null params");
+    if (!(p->gamma >= 0.f && p->gamma <= 1.f) || !(p->lambda >= 0.f && p->lambda <= 1.f))
+        return fail(-1, "gamma and lambda must lie in [0, 1]");
+    return 0;
+}
+
+int check_segments(long long n_rows, int n_segs, long long seg_first, long long seg_last) {
+    if (n_rows < 1 || n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", n_rows);
+    if (n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", n_segs);
+    if (n_segs > n_rows) return fail(-1, "n_segs %d > n_rows %lld: a segment has at least one row", n_segs, n_rows);
+    if (seg_first != 0 || seg_last != n_rows)
+        return fail(-1, "seg_start must run from 0 to n_rows %lld, got %lld .. %lld", n_rows, seg_first, seg_last);
+    return 0;
+}
+
+int check_gae_scratch(const void* scratch, size_t bytes, int n_segs) {
+    if (!scratch) return fail(-1, "scratch is null");
+    if ((uintptr_t)scratch & 15) return fail(-1, "scratch must be 16-byte aligned");
+    if (bytes < gae_scratch_bytes(n_segs)) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, gae_scratch_bytes(n_segs));
+    return 0;
+}
+
+// the GAE launch and, with `standardize`, the rescale launch (arguments checked by the caller); `launches` counts them
+int run_gae(const float* rewards, const float* vpred, const float* last_value, const uint8_t* done, const int32_t* seg_start,
+            long long n_rows, int n_segs, const pvae_gae_params* p, float* adv, float* vtarg, void* scratch, hipStream_t st,
+            int& launches) {
+    GaeArgs g;
+    memset(&g, 0, sizeof(g));
+    g.rewards = rewards; g.vpred = vpred; g.last_value = last_value; g.done = done; g.seg_start = seg_start;
+    g.n_rows = n_rows; g.n_segs = n_segs; g.gamma = p->gamma; g.c = p->gamma * p->lambda;
+    g.adv = adv; g.vtarg = vtarg; g.part = (double*)scratch;
+    const int blocks = gae_blocks(n_segs);
+    hipLaunchKernelGGL(gae_kernel, dim3(blocks), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    if (p->standardize) {
+        long long grid = (n_rows + 255) / 256;
+        if (grid > 1024) grid = 1024;
+        hipLaunchKernelGGL(gae_standardize_kernel, dim3((int)grid), dim3(256), 0, st, adv, n_rows, (const double*)scratch, blocks);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    return 0;
+}
+
+int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) {
+    if (ro->n_segs < 1) return fail(-1, "n_segs must be >= 1, got %d", ro->n_segs);
+    if (!ro->boot_obs || !ro->seg_done) return fail(-1, "rollout boot_obs or seg_done is null");
+    if (!out->last_value) return fail(-1, "last_value is null");
+    return 0;
+}
+
+extern "C" {
+
+int pvae_ppo_loss(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
+                  const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
+                  float* d_mean, float* d_log_std, float* d_value, float* stats_out, void* stream) {
+    int rc = check_loss_args(b, p, rows);
+    if (rc) return rc;
+    if (!mean || !log_std || !value) return fail(-1, "mean, log_std or value is null");
+    if (!d_mean || !d_log_std || !d_value || !stats_out) return fail(-1, "an output is null");
+    if (log_std_row_stride < 0) return fail(-1, "log_std_row_stride must be >= 0");
+    if (!index && rows > b->n_rows) return fail(-1, "rows %d > n_rows %lld without an index", rows, (long long)b->n_rows);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = nullptr;
+    if ((rc = loss_scratch(st, &part))) return rc;
+    const int k = b->k, waves = head_waves(pad32(rows));      // (the fused step's row -> wave map: the same stats bits)
+    PpoHead h;
+    fill_head(h, b, p, index, 0, rows, rows);
+    h.mean = mean; h.ld_mean = k; h.ls = log_std; h.ld_ls = log_std_row_stride; h.value = value; h.ld_value = 1;
+    h.d_mean = d_mean; h.ld_dm = k; h.width_dm = k;
+    h.d_ls = d_log_std; h.ld_dls = k; h.width_dls = k;
+    h.d_value = d_value; h.ld_dv = 1; h.width_dv = 1;
+    h.part = part; h.part_stride = kPartStats; h.colsum = 0;
+    if ((rc = ppo_head_launch(h, st))) return rc;
+    hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, waves, kPartStats, h.inv_rows, stats_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t pvae_fc_gae_workspace_bytes(int32_t n_segs) {
+    if (n_segs < 1) { fail(-1, "n_segs must be >= 1, got %d", n_segs); return 0; }
+    return (gae_scratch_bytes(n_segs) + 15) / 16 * 16;
+}
+
+int pvae_gae_sizeof(int which) {
+    return which == 0 ? (int)sizeof(pvae_gae_params) : which == 1 ? (int)sizeof(pvae_fc_rollout)
+         : which == 2 ? (int)sizeof(pvae_fc_prepared) : fail(-1, "which must be 0, 1 or 2");
+}
+
+int pvae_gae(const float* rewards, const float* vf_preds, const float* last_values, const int32_t* seg_start,
+             const uint8_t* seg_done, int64_t n_rows, int32_t n_segs, int64_t seg_first, int64_t seg_last,
+             const pvae_gae_params* p, float* advantages, float* value_targets, void* scratch, size_t scratch_bytes,
+             void* stream) {
+    int rc = check_gae_params(p);
+    if (rc) return rc;
+    if (!rewards || !vf_preds || !last_values || !seg_start) return fail(-1, "rewards, vf_preds, last_values or seg_start is null");
+    if (!advantages || !value_targets) return fail(-1, "an output is null");
+    if ((rc = check_segments(n_rows, n_segs, seg_first, seg_last))) return rc;
+    if ((rc = check_gae_scratch(scratch, scratch_bytes, n_segs))) return rc;
+    int launches = 0;
+    if ((rc = run_gae(rewards, vf_preds, last_values, seg_done, seg_start, n_rows, n_segs, p, advantages, value_targets, scratch,
+                      (hipStream_t)stream, launches)))
+        return rc;
+    return launches;
+}
+
+}  // extern "C"

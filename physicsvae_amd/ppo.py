@@ -1,6 +1,6 @@
 """The PPO learner step of the imitation stage (`run: DDPPO`, `custom_model: fcnn`): its configuration under RLlib's key
 names, the loss restated in plain torch (the specification and the tests' oracle; RLlib 1.11's ppo_torch_policy computes
-the same terms), its closed-form gradients (what `fc_ppo_head_kernel` follows), and the HIP loss head under autograd.
+the same terms), its closed-form gradients (what `ppo_head_kernel` follows), and the HIP loss head under autograd.
 
     logp    = -0.5 sum_j ((a_j - mean_j) / exp(ls_j))^2 - sum_j ls_j - 0.5 k log(2 pi)
     ratio   = exp(logp - old_logp)

@@ -159,7 +159,7 @@ def arena_views(m, arena):
 
 
 def ls_grad_from_moment(m, beta1=0.9):
-    """After the FIRST step from zero moments m = (1 - beta1) g: the gradient `fc_adam_kernel` formed for the vector."""
+    """After the FIRST step from zero moments m = (1 - beta1) g: the gradient `ppo_adam_kernel` formed for the vector."""
     f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))            # noqa: E731
     return m.engine.ppo_ls_m.double().cpu() / f32(1.0 - f32(beta1))      # (the factor as the library rounds it)
 

@@ -1,0 +1,197 @@
+"""Digests of everything the on-device PPO learner computes, for comparing two builds of the library bit for bit: in one
+process, with fixed seeds, every entry point that runs the learner's kernels (the fused steps of the stack set and of
+PhysicsVAE, `pvae_ppo_loss`, `pvae_gae`, evaluate and prepare of both models) at the smallest shapes that still take every
+path -- k 5 (a padded column-sum stride), 70 rows in minibatches of 33 (a two-tile step with pad rows and a 4-row step on
+the GEMV / zero-rows path), segments of 1, 63, 64, 65 and 130 rows (a piece boundary and a carry), 70 rows in 40 segments at
+max_batch 32 (more than one chunk in the rows pass and in the bootstrap pass, the last one short).  Prints one JSON line:
+scenario -> output tensor -> sha256 of its raw bytes.  The library is the in-tree one, or the one PVAE_LIB_PATH names:
+
+    python tools/ppo_digest.py > new.json;  PVAE_LIB_PATH=/path/to/other/libpvae_gfx950.so python tools/ppo_digest.py > old.json
+
+Two builds that launch the same kernels in the same order with the same arithmetic print the same line.  The digests belong
+to one compiler and one pair of builds: they are compared, never pinned.
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from physicsvae_amd import engine as E                           # noqa: E402
+from physicsvae_amd import ppo as P                              # noqa: E402
+
+DEV = "cuda"
+K = 5
+CFG = P.PPOConfig(clip_param=0.2, kl_coeff=0.3, entropy_coeff=0.01, vf_clip_param=0.7, vf_loss_coeff=0.5, lr=1e-3,
+                  gamma=0.98, lambda_=0.95)
+
+
+def digest(tensors):
+    torch.cuda.synchronize()
+    return {name: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+            for name, t in tensors.items() if t is not None}
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def fill(views, rng):
+    """Weights N(0, 1 / n_in) and small biases into the live entries of an arena (its pads stay zero)."""
+    with torch.no_grad():
+        for w, b in views:
+            w.copy_(dev((rng.standard_normal(tuple(w.shape)) / np.sqrt(w.shape[1])).astype(np.float32)))
+            b.copy_(dev((0.1 * rng.standard_normal(tuple(b.shape))).astype(np.float32)))
+
+
+def pairs(named):
+    names = sorted(k[:-len("weight")] for k in named if k.endswith("weight"))
+    return [(named[n + "weight"], named[n + "bias"]) for n in names]
+
+
+def batch(rng, n, n_in):
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)      # noqa: E731
+    b = {"obs": f(n, n_in), "actions": f(n, K), "old_dist": np.concatenate([0.3 * f(n, K), -0.5 + 0.1 * f(n, K)], 1),
+         "old_logp": -6.0 + f(n), "advantages": f(n), "value_targets": f(n), "vf_preds": f(n)}
+    return {k: dev(v) for k, v in b.items()}
+
+
+def perms(rng, passes, n):
+    return dev(np.stack([rng.permutation(n) for _ in range(passes)]).astype(np.int32))
+
+
+def rollout(rng, n_in):
+    """70 rows in 40 segments (30 of two rows, 10 of one), every fifth segment done."""
+    lens = [2] * 30 + [1] * 10
+    n, s = sum(lens), len(lens)
+    f = lambda *sh: rng.standard_normal(sh).astype(np.float32)    # noqa: E731
+    ro = {"obs": dev(f(n, n_in)), "actions": dev(f(n, K)), "rewards": dev(rng.random(n, dtype=np.float32)),
+          "seg_start": torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)),
+          "seg_done": dev((np.arange(s) % 5 == 2).astype(np.uint8)), "boot_obs": dev(f(s, n_in))}
+    sampler = {"vf_preds": dev(f(n)), "old_dist": dev(np.concatenate([0.3 * f(n, K), -0.5 + 0.1 * f(n, K)], 1)),
+               "old_logp": dev(-6.0 + f(n))}
+    return ro, sampler
+
+
+def log_std_vector(rng):
+    return dev((-0.5 + 0.1 * rng.standard_normal(K)).astype(np.float32))
+
+
+def fc_engine(kind, max_batch, rng):
+    stacks = [(E.Stack.of((32, 2)), K), (E.Stack.of((16, 2)), 1)] + ([(E.Stack.of((32, 2)), K)] if kind == 2 else [])
+    eng = E.StackSetEngine(7, stacks, max_batch, device=DEV)
+    for s in range(len(stacks)):
+        fill(eng.views(s), rng)
+    ls = None if kind == 2 else log_std_vector(rng)
+    eng.ppo_bind(ls, kind == 1)
+    return eng, ls
+
+
+def fc_sgd(out):
+    for kind in (0, 1, 2):
+        for with_perm in (False, True):
+            for frozen in (False, True):
+                rng = np.random.default_rng(100 + kind)
+                eng, ls = fc_engine(kind, 64, rng)
+                b = batch(rng, 70, 7)
+                mask = 0 if not frozen else (5 if kind == 2 else 1)             # frozen: every stack but the value stack (1)
+                stats = eng.ppo_sgd(b, CFG.params(kind, -0.5 if kind == 2 else 0.0, adam_t=1, train_mask=mask), 33, 2,
+                                    perms(rng, 2, 70) if with_perm else None)
+                out["fc_sgd kind%d perm%d value_frozen%d" % (kind, with_perm, frozen)] = digest(
+                    {"stats": stats, "params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "log_std": ls,
+                     "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v})
+
+
+def loss(out):
+    rng = np.random.default_rng(200)
+    b = batch(rng, 40, 7)
+    del b["obs"]
+    for rows in (3, 33):
+        mean, value = dev(0.3 * rng.standard_normal((rows, K)).astype(np.float32)), dev(rng.standard_normal(rows).astype(np.float32))
+        per_row, vec = dev((-0.5 + 0.1 * rng.standard_normal((rows, K))).astype(np.float32)), log_std_vector(rng)
+        index = dev(rng.integers(0, 40, rows).astype(np.int32))
+        for with_index in (False, True):
+            for broadcast in (False, True):
+                ls = vec.expand(rows, K) if broadcast else per_row
+                stats, d_mean, d_ls, d_value = E.ppo_loss(mean, ls, value, b, CFG.params(0), index if with_index else None)
+                out["loss rows%d index%d broadcast%d" % (rows, with_index, broadcast)] = digest(
+                    {"stats": stats, "d_mean": d_mean, "d_log_std": d_ls, "d_value": d_value})
+
+
+def gae(out):
+    rng = np.random.default_rng(300)
+    lens = [1, 63, 64, 65, 130]
+    n = sum(lens)
+    seg = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32))
+    rewards, vf = dev(rng.random(n, dtype=np.float32)), dev(rng.standard_normal(n).astype(np.float32))
+    last, done = dev(rng.standard_normal(len(lens)).astype(np.float32)), dev(np.array([0, 1, 0, 0, 1], dtype=np.uint8))
+    for with_done in (False, True):
+        for standardize in (False, True):
+            adv, vt = E.gae(rewards, vf, last, seg, CFG.gamma, CFG.lambda_, standardize, done if with_done else None)
+            out["gae done%d standardize%d" % (with_done, standardize)] = digest({"advantages": adv, "value_targets": vt})
+
+
+def fc_prepare(out):
+    for kind in (0, 2):
+        rng = np.random.default_rng(400 + kind)
+        eng, _ = fc_engine(kind, 32, rng)
+        ro, sampler = rollout(rng, 7)
+        gp = CFG.gae_params(kind, -0.5 if kind == 2 else 0.0)
+        out["fc_evaluate kind%d" % kind] = digest(eng.ppo_evaluate(ro, gp))
+        out["fc_prepare kind%d" % kind] = digest(eng.ppo_prepare(ro, gp))
+        out["fc_prepare_given kind%d" % kind] = digest(eng.ppo_prepare(dict(ro, **sampler), gp))
+
+
+def vae_engine(prior, kind, max_batch, rng):
+    arch = E.Arch(6, K, 4, te=(32, 2), md=(32, 2), wm=(16, 1), prior=prior)
+    eng = E.HipEngine(arch, max_batch, device=DEV)
+    fill(pairs(eng.named_views()), rng)
+    ve = E.StackSetEngine(12, [(E.Stack.of((16, 2)), 1)], max_batch, device=DEV)
+    fill(ve.views(0), rng)
+    ls = log_std_vector(rng)
+    eng.ppo_bind(ve, ls, kind == 1)
+    return eng, ve, ls
+
+
+def vae_sgd(out):
+    for prior in ("normal_zero_mean_one_std", False):
+        for kind in (0, 1):
+            for with_eps in (False, True):
+                for mask in (7, 3, 4):
+                    rng = np.random.default_rng(500 + kind)
+                    eng, ve, ls = vae_engine(prior, kind, 64, rng)
+                    b = batch(rng, 70, 12)
+                    eps = dev(rng.standard_normal((6, 33, 4)).astype(np.float32)) if with_eps else None
+                    stats = eng.ppo_sgd(b, CFG.params(kind, 0.0, adam_t=1, train_mask=mask), 33, 2, perms(rng, 2, 70), eps=eps,
+                                        noise=True, seed=11, offset=5)
+                    out["vae_sgd prior_%s kind%d eps%d mask%d" % (prior, kind, with_eps, mask)] = digest(
+                        {"stats": stats, "params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "value_params": ve.params,
+                         "value_m": ve.ppo_m, "value_v": ve.ppo_v, "log_std": ls, "log_std_m": eng.ppo_ls_m,
+                         "log_std_v": eng.ppo_ls_v})
+
+
+def vae_prepare(out):
+    for prior in ("normal_zero_mean_one_std", False):
+        rng = np.random.default_rng(600)
+        eng, _, _ = vae_engine(prior, 0, 32, rng)
+        ro, sampler = rollout(rng, 12)
+        gp = CFG.gae_params(0)
+        eps = dev(rng.standard_normal((70, 4)).astype(np.float32))
+        out["vae_evaluate prior_%s" % prior] = digest(eng.ppo_evaluate(ro, gp, noise=True, seed=11, offset=5))
+        out["vae_prepare prior_%s" % prior] = digest(eng.ppo_prepare(ro, gp, eps=eps))
+        out["vae_prepare_given prior_%s" % prior] = digest(eng.ppo_prepare(dict(ro, **sampler), gp))
+
+
+def main():
+    assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
+    out = {}
+    for scenario in (fc_sgd, loss, gae, fc_prepare, vae_sgd, vae_prepare):
+        scenario(out)
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
