@@ -578,7 +578,9 @@ int pvae_reparam_backward(pvae_ctx* ctx, const float* mu_logvar, const float* ep
  * them, instead of one per layer per stack.
  *
  * pvae_fc_config: stack s has depth[s] hidden layers of width[s][i] with activation act[s][i] (PVAE_ACT_*), then a linear
- * output layer of n_out[s] values.  1 <= n_stacks <= PVAE_FC_MAX_STACKS, depth in [0, PVAE_MAX_HIDDEN].
+ * output layer of n_out[s] values.  1 <= n_stacks <= PVAE_FC_MAX_STACKS, depth in [0, PVAE_MAX_HIDDEN].  depth 0 -- the
+ * stack is its linear output layer alone, a column block of the shared first-layer GEMM -- is supported and tested
+ * (tests/test_gpu_fc_shapes.py, forward and backward against float64, both schedules), though the Python `Stack` refuses it.
  *
  * Arena (one flat fp32 buffer, the padding rules of the five-net arena: W[n_out_pad][ld] row-major with ld = n_in rounded
  * up to 64 and n_out_pad = n_out rounded up to 64, then bias[n_out_pad]; pads are zero and stay zero):
