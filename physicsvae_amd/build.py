@@ -9,8 +9,8 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpvae_gfx950.so")
-UNITS = ["pvae.hip", "pvae_exchange.hip", "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip",
-         "pvae_ppo.hip"]
+UNITS = ["pvae.hip", "pvae_net.hip", "pvae_step.hip", "pvae_lookahead.hip", "pvae_infer.hip", "pvae_exchange.hip",
+         "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip", "pvae_ppo.hip"]
 HEADERS = ["pvae_internal.h", "pvae_gemm.h", "pvae_layout.h", "pvae_fc_layout.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(HERE), "include", "pvae.h")

@@ -135,7 +135,7 @@ fc_forward_group_kernel(FcFwdGroup g) {
     else splitk_reg_body<true, EpiFc, 0>(lds, b - lo, ga, e);
 }
 
-// forward, rows <= 4: the arithmetic of gemv_rows_kernel (pvae.hip) -- one wave per output feature streams its weight row
+// forward, rows <= 4: the arithmetic of gemv_rows_kernel (pvae_net.hip) -- one wave per output feature streams its weight row
 // once with float4 loads, lanes split K and combine with a shuffle tree -- over the layers of one depth of all stacks
 struct FcGemvProb {
     const float* x; const float* W; const float* bias;

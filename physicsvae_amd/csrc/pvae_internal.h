@@ -1,13 +1,17 @@
 // pvae_internal.h -- what the translation units of libpvae_gfx950.so share: error handling, the optional per-launch
 // profiler, the run-time RCCL binding, the context, Philox, and the few functions one unit calls in another.
-//   pvae.hip                 the training step (glue kernels, forward / backward plans, the C ABI of the step and of rollout launches)
+//   pvae.hip                 the context: layout queries, lifecycle, options, bindings, minibatch staging, pvae_read_tensor
+//   pvae_net.hip             one stack: forward launches, the sampler, the backward plan and its deferred-Adam hand-over
+//   pvae_step.hip            the training step at lookahead 1 and the step's C ABI (direct, prefetch and data-parallel steps)
+//   pvae_lookahead.hip       the training step at lookahead > 1 (the multi-step unroll)
+//   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
 //   pvae_fc.hip              the stack set, and its PPO learner step and train-batch preparation on the launches of pvae_ppo_core.hip
 //   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats, evaluate
 //                            epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
-//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae.hip,
+//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae_infer.hip,
 //                            pvae_fc.hip and pvae_ppo_core.hip
 #pragma once
 #include <hip/hip_runtime.h>
@@ -305,6 +309,103 @@ __device__ inline float philox_normal(uint64_t seed, uint64_t offset, uint32_t r
     return philox_normal4(seed, offset, row, col >> 2)[col & 3];
 }
 
+__device__ inline float block_sum_256(float v) {
+    __shared__ float red[4];
+    return block_sum_256(v, red);
+}
+
+// The same sampler as the PROLOGUE of the decoder's first-layer launch (pvae_gemm.h, splitk_ws_body / NoPro): every
+// workgroup of that launch forms z for its own 32 batch rows while its first k-tile is in flight and patches it over
+// the z columns of its input tile in LDS; the workgroups of column tile 0 also store z (the decoder's first-layer
+// weight gradient reads it from the input panel), the draws actually used, and the KL partial of their row block.
+// One launch less per joint step (the sampler launch was ~4.5 us of fixed cost for 8 K elements).
+struct ProSampler {
+    static constexpr bool kActive = true;
+    static constexpr int kMaxZ = 64, kScratchFloats = 8;
+    static constexpr int kPer = 32 * kMaxZ / 4 / 256;     // work items per thread at Z = kMaxZ
+    const float* te_out; int ldte;       // encoder output [mu | logvar]
+    const float* eps_in;                 // supplied draws [rows][Z], or null: Philox
+    float* eps_used;                     // [rows_pad][Z]
+    float* md_in; int ld_md;             // the decoder's input panel: z columns written by column tile 0
+    int c0, Z, rows, noise;              // z columns = [c0, c0 + Z), Z % 4 == 0
+    unsigned long long seed, offset;
+    float* partial;                      // KL partial per row block (tiles_q of them), or null
+    // work item = 4 consecutive z columns of one row (one Philox call, 16-byte accesses): item e of the workgroup is
+    // row e / (Z/4), columns 4 (e % (Z/4)) ..; thread tid owns items tid, tid + 256, ...
+    struct State { v4f mu[kPer], lv[kPer], ep[kPer], z[kPer]; bool formed; };
+    __device__ inline bool needs(int t) const { return t == (c0 >> 6) || t == ((c0 + Z - 1) >> 6); }
+    // request the inputs (the encoder's output was written through by the previous launch: cold fetches, which now
+    // travel while the k-tiles in front of the z columns are contracted)
+    __device__ inline State prepare(int q0, int tid) const {
+        State st;
+        const int G = Z >> 2;
+        const float* __restrict__ te = te_out;
+        const float* __restrict__ ei = eps_in;
+        const v4f zero = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int e = tid + 256 * u;
+            const int r = e / G, j = (e - r * G) * 4, q = q0 + r;
+            const bool live = e < 32 * G && q < rows;
+            st.mu[u] = live ? *reinterpret_cast<const v4f*>(te + (size_t)q * ldte + j) : zero;
+            st.lv[u] = live ? *reinterpret_cast<const v4f*>(te + (size_t)q * ldte + Z + j) : zero;
+            st.ep[u] = (live && noise && ei) ? *reinterpret_cast<const v4f*>(ei + (size_t)q * Z + j) : zero;
+            st.z[u] = zero;
+        }
+        st.formed = false;
+        return st;
+    }
+    // tile = the swizzled [32][64] image of k-tile t (chunk ^= row & 15, as the loaders write it)
+    __device__ inline void patch(float* tile, float* scratch, State& st, int t, int q0, int tile_p, int, int tid) const {
+        const int G = Z >> 2;
+        if (!st.formed) {                 // first patched tile: form z, KL partial, and (column tile 0) store z and the draws
+            float acc = 0.f;
+#pragma unroll
+            for (int u = 0; u < kPer; ++u) {
+                const int e = tid + 256 * u;
+                if (e >= 32 * G) break;
+                const int r = e / G, j = (e - r * G) * 4, q = q0 + r;
+                v4f ee = v4f{0.f, 0.f, 0.f, 0.f};
+                if (q < rows) {
+                    if (noise) ee = eps_in ? st.ep[u] : philox_normal4(seed, offset, q, j >> 2);
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) {
+                        st.z[u][x] = __fmaf_rn(ee[x], expf(0.5f * st.lv[u][x]), st.mu[u][x]);
+                        acc += -0.5f * (1.0f + st.lv[u][x] - st.mu[u][x] * st.mu[u][x] - expf(st.lv[u][x]));
+                    }
+                }
+                if (tile_p == 0) {
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) md_in[(size_t)q * ld_md + c0 + j + x] = st.z[u][x];      // (c0 = dim_body: unaligned)
+                    *reinterpret_cast<v4f*>(eps_used + (size_t)q * Z + j) = ee;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+            if ((tid & 63) == 0) scratch[tid >> 6] = acc;
+            st.formed = true;
+        }
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int e = tid + 256 * u;
+            if (e >= 32 * G) break;
+            const int r = e / G, j = (e - r * G) * 4;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const int c = c0 + j + x;
+                if ((c >> 6) != t) continue;
+                const int kc = c & 63;
+                tile[r * 64 + ((((kc >> 2) ^ (r & 15))) << 2) + (kc & 3)] = st.z[u][x];
+            }
+        }
+    }
+    // behind the barrier that follows the first patch: the four compute waves' KL sums are in the scratch
+    __device__ inline void publish(const float* scratch, int t, int tile_p, int tile_q, int tid) const {
+        if (t == (c0 >> 6) && tile_p == 0 && tid == 0 && partial)
+            partial[tile_q] = (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
+    }
+};
+
 // ---------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------
@@ -333,7 +434,124 @@ inline int check_ready(const pvae_ctx* c, bool need_arenas) {
 }
 
 
-// ---- pvae_exchange.hip, called by the data-parallel step in pvae.hip ----
+// grid of a 1-D glue launch: one thread per element in blocks of 256, at most `cap` blocks (the kernels stride)
+inline int grid1d(long long n, int cap) {
+    const long long g = (n + 255) / 256;
+    return (int)(g < cap ? g : cap);
+}
+
+// ---------------------------------------------------------------------------------------
+// the training step of PhysicsVAE: what pvae.hip, pvae_net.hip, pvae_step.hip, pvae_lookahead.hip and pvae_infer.hip
+// call in one another
+// ---------------------------------------------------------------------------------------
+inline bool g_look_pair = true, g_rollout_fused = true;          // process-wide options "look_pair", "rollout_fused"
+
+// ---- pvae.hip: staging ----
+// Arguments of a staging job into the CURRENT (alt == false) or the alternate set of input panels; `steps`: time steps to
+// stage (the ctx's lookahead for training batches, 1 for rollout inference)
+StageArgs stage_args(const pvae_ctx* c, long long first_window, const float* x, const float* y, int rows, bool from_set,
+                     int steps, bool alt);
+int stage(pvae_ctx* c, long long first_window, const float* x, const float* y, int rows, bool from_set, hipStream_t st, int steps);
+void flip_stage_panels(pvae_ctx* c);
+RowMap row_map(const pvae_ctx* c, int64_t first_window, int rows);
+void plan_touch(pvae_ctx* c, int64_t next_first, int next_rows);
+int copy_cols_launch(const float* src, int lds_, int src_col0, float* dst, int ldd, int dst_col0, int rows, int ncols,
+                     hipStream_t st);                           // dst[r][dst_col0 + c] = src[r][src_col0 + c]
+
+// ---- pvae_net.hip: one stack ----
+struct FwdTail {              // what the output layer's epilogue does besides bias
+    const EpiMse* mse = nullptr;      // fused MSE loss + gradient
+    float* out2 = nullptr;            // or: copy the first n2 output columns to out2[:, off2:]
+    int ld2 = 0, off2 = 0, n2 = 0;
+    const ProSampler* pro0 = nullptr; // layer 0 forms the sampler's z columns of its input itself (decoder, joint step)
+    const XSrc* xs0 = nullptr;        // layer 0 gathers its input rows from the demonstration set (direct steps)
+    const ProCols* cols0 = nullptr;   // ... and copies these columns over its input tile (world model: a_t / a_hat)
+};
+// `row0`: first row of the time-step block to run on (0 unless lookahead > 1)
+int forward_net(pvae_ctx* c, int n, int rows_pad, hipStream_t st, const FwdTail& tail = FwdTail(), int64_t row0 = 0);
+// a_hat += range * (the helper's output), also into the world model's action columns; row blocks `row0` / `wm_row0`
+int helper_add_launch(pvae_ctx* c, int rows, int64_t row0, int64_t wm_row0, hipStream_t st);
+int sampler_grid(const pvae_ctx* c, int rows_pad);
+int64_t z_panel(const pvae_ctx* c);
+int launch_sampler(pvae_ctx* c, const float* te_out, int ldte, const float* eps, float* eps_used, float* md_in, int ld_md,
+                   int rows, int rows_pad, int noise, unsigned long long seed, unsigned long long offset, float* partial,
+                   float* z_dense, const float* mu_p, int ldmp, hipStream_t st);
+bool sampler_folds(const pvae_ctx* c, int rows);
+XSrc xsrc_of(const pvae_ctx* c, int net, int phase, bool with_s1, int rows);
+// A backward pass is a list of stages = launches in stream order.  `ready_*` names the slice of
+// the gradient arena that is final once the stage has run (data-parallel callers start that
+// slice's all-reduce right away, while later stages execute).
+struct Stage {
+    std::function<int()> run;
+    int64_t ready_off = 0, ready_cnt = 0;
+    int net = -1;
+};
+typedef std::vector<Stage> Plan;
+enum { kTakeAll = 0, kTakeSmall = 1 };
+AdamPair take_pending(pvae_ctx* c, int how = kTakeAll);
+int flush_pending_adam(pvae_ctx* c, hipStream_t st);
+int adam_flat_launch(float* p, const float* g, float* m, float* v, long long n4, const AdamScalars& s, hipStream_t st);
+// What the input-gradient launch of a stack's FIRST layer does with its result (lookahead 1):
+// nothing special (store the panel), or form the gradient seed of the stack that produced those
+// input columns in its epilogue (pvae_gemm.h: EpiActionSeed / EpiSamplerSeed).
+// Columns [c0, c0 + n) of a first-layer input gradient, widened to whole 32-column tiles: the only
+// part of that panel a gradient seed reads, so the only part its launch contracts.
+struct SeedWindow { int lo, width; };
+static inline SeedWindow seed_window(int c0, int n) {
+    const int lo = c0 & ~31;
+    return SeedWindow{lo, pad32(c0 + n) - lo};
+}
+struct InputSeed {
+    int kind = 0;                      // 0 none, 1 action seed (world model -> decoder), 2 sampler seed (decoder -> encoder)
+    EpiActionSeed a;
+    EpiSamplerSeed s;
+};
+// A weight-gradient launch handed from one stack's plan to the next one's first input-gradient
+// launch, so the two go out as ONE horizontally fused launch across the stack boundary.
+struct DgradArgs {
+    const float* dZ; int ldz; const float* W; int ldw; const float* mask; int ldm; float* dX; int ldo;
+    int M, Kin, Nd;
+    double flops;
+    int act = 1;          // act_grad code of the layer behind `mask`
+};
+struct CarriedWgrad {
+    bool valid = false;
+    std::function<int(const DgradArgs&)> run_with_dgrad;
+    int64_t ready_off = 0, ready_cnt = 0;
+    int net = -1;
+};
+void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool input_grad, const pvae_step_params* sp, bool fused,
+                       hipStream_t st, const LossFinal* fold, Plan& plan, const InputSeed* seed = nullptr,
+                       CarriedWgrad* carry_out = nullptr, const CarriedWgrad* carry_in = nullptr,
+                       bool wide_follows_layer0 = false);
+
+// ---- pvae_step.hip: the step's shape, and the glue launches the unroll shares with the lookahead-1 plan ----
+// Everything a step needs that is a pure function of (phase, rows, step params).
+struct StepShape {
+    bool fold_sampler;
+    int rows_pad, wm_tiles, gridz, nparts_a;
+    bool seed_action, seed_sampler;   // stack hand-overs fused into input-gradient epilogues (plan_backward)
+    int l1;                    // loss_kind of the three reconstruction terms
+    float gs;                  // d(mean loss)/d(residual) factor: 2 for MSE, 1 for L1
+    float Bg;
+    bool cyc_grad, kl_active;
+    LossFinal lf;
+};
+int add_cols_launch(float* dst, int ldd, int rows, int n, const float* s0, int l0, const float* s1, int l1, const float* s2,
+                    int l2, const float* s3, int l3, hipStream_t st);                 // dst[r][c] += s0[r][c] (+ s1 + s2 + s3)
+// on the row block `row0` of time step t (`wm_row0`: the world model's predicted-action block)
+int helper_seed_launch(pvae_ctx* c, int rows, int64_t row0, hipStream_t st);
+int action_loss_launch(pvae_ctx* c, int rows, int t, int64_t row0, int64_t wm_row0, int nparts, float grad_scale, int l1,
+                       bool backward, bool extra, hipStream_t st);
+int reparam_bwd_launch(pvae_ctx* c, int rows, int64_t row0, float kl_scale, hipStream_t st);
+
+// ---- pvae_lookahead.hip ----
+int run_forward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_params* sp, const float* eps, bool backward,
+                         const StepShape& S, hipStream_t st);
+void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_params* sp, bool backward, bool fused,
+                            const StepShape& S, hipStream_t st, Plan& plan);
+
+// ---- pvae_exchange.hip, called by the data-parallel step in pvae_step.hip ----
 struct Bucket { int64_t off, cnt; };
 int64_t auto_bucket_bytes(const pvae_ctx* c, int phase);
 std::vector<Bucket> exchange_buckets(const pvae_ctx* c, int net);
@@ -437,8 +655,8 @@ int check_prepare(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pva
     return check_gae_scratch(scratch, scratch_bytes, ro->n_segs);
 }
 
-// ---- the PPO learner step of PhysicsVAE (pvae_ppo.hip) and what it runs of pvae.hip and pvae_fc.hip ----
-// pvae.hip: a stack's forward on the panels as they are, the sampler into the decoder's input panel, a stack's backward plan
+// ---- the PPO learner step of PhysicsVAE (pvae_ppo.hip) and what it runs of pvae_infer.hip and pvae_fc.hip ----
+// pvae_infer.hip: a stack's forward on the panels as they are, the sampler into the decoder's input panel, a stack's backward plan
 // with a gradient store into `grad_arena` (arena layout); `launches` counts what went out
 void ppo_enter(pvae_ctx* c, int rows);
 int ppo_forward_net(pvae_ctx* c, int net, int rows, hipStream_t st, int* launches);

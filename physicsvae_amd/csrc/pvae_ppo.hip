@@ -1,7 +1,7 @@
 // pvae_ppo.hip -- the PPO learner step of PhysicsVAE (include/pvae.h pvae_ppo_*; `run: DDPPO`, `custom_model: physics_vae`):
 // one minibatch update -- rmt:742-771 without the world model, the clipped-surrogate loss, backward, Adam -- as ONE
 // library call with no host synchronisation.  It joins launches that exist: the stacks' forward and backward plans of
-// pvae.hip, the stack set's grouped launches (the value branch, pvae_fc.hip) and the learner's model-independent launches
+// pvae_net.hip (through pvae_infer.hip's hooks), the stack set's grouped launches (the value branch, pvae_fc.hip) and the learner's model-independent launches
 // (loss head, Adam + stats, evaluate epilogue, GAE: pvae_ppo_core.hip).  What is PhysicsVAE's own stays here: the copy-in
 // into three input panels, the sampler's backward, and the order of the launches.  No forward is
 // recomputed: the encoder's, the decoder's and the value stack's panels stay live from the forward to their backward
@@ -40,7 +40,7 @@ ppo_copy_in_kernel(PpoCopyIn a) {
     }
 }
 
-// Backward of the sampler on the panels (sampler_bwd_kernel's arithmetic, pvae.hip; autograd of rmt:734-740, no KL term:
+// Backward of the sampler on the panels (sampler_bwd_kernel's arithmetic, pvae_infer.hip; autograd of rmt:734-740, no KL term:
 // the PPO loss has none): dz = the z columns of the decoder's input gradient, mu_logvar = the encoder's output panel,
 // d_mu_logvar -> the encoder's output gradient panel, written over its whole [rows_pad][ld] block (zeros in pad rows / columns).
 //   N(mu, s^2):  dmu = dz, dlv = dz eps exp(lv / 2) / 2 (noise = 0: z = mu, dlv = 0);   no prior (False): de = dz
