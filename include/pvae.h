@@ -217,7 +217,8 @@ int pvae_set_direct(pvae_ctx* ctx, int on);
  * the tests and the A/B scripts).  Defaults are the production values.
  *   ctx == NULL, process-wide kernel geometry:  "ws64" "ws6464" "ws6464_rows" "pair64" "dgrad16" (0 / 1), "wgrad32" (0 / 1 / 2),
  *       "krot" "rowxcd" (0 / 1, experiments, default 0), "look_pair" "rollout_fused" (0 / 1),
- *       "fc_per_stack" (0 / 1: the stack set's launches one per stack instead of one per layer depth, see pvae_fc_* below)
+ *       "fc_per_stack" (0 / 1: the stack set's launches one per stack instead of one per layer depth, see pvae_fc_* below),
+ *       "p2p_timeout_ms" (> 0: the bounded waits of the stack sets' PPO gradient exchange, pvae_fc_ppo_peer_*)
  *   ctx, that context's schedule:  "pair" "defer_adam" "same_layer" "fold_sampler" (0 / 1), "direct" (= pvae_set_direct),
  *       "p2p_timeout_ms" (> 0), "p2p_selftest_flags_only" (0 / 1), "server_mailbox" (0 auto, 1 pinned host memory, 2 device)
  * Every variant gives the same bits as the default (held by tests/test_gpu_shapes.py, test_gpu_fuzz.py).  -1: unknown name. */
@@ -860,6 +861,62 @@ int pvae_ppo_sgd(pvae_ctx* ctx, const pvae_fc_ppo_batch* batch, const int32_t* p
                  float* stats_out, void* stream);
 int pvae_ppo_launches(pvae_ctx* ctx, int32_t* per_step);
 int pvae_ppo_sizeof(int which);
+
+/* ---- Gradient exchange between workers inside the PPO learners (`run: DDPPO`, `num_workers: 8`) ----------------------------
+ * Both training specs that use these models are decentralised PPO with eight workers (data/spec/loco/loco_imitation.yaml:1,35;
+ * data/spec/loco/loco_runtime_physics_vae.yaml:1,36): every worker runs the learner on its own train batch, and after every
+ * minibatch's backward pass the workers average their gradients before each takes the -- then identical -- Adam step.  The
+ * reference leaves that to RLlib; there is no reference counterpart of what follows.  The rule, with N workers and g_r the
+ * gradient worker r's own minibatch gives (the mean over ITS rows, as the step computes it):
+ *     g = (((g_0 + g_1) + g_2) + ... + g_{N-1}) * float32(1 / N)
+ * in float32, in rank order, element by element over every trained segment and the state-independent log-std vector; N = 1
+ * gives g_0 bit for bit.  Minibatches of different row counts give the mean of the workers' means (as DDP does), not the
+ * row-weighted mean.  The stats stay each worker's own.  Every worker must issue the same number of steps.  The rank does
+ * not enter the Philox stream: distinct draws per worker come from distinct seeds.
+ *
+ * The step in two halves, for a transport outside the library (torch.distributed: nccl between GPUs, gloo anywhere):
+ *   pvae_fc_ppo_grad / pvae_ppo_grad     everything *_ppo_step does before its Adam launch, with the step's arguments: the
+ *                         gradient lies in the bound gradient buffers; then the five stats are finished into stats_out and,
+ *                         log_std_kind 1, the log-std vector's gradient is written to ls_grad[k] (device; may be NULL for the
+ *                         other kinds) -- the value the Adam launch's last workgroup forms.  No parameter, no moment moves.
+ *   pvae_fc_ppo_apply / pvae_ppo_apply   Adam over the trained segments (params->train_mask, adam_t, log_std_kind as the step's)
+ *                         on grad_scale * gradient, the product formed in float32 element by element, and on the log-std
+ *                         vector from grad_scale * ls_grad.  grad + apply(1.0) is the step, bit for bit.
+ * Neither half ever exchanges.
+ *
+ * The exchange inside the library, peer-mapped (as pvae_p2p_*; no RCCL form): every worker maps its peers' gradient
+ * buffers -- a stack set's gradient arena; PhysicsVAE's, the one of pvae_ppo_bind and the value stack set's -- and a flag
+ * block whose tail holds the k floats of the log-std gradient.  Parameters and moments are not mapped: every rank reads
+ * every rank's gradient ((N - 1) x the gradient bytes come in over the links per step) and updates its own replica whole,
+ * so moments stay complete on every rank and nobody writes into a peer's parameters.  While an exchange is open,
+ * *_ppo_step and *_ppo_sgd issue the exchanged form of their Adam launch -- ONE launch, the launch count unchanged: ready
+ * flags, a bounded wait for the peers', the N gradients read with system-scope loads and summed in rank order, Adam on the
+ * local parameters, the log-std vector from the N slots, a "done" hand-shake so that the next step's backward may overwrite
+ * the buffers.  A wait that gives up ("p2p_timeout_ms"; for stack sets the process-wide option of that name) aborts this
+ * rank's update -- nothing moves -- and is counted.  With world 1 the exchanged launch gives the plain step's bits.
+ *   *_peer_export   writes this worker's blob (PVAE_P2P_BLOB_BYTES: IPC handles, offsets, sizes); zeroes the flag block.
+ *                   *_ppo_bind must have been called, and the buffers must come from hipMalloc.
+ *   *_peer_open     blobs: world x PVAE_P2P_BLOB_BYTES in rank order (an exchange of the blobs between the workers is the
+ *                   barrier between export and open); world <= PVAE_P2P_MAX_RANKS, world 1 is legal.  Ends with an attach-time
+ *                   check, collective and bounded (< 1 s per wait): flag delivery both ways, and a gradient line read
+ *                   remotely, overwritten by its owner and read again must not be stale.  On failure nothing stays open.
+ *   *_peer_close    unmaps the peers (after every worker's last step has completed); export + open again starts from clean flags.
+ *   *_peer_status   rank and world (0, 0 when not open), and the waits that gave up so far (synchronises `stream`). */
+int pvae_fc_ppo_grad(pvae_fc* fc, const pvae_fc_ppo_batch* batch, const int32_t* index, int64_t first, int32_t rows,
+                     const pvae_fc_ppo_params* params, float* stats_out, float* ls_grad, void* stream);
+int pvae_fc_ppo_apply(pvae_fc* fc, const pvae_fc_ppo_params* params, float grad_scale, const float* ls_grad, void* stream);
+int pvae_ppo_grad(pvae_ctx* ctx, const pvae_fc_ppo_batch* batch, const int32_t* index, int64_t first, int32_t rows,
+                  const pvae_fc_ppo_params* params, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                  float* stats_out, float* ls_grad, void* stream);
+int pvae_ppo_apply(pvae_ctx* ctx, const pvae_fc_ppo_params* params, float grad_scale, const float* ls_grad, void* stream);
+int pvae_fc_ppo_peer_export(pvae_fc* fc, void* blob);
+int pvae_fc_ppo_peer_open(pvae_fc* fc, int rank, int world, const void* blobs);
+int pvae_fc_ppo_peer_close(pvae_fc* fc);
+int pvae_fc_ppo_peer_status(pvae_fc* fc, int* rank, int* world, uint32_t* timeouts, void* stream);
+int pvae_ppo_peer_export(pvae_ctx* ctx, void* blob);
+int pvae_ppo_peer_open(pvae_ctx* ctx, int rank, int world, const void* blobs);
+int pvae_ppo_peer_close(pvae_ctx* ctx);
+int pvae_ppo_peer_status(pvae_ctx* ctx, int* rank, int* world, uint32_t* timeouts, void* stream);
 
 /* ---- Train-batch preparation for PhysicsVAE: evaluate, bootstrap, GAE, standardisation -------------------------------
  * "Train-batch preparation for the PPO learner" above, with PhysicsVAE as the policy: from a device-resident rollout to the

@@ -225,6 +225,19 @@ _SIGS = {
     "pvae_ppo_sgd": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.c_int32, C.POINTER(FcPpoParams), _P, C.c_int,
                                C.c_uint64, C.c_uint64, _P, _P]),
     "pvae_ppo_launches": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "pvae_fc_ppo_grad": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int64, C.c_int32, C.POINTER(FcPpoParams), _P, _P, _P]),
+    "pvae_fc_ppo_apply": (C.c_int, [_P, C.POINTER(FcPpoParams), C.c_float, _P, _P]),
+    "pvae_ppo_grad": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int64, C.c_int32, C.POINTER(FcPpoParams), _P, C.c_int,
+                                C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "pvae_ppo_apply": (C.c_int, [_P, C.POINTER(FcPpoParams), C.c_float, _P, _P]),
+    "pvae_fc_ppo_peer_export": (C.c_int, [_P, _P]),
+    "pvae_fc_ppo_peer_open": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "pvae_fc_ppo_peer_close": (C.c_int, [_P]),
+    "pvae_fc_ppo_peer_status": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), _P]),
+    "pvae_ppo_peer_export": (C.c_int, [_P, _P]),
+    "pvae_ppo_peer_open": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "pvae_ppo_peer_close": (C.c_int, [_P]),
+    "pvae_ppo_peer_status": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), _P]),
     "pvae_ppo_sizeof": (C.c_int, [C.c_int]),
     "pvae_ppo_evaluate": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(FcPrepared),
                                     _P]),
@@ -279,6 +292,7 @@ PROCESS_OPTIONS = {
     "PVAE_WS6464": ("ws6464", _flag), "PVAE_WS6464_ROWS": ("ws6464_rows", _flag), "PVAE_PAIR64": ("pair64", _flag),
     "PVAE_DGRAD16": ("dgrad16", _flag), "PVAE_WGRAD32": ("wgrad32", int), "PVAE_LOOK_PAIR": ("look_pair", _flag),
     "PVAE_ROLLOUT_FUSED": ("rollout_fused", _flag), "PVAE_FC_PER_STACK": ("fc_per_stack", _flag),
+    "PVAE_P2P_TIMEOUT_MS": ("p2p_timeout_ms", int),         # (the stack sets' PPO gradient exchange; per context: below)
 }
 CONTEXT_OPTIONS = {
     "PVAE_PAIR": ("pair", _flag), "PVAE_DEFER_ADAM": ("defer_adam", _flag), "PVAE_SAME_LAYER": ("same_layer", _flag),

@@ -159,6 +159,7 @@ int pvae_set_option(pvae_ctx* c, const char* name, int64_t value) {
         else if (k == "look_pair") g_look_pair = v != 0;
         else if (k == "rollout_fused") g_rollout_fused = v != 0;
         else if (k == "fc_per_stack") g_fc_per_stack = v != 0;
+        else if (k == "p2p_timeout_ms") { if (value > 0) g_ppo_peer_timeout_ticks = (long long)value * 100000ll; }
         else return fail(-1, "unknown process-wide option '%s'", name);
         return 0;
     }
@@ -181,6 +182,7 @@ void pvae_destroy(pvae_ctx* ctx) {
         if (ctx->p2p.flags) (void)hipFree(ctx->p2p.flags);
         if (ctx->p2p.staging) (void)hipFree(ctx->p2p.staging);
         if (ctx->p2p.self_buf) (void)hipFree(ctx->p2p.self_buf);
+        ppo_peer_free(ctx->ppo.peers);
         server_free(ctx);
     }
     delete ctx;

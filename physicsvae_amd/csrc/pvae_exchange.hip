@@ -36,16 +36,7 @@ struct P2pArgs {
     AdamScalars s;
 };
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
-__device__ inline unsigned p2p_ld(const unsigned* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ inline void p2p_st(unsigned* q, unsigned x) { __hip_atomic_store(q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ inline bool p2p_wait(const unsigned* flag, unsigned epoch, long long timeout, unsigned* err) {
-    const long long t0 = wall_clock64();
-    while ((int)(p2p_ld(flag) - epoch) < 0) {
-        __builtin_amdgcn_s_sleep(8);
-        if (wall_clock64() - t0 > timeout) { atomicAdd(err, 1u); return false; }
-    }
-    return true;
-}
+// (p2p_ld / p2p_st / p2p_wait: pvae_internal.h -- the PPO learners' exchanged Adam launch waits with them too)
 template <int N>
 __global__ void __launch_bounds__(256) p2p_exchange_kernel(P2pArgs a) {
     unsigned* mine = a.f[a.me];
@@ -840,3 +831,237 @@ int pvae_allreduce_grads(pvae_ctx* c, int64_t offset, int64_t count, void* strea
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// The PPO learners' gradient exchange between workers: set-up (include/pvae.h "Gradient exchange between workers"; the
+// launch is ppo_adam_exchange_kernel, pvae_ppo_core.hip).  What pvae_p2p_export / open / close / status do for the
+// trainer's arenas, for a learner's gradient arena(s): a stack set has one, PhysicsVAE its own and the value stack set's.
+// Only gradients and the flag block are mapped -- nobody writes into a peer's parameters here, so of pvae_p2p_selftest's
+// checks the flag part and the gradient half of the arena part apply, and ppo_peer_open ends with them.
+// ---------------------------------------------------------------------------------------
+struct PpoPeerBlob {                                      // PVAE_P2P_BLOB_BYTES on the wire
+    uint32_t magic, abi;
+    int32_t n_arenas, k;
+    int64_t floats[kPpoPeerArenas];
+    hipIpcMemHandle_t h[kPpoPeerArenas + 1];              // allocations holding the gradient arenas, then the flag block
+    int64_t off[kPpoPeerArenas + 1];                      // byte offset of the buffer inside its allocation
+};
+static_assert(sizeof(PpoPeerBlob) <= PVAE_P2P_BLOB_BYTES, "blob layout");
+constexpr uint32_t kPpoPeerMagic = 0x50504756u;           // "VGPP"
+constexpr int kPpoSelfLine = 32, kPpoSelfFloats = PVAE_P2P_MAX_RANKS * kPpoSelfLine;    // 8 lines of 128 bytes, one per reader
+
+struct PpoSelfArgs {
+    unsigned* f[PVAE_P2P_MAX_RANKS];
+    float* g[PVAE_P2P_MAX_RANKS];       // first kPpoSelfFloats floats of gradient arena 0 (null: flags only)
+    float* save;
+    int me, n;
+    unsigned token;
+    long long timeout_ticks;
+};
+__device__ inline float ppo_self_pat(unsigned token, int src, int dst, int j, int round) {
+    return (float)(((token & 0xFFFFu) * 131u + (unsigned)src * 1021u + (unsigned)dst * 67u + (unsigned)round * 4099u) % 65521u) +
+           (float)j * 0.0078125f;                                     // exactly representable, distinct per (src, dst, j, round)
+}
+// one wave.  round 0: save the region, write pattern A (plain stores, as the backward launches write gradients);
+// round 1: pattern B; round 2: restore
+__global__ void __launch_bounds__(64) ppo_peer_self_fill_kernel(PpoSelfArgs s, int round) {
+    const int lane = threadIdx.x, me = s.me;
+    v4f* mine = reinterpret_cast<v4f*>(s.g[me]) + lane;
+    if (round == 0) reinterpret_cast<v4f*>(s.save)[lane] = *mine;
+    if (round == 2) { *mine = reinterpret_cast<const v4f*>(s.save)[lane]; return; }
+    v4f a;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = ppo_self_pat(s.token, me, (4 * lane + e) / kPpoSelfLine, (4 * lane + e) % kPpoSelfLine, round);
+    *mine = a;
+}
+// one wave, behind a fill launch.  round 0 also proves the flag block: a 4-word record written into every peer's block,
+// flag delivery both ways, the record the peer wrote here, and the own record read back remotely.  Both rounds: tell the
+// peers "my pattern is final", wait for theirs, read my line of every peer's region with the exchange's loads; round 1
+// would return pattern A from a stale line.  Then nobody goes on (to overwrite or restore) while a peer may still read.
+__global__ void __launch_bounds__(64) ppo_peer_self_check_kernel(PpoSelfArgs s, int round) {
+    unsigned* mine = s.f[s.me];
+    const int lane = threadIdx.x, me = s.me, n = s.n;
+    const bool peer = lane < n && lane != me;
+    const int sig = round == 0 ? kPpoPeerGradA : kPpoPeerGradB, fin = round == 0 ? kPpoPeerSelf : kPpoPeerFin;
+    unsigned bad = 0;
+    if (peer) {
+        unsigned* theirs = s.f[lane];
+        if (round == 0)
+            for (int wd = 0; wd < 4; ++wd)
+                p2p_st(theirs + kPpoPeerPayload + me * 4 + wd, wd == 0 ? s.token : wd == 1 ? (unsigned)me : wd == 2 ? (unsigned)lane : 0xC0FFEEu);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        p2p_st(theirs + sig + me, s.token);
+        p2p_wait(mine + sig + lane, s.token, s.timeout_ticks, mine + kPpoPeerErr);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        if (round == 0) {
+            const bool got = p2p_ld(mine + kPpoPeerPayload + lane * 4) == s.token && p2p_ld(mine + kPpoPeerPayload + lane * 4 + 1) == (unsigned)lane &&
+                             p2p_ld(mine + kPpoPeerPayload + lane * 4 + 2) == (unsigned)me && p2p_ld(mine + kPpoPeerPayload + lane * 4 + 3) == 0xC0FFEEu;
+            const bool back = p2p_ld(theirs + kPpoPeerPayload + me * 4) == s.token && p2p_ld(theirs + kPpoPeerPayload + me * 4 + 3) == 0xC0FFEEu;
+            bad += !got + !back;
+        }
+    }
+    __builtin_amdgcn_s_barrier();
+    for (int q = 0; q < n && s.g[me]; ++q) {
+        if (q == me || lane >= kPpoSelfLine / 4) continue;
+        const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(s.g[q], 0, kPpoSelfFloats * 4, 0x00020000);
+        const v4f g = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rg, (unsigned)((me * kPpoSelfLine + 4 * lane) * 4), 0, 17));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bad += g[e] != ppo_self_pat(s.token, q, me, 4 * lane + e, round);
+    }
+    if (bad) atomicAdd(mine + kPpoPeerErr, bad);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (peer) {
+        p2p_st(s.f[lane] + fin + me, s.token);
+        p2p_wait(mine + fin + lane, s.token, s.timeout_ticks, mine + kPpoPeerErr);
+    }
+}
+
+void ppo_peer_free(PpoPeers& P) {
+    ppo_peer_close(P);
+    if (P.flags) (void)hipFree(P.flags);
+    if (P.self_buf) (void)hipFree(P.self_buf);
+    P.flags = nullptr; P.self_buf = nullptr; P.flag_bytes = 0;
+}
+
+int ppo_peer_export(PpoPeers& P, float* const* arenas, const long long* floats, int n_arenas, int k, void* blob) {
+    if (!blob) return fail(-1, "null blob");
+    if (P.open) return fail(-2, "the PPO gradient exchange is open: close it before exporting again");
+    const size_t need = ((size_t)kPpoPeerLs + (size_t)(k + 3) / 4 * 4) * sizeof(unsigned);
+    if (P.flags && P.flag_bytes < need) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(P.flags); P.flags = nullptr; }
+    if (!P.flags) {
+        HIP_TRY(hipExtMallocWithFlags((void**)&P.flags, need, hipDeviceMallocUncached));
+        P.flag_bytes = need;
+    }
+    // every set-up starts from a zeroed flag block (epochs restart at 0 in ppo_peer_open): see pvae_p2p_export
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(P.flags, 0, P.flag_bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    P.selftests = 0;
+    PpoPeerBlob b;
+    memset(&b, 0, sizeof(b));
+    b.magic = kPpoPeerMagic; b.abi = PVAE_ABI_VERSION; b.n_arenas = n_arenas; b.k = k;
+    void* ptrs[kPpoPeerArenas + 1] = {};
+    for (int r = 0; r < n_arenas; ++r) { ptrs[r] = arenas[r]; b.floats[r] = floats[r]; }
+    ptrs[kPpoPeerArenas] = P.flags;
+    for (int r = 0; r <= kPpoPeerArenas; ++r) {
+        if (!ptrs[r]) continue;
+        const char* what = r == kPpoPeerArenas ? "flag block" : "gradient arena";
+        void* base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, ptrs[r]) != hipSuccess || !base)
+            return fail(-10, "%s: not inside a hipMalloc allocation", what);
+        hipError_t e = hipIpcGetMemHandle(&b.h[r], base);
+        if (e != hipSuccess)
+            return fail(-10, "hipIpcGetMemHandle(%s): %s (the arenas must come from hipMalloc -- PyTorch's default "
+                             "caching allocator, not expandable segments -- and HSA_ENABLE_IPC_MODE_LEGACY=0 must be set "
+                             "where the driver only supports dmabuf IPC)", what, hipGetErrorString(e));
+        b.off[r] = (char*)ptrs[r] - (char*)base;
+    }
+    P.n_arenas = n_arenas; P.k = k;
+    for (int r = 0; r < n_arenas; ++r) P.floats[r] = floats[r];
+    memset(blob, 0, PVAE_P2P_BLOB_BYTES);
+    memcpy(blob, &b, sizeof(b));
+    return 0;
+}
+
+int ppo_peer_close(PpoPeers& P) {
+    for (int q = 0; q < PVAE_P2P_MAX_RANKS; ++q)
+        for (int r = 0; r <= kPpoPeerArenas; ++r) {
+            if (!P.mapped[q][r]) continue;
+            bool dup = false;                             // one mapping may serve two buffers of a peer
+            for (int j = 0; j < r; ++j) dup = dup || P.mapped[q][j] == P.mapped[q][r];
+            if (!dup) (void)hipIpcCloseMemHandle(P.mapped[q][r]);
+        }
+    memset(P.mapped, 0, sizeof(P.mapped));
+    memset(P.arena, 0, sizeof(P.arena)); memset(P.peer_flags, 0, sizeof(P.peer_flags));
+    P.open = false; P.world = 0; P.rank = 0;
+    return 0;
+}
+
+static int ppo_peer_selftest(PpoPeers& P, long long timeout_ticks) {
+    PpoSelfArgs s;
+    memset(&s, 0, sizeof(s));
+    const bool arenas = P.world > 1 && P.floats[0] >= kPpoSelfFloats;
+    for (int q = 0; q < P.world; ++q) { s.f[q] = P.peer_flags[q]; s.g[q] = arenas ? P.arena[0][q] : nullptr; }
+    if (arenas && !P.self_buf) HIP_TRY(hipMalloc((void**)&P.self_buf, kPpoSelfFloats * sizeof(float)));
+    s.save = P.self_buf; s.me = P.rank; s.n = P.world;
+    s.timeout_ticks = timeout_ticks < 100000000ll ? timeout_ticks : 100000000ll;       // at most 1 s
+    s.token = 0x5E1F0000u + (++P.selftests) * 16u + (unsigned)P.world;
+    hipStream_t st = nullptr;
+    uint32_t before = 0, after = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&before, P.flags + kPpoPeerErr, sizeof(before), hipMemcpyDeviceToHost));
+    for (int round = 0; round < 2; ++round) {
+        if (arenas) hipLaunchKernelGGL(ppo_peer_self_fill_kernel, dim3(1), dim3(64), 0, st, s, round);
+        hipLaunchKernelGGL(ppo_peer_self_check_kernel, dim3(1), dim3(64), 0, st, s, round);
+    }
+    if (arenas) hipLaunchKernelGGL(ppo_peer_self_fill_kernel, dim3(1), dim3(64), 0, st, s, 2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&after, P.flags + kPpoPeerErr, sizeof(after), hipMemcpyDeviceToHost));
+    if (after != before) {
+        HIP_TRY(hipMemcpy(P.flags + kPpoPeerErr, &before, sizeof(before), hipMemcpyHostToDevice));
+        return fail(-22, "PPO gradient exchange: attach-time check failed on rank %d: %u flag(s) / record(s) / gradient word(s) "
+                         "from peers wrong, stale or missing", P.rank, after - before);
+    }
+    return 0;
+}
+
+int ppo_peer_open(PpoPeers& P, float* const* arenas, int rank, int world, const void* blobs, long long timeout_ticks) {
+    if (!blobs) return fail(-1, "null blobs");
+    if (world < 1 || world > PVAE_P2P_MAX_RANKS || rank < 0 || rank >= world)
+        return fail(-1, "rank %d / world %d outside [0, %d]", rank, world, PVAE_P2P_MAX_RANKS);
+    if (P.open) return fail(-2, "the PPO gradient exchange is already open");
+    if (!P.flags) return fail(-2, "export first");
+    const char* all = (const char*)blobs;
+    for (int q = 0; q < world; ++q) {
+        PpoPeerBlob b;
+        memcpy(&b, all + (size_t)q * PVAE_P2P_BLOB_BYTES, sizeof(b));
+        bool ok = b.magic == kPpoPeerMagic && b.abi == PVAE_ABI_VERSION && b.n_arenas == P.n_arenas && b.k == P.k;
+        for (int r = 0; ok && r < P.n_arenas; ++r) ok = b.floats[r] == P.floats[r];
+        if (!ok) {
+            ppo_peer_close(P);
+            return fail(-1, "blob of rank %d does not describe a matching learner", q);
+        }
+        if (q == rank) {
+            for (int r = 0; r < P.n_arenas; ++r) P.arena[r][q] = arenas[r];
+            P.peer_flags[q] = P.flags;
+            continue;
+        }
+        void* base[kPpoPeerArenas + 1] = {};
+        for (int r = 0; r <= kPpoPeerArenas; ++r) {
+            if (r < kPpoPeerArenas && r >= P.n_arenas) continue;
+            for (int j = 0; j < r; ++j)                   // two buffers inside one allocation: open it once
+                if (base[j] && memcmp(&b.h[j], &b.h[r], sizeof(b.h[r])) == 0) base[r] = base[j];
+            if (!base[r]) {
+                hipError_t e = hipIpcOpenMemHandle(&base[r], b.h[r], hipIpcMemLazyEnablePeerAccess);
+                if (e != hipSuccess) {
+                    ppo_peer_close(P);
+                    return fail(-10, "hipIpcOpenMemHandle(rank %d, buffer %d): %s", q, r, hipGetErrorString(e));
+                }
+            }
+            P.mapped[q][r] = base[r];
+            if (r < kPpoPeerArenas) P.arena[r][q] = (float*)((char*)base[r] + b.off[r]);
+            else P.peer_flags[q] = (unsigned*)((char*)base[r] + b.off[r]);
+        }
+    }
+    P.rank = rank; P.world = world; P.epoch = 0; P.open = true;
+    const int rc = ppo_peer_selftest(P, timeout_ticks);
+    if (rc) ppo_peer_close(P);                            // (the error text stays: closing reports none)
+    return rc;
+}
+
+int ppo_peer_status(const PpoPeers& P, int* rank, int* world, uint32_t* timeouts, hipStream_t st) {
+    if (rank) *rank = P.open ? P.rank : 0;
+    if (world) *world = P.open ? P.world : 0;
+    if (timeouts) {
+        *timeouts = 0;
+        if (P.flags) {
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpy(timeouts, P.flags + kPpoPeerErr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}

@@ -33,6 +33,7 @@ struct pvae_fc {
     float* log_std_v = nullptr;
     int ppo_launches = 0;
     int eval_launches = 0, gae_launches = 0;      // pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate (pvae_fc_gae_launches)
+    PpoPeers peers;                               // the learner's gradient exchange between workers (pvae_fc_ppo_peer_*)
 };
 
 namespace {
@@ -515,9 +516,10 @@ int check_ppo(pvae_fc* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* 
     return 0;
 }
 
-// one minibatch (arguments checked by the caller)
-int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-             const pvae_fc_ppo_params* p, int adam_t, float* stats_out, hipStream_t st) {
+// The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
+// gradient arena (arguments checked by the caller); `launches` counts what went out
+int ppo_grad_half(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
+                  const pvae_fc_ppo_params* p, hipStream_t st, int* launches) {
     const FcLayout& L = c->L;
     const int mask = p->train_mask ? p->train_mask : (1 << L.S) - 1;
     Run r{c, st, rows, pad32(rows)};
@@ -551,34 +553,53 @@ int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long 
     }
     for (int s = 0; s < L.S; ++s) r.want[s] = (mask >> s) & 1;
     if ((rc = run_backward_layers<EpiGradStore>(r, false, c->grad, mask))) return rc;
-    {
-        // the trained stacks' parts of the arena, in arena order, adjacent ones merged
-        std::vector<std::pair<long long, long long>> seg;
-        auto add = [&](long long off, long long n) {
-            if (!seg.empty() && seg.back().first + seg.back().second == off) seg.back().second += n;
-            else seg.push_back({off, n});
-        };
-        for (int s = 0; s < L.S; ++s)
-            if ((mask >> s) & 1) add(L.stack[s][0].w_off, (long long)L.stack[s][0].n_out_pad * L.stack[s][0].ld);
-        for (int s = 0; s < L.S; ++s)
-            if ((mask >> s) & 1) add(L.stack[s][0].b_off, L.stack[s][0].n_out_pad);
-        for (int s = 0; s < L.S; ++s)
-            for (size_t i = 1; ((mask >> s) & 1) && i < L.stack[s].size(); ++i) {
-                add(L.stack[s][i].w_off, (long long)L.stack[s][i].n_out_pad * L.stack[s][i].ld);
-                add(L.stack[s][i].b_off, L.stack[s][i].n_out_pad);
-            }
-        PpoAdamSegs sg;
-        memset((void*)&sg, 0, sizeof(sg));
-        for (const auto& e : seg) {
-            if (sg.n == kAdamSegs) return fail(-3, "the trained parts of the arena form more than %d segments", kAdamSegs);
-            sg.p[sg.n] = c->params + e.first; sg.g[sg.n] = c->grad + e.first; sg.m[sg.n] = c->m + e.first; sg.v[sg.n] = c->v + e.first;
-            sg.n4[sg.n++] = e.second / 4;
+    *launches = r.launches;
+    return 0;
+}
+
+// the trained stacks' parts of the arena, in arena order, adjacent ones merged: what the Adam launch runs over
+int ppo_segments(pvae_fc* c, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
+    const FcLayout& L = c->L;
+    const int mask = p->train_mask ? p->train_mask : (1 << L.S) - 1;
+    std::vector<std::pair<long long, long long>> seg;
+    auto add = [&](long long off, long long n) {
+        if (!seg.empty() && seg.back().first + seg.back().second == off) seg.back().second += n;
+        else seg.push_back({off, n});
+    };
+    for (int s = 0; s < L.S; ++s)
+        if ((mask >> s) & 1) add(L.stack[s][0].w_off, (long long)L.stack[s][0].n_out_pad * L.stack[s][0].ld);
+    for (int s = 0; s < L.S; ++s)
+        if ((mask >> s) & 1) add(L.stack[s][0].b_off, L.stack[s][0].n_out_pad);
+    for (int s = 0; s < L.S; ++s)
+        for (size_t i = 1; ((mask >> s) & 1) && i < L.stack[s].size(); ++i) {
+            add(L.stack[s][i].w_off, (long long)L.stack[s][i].n_out_pad * L.stack[s][i].ld);
+            add(L.stack[s][i].b_off, L.stack[s][i].n_out_pad);
         }
-        if ((rc = ppo_adam_launch(sg, p, adam_t, rows, b->k, c->scratch, colsum, c->log_std, c->log_std_m, c->log_std_v, stats_out, st)))
-            return rc;
-        ++r.launches;
+    memset((void*)&sg, 0, sizeof(sg));
+    for (const auto& e : seg) {
+        if (sg.n == kAdamSegs) return fail(-3, "the trained parts of the arena form more than %d segments", kAdamSegs);
+        sg.p[sg.n] = c->params + e.first; sg.g[sg.n] = c->grad + e.first; sg.m[sg.n] = c->m + e.first; sg.v[sg.n] = c->v + e.first;
+        sg.n4[sg.n++] = e.second / 4;
     }
-    c->ppo_launches = r.launches;
+    return 0;
+}
+
+// one minibatch (arguments checked by the caller): the first half, then the Adam launch -- its exchanged form while a
+// gradient exchange between workers is open (pvae_fc_ppo_peer_open)
+int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
+             const pvae_fc_ppo_params* p, int adam_t, float* stats_out, hipStream_t st) {
+    int launches = 0;
+    int rc = ppo_grad_half(c, b, index, first, rows, p, st, &launches);
+    if (rc) return rc;
+    PpoAdamSegs sg;
+    if ((rc = ppo_segments(c, p, sg))) return rc;
+    const bool colsum = p->log_std_kind == 1;
+    rc = c->peers.open ? ppo_adam_exchange_launch(c->peers, g_ppo_peer_timeout_ticks, sg, p, adam_t, rows, b->k, c->scratch, colsum,
+                                                  c->log_std, c->log_std_m, c->log_std_v, stats_out, st)
+                       : ppo_adam_launch(sg, p, adam_t, rows, b->k, c->scratch, colsum, c->log_std, c->log_std_m, c->log_std_v,
+                                         stats_out, st);
+    if (rc) return rc;
+    c->ppo_launches = launches + 1;
     return 0;
 }
 
@@ -763,7 +784,10 @@ int pvae_fc_create(const pvae_fc_config* cfg, pvae_fc** out) {
     return 0;
 }
 
-void pvae_fc_destroy(pvae_fc* fc) { delete fc; }
+void pvae_fc_destroy(pvae_fc* fc) {
+    if (fc) ppo_peer_free(fc->peers);
+    delete fc;
+}
 
 int pvae_fc_bind(pvae_fc* c, float* params, void* workspace, size_t workspace_bytes) {
     if (!c || !params || !workspace) return fail(-1, "null argument");
@@ -894,6 +918,67 @@ int pvae_fc_ppo_sgd(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* perm,
             if (rc) return rc;
         }
     return 0;
+}
+
+int pvae_fc_ppo_grad(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
+                     const pvae_fc_ppo_params* p, float* stats_out, float* ls_grad, void* stream) {
+    int rc = check_ppo(c, b, p, first, rows, stats_out);
+    if (rc) return rc;
+    const bool colsum = p->log_std_kind == 1;
+    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+    int launches = 0;
+    if ((rc = ppo_grad_half(c, b, index, first, rows, p, (hipStream_t)stream, &launches))) return rc;
+    if ((rc = ppo_grad_finish_launch(rows, b->k, c->scratch, colsum, ls_grad, stats_out, (hipStream_t)stream, &launches))) return rc;
+    c->ppo_launches = launches;
+    return 0;
+}
+
+int pvae_fc_ppo_apply(pvae_fc* c, const pvae_fc_ppo_params* p, float grad_scale, const float* ls_grad, void* stream) {
+    if (!c) return fail(-1, "null stack set");
+    if (!p) return fail(-1, "null params");
+    if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
+    if (!c->grad || !c->m || !c->v || !c->scratch) return fail(-2, "pvae_fc_ppo_bind has not been called");
+    const FcLayout& L = c->L;
+    if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
+    if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
+    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
+    if (p->train_mask < 0 || p->train_mask >= (1 << L.S)) return fail(-1, "train_mask names a stack that does not exist");
+    const bool colsum = p->log_std_kind == 1;
+    if (colsum && (!c->log_std || !c->log_std_m || !c->log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_fc_ppo_bind)");
+    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+    PpoAdamSegs sg;
+    int rc = ppo_segments(c, p, sg);
+    if (rc) return rc;
+    if ((rc = ppo_apply_launch(sg, p, p->adam_t, L.cfg.n_out[0], grad_scale, ls_grad, colsum, c->log_std, c->log_std_m, c->log_std_v,
+                               (hipStream_t)stream)))
+        return rc;
+    c->ppo_launches = 1;
+    return 0;
+}
+
+int pvae_fc_ppo_peer_export(pvae_fc* c, void* blob) {
+    if (!c || !blob) return fail(-1, "null argument");
+    if (!c->grad) return fail(-2, "pvae_fc_ppo_bind has not been called");
+    float* arenas[1] = {c->grad};
+    const long long floats[1] = {c->L.arena_floats};
+    return ppo_peer_export(c->peers, arenas, floats, 1, c->L.cfg.n_out[0], blob);
+}
+
+int pvae_fc_ppo_peer_open(pvae_fc* c, int rank, int world, const void* blobs) {
+    if (!c || !blobs) return fail(-1, "null argument");
+    if (!c->grad) return fail(-2, "pvae_fc_ppo_bind has not been called");
+    float* arenas[1] = {c->grad};
+    return ppo_peer_open(c->peers, arenas, rank, world, blobs, g_ppo_peer_timeout_ticks);
+}
+
+int pvae_fc_ppo_peer_close(pvae_fc* c) {
+    if (!c) return fail(-1, "null stack set");
+    return ppo_peer_close(c->peers);
+}
+
+int pvae_fc_ppo_peer_status(pvae_fc* c, int* rank, int* world, uint32_t* timeouts, void* stream) {
+    if (!c) return fail(-1, "null stack set");
+    return ppo_peer_status(c->peers, rank, world, timeouts, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_launches(pvae_fc* c, int32_t* per_step) {

@@ -5,12 +5,13 @@
 //   pvae_step.hip            the training step at lookahead 1 and the step's C ABI (direct, prefetch and data-parallel steps)
 //   pvae_lookahead.hip       the training step at lookahead > 1 (the multi-step unroll)
 //   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
-//   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test
+//   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test;
+//                            the set-up of the PPO learners' gradient exchange between workers
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
 //   pvae_fc.hip              the stack set, and its PPO learner step and train-batch preparation on the launches of pvae_ppo_core.hip
-//   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats, evaluate
-//                            epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
+//   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats and its
+//                            two-halves and exchanged forms, evaluate epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
 //   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae_infer.hip,
 //                            pvae_fc.hip and pvae_ppo_core.hip
 #pragma once
@@ -157,6 +158,28 @@ inline int rccl_load() {
         if (r_ != 0) return fail(-21, "%s: %s", #expr, g_rccl.GetErrorString(r_));            \
     } while (0)
 
+// ---- the PPO learners' peer-mapped gradient exchange: its state (functions: below, "the PPO learner") ----
+// A learner's exchange state: every rank's gradient arena(s) and flag block mapped into this process (index = rank;
+// [rank] = the local pointers).  Parameters and moments are NOT mapped: every rank reads all gradients and updates its own
+// replica whole.  Flag block: [0, 8) ready[src], [8, 16) done[src], 16 ticket, 17 waits that gave up, [32, 64) the attach-time
+// check's tokens, then from word kPpoPeerLs the k floats of this rank's log-std gradient, where the peers read them.
+constexpr int kPpoPeerReady = 0, kPpoPeerDone = 8, kPpoPeerTicket = 16, kPpoPeerErr = 17, kPpoPeerSelf = 32, kPpoPeerGradA = 40,
+              kPpoPeerGradB = 48, kPpoPeerFin = 56, kPpoPeerPayload = 64, kPpoPeerLs = 256;
+constexpr int kPpoPeerArenas = 2;                // a stack set has one gradient arena, PhysicsVAE two (its own + the value stack set's)
+struct PpoPeers {
+    bool open = false;
+    int rank = 0, world = 0, n_arenas = 0, k = 0;
+    unsigned* flags = nullptr;                               // own flag block (hipExtMallocWithFlags, uncached)
+    size_t flag_bytes = 0;
+    unsigned* peer_flags[PVAE_P2P_MAX_RANKS] = {};
+    float* arena[kPpoPeerArenas][PVAE_P2P_MAX_RANKS] = {};   // gradient arenas
+    long long floats[kPpoPeerArenas] = {};
+    void* mapped[PVAE_P2P_MAX_RANKS][kPpoPeerArenas + 1] = {};   // what hipIpcOpenMemHandle returned (to close)
+    unsigned epoch = 0;                                      // exchanged launches issued so far (identical on every rank)
+    unsigned selftests = 0;
+    float* self_buf = nullptr;                               // the attach-time check's saved gradient line
+};
+
 struct pvae_ctx {
     void* comm = nullptr;        // ncclComm_t of the data-parallel group (pvae_comm_init)
     int comm_rank = 0, comm_world = 1;
@@ -251,6 +274,7 @@ struct pvae_ctx {
         pvae_fc* value = nullptr;
         int launches = 0;
         int eval_launches = 0, gae_launches = 0;         // pvae_ppo_prepare / pvae_ppo_evaluate (pvae_ppo_gae_launches)
+        PpoPeers peers;                                  // the learner's gradient exchange between workers (pvae_ppo_peer_*)
     } ppo;
 };
 static inline void params_touched(pvae_ctx* c, hipStream_t st, bool queued = true) {
@@ -596,6 +620,39 @@ struct PpoAdamSegs {
 };
 int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
                     int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);
+// The step in two halves (include/pvae.h "Gradient exchange between workers").  The first half ends with
+// ppo_grad_finish_launch in place of the Adam launch: stats_out[5] (ppo_finish_kernel) and, colsum, ls_grad[k] = the column
+// sums of the partial rows, the value the Adam launch's last workgroup forms; `launches` counts what went out.  The second
+// half is ppo_apply_launch: Adam over the segments on grad_scale * gradient, the log-std vector from grad_scale * ls_grad.
+int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out, hipStream_t st,
+                           int* launches);
+int ppo_apply_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int k, float grad_scale,
+                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, hipStream_t st);
+
+// ---- the PPO learners' peer-mapped gradient exchange (set-up: pvae_exchange.hip; the launch: pvae_ppo_core.hip) ----
+// Flag words of the peer-mapped exchanges (unsigned, one block per rank in uncached device memory): epochs and tokens only
+// grow, a wait compares with >=, and every wait is bounded -- a peer that never signals raises the error word.
+__device__ inline unsigned p2p_ld(const unsigned* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ inline void p2p_st(unsigned* q, unsigned x) { __hip_atomic_store(q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ inline bool p2p_wait(const unsigned* flag, unsigned epoch, long long timeout, unsigned* err) {
+    const long long t0 = wall_clock64();
+    while ((int)(p2p_ld(flag) - epoch) < 0) {
+        __builtin_amdgcn_s_sleep(8);
+        if (wall_clock64() - t0 > timeout) { atomicAdd(err, 1u); return false; }
+    }
+    return true;
+}
+// `arenas` / `floats`: the local gradient arenas as bound; k: the log-std vector's length
+int ppo_peer_export(PpoPeers& P, float* const* arenas, const long long* floats, int n_arenas, int k, void* blob);
+int ppo_peer_open(PpoPeers& P, float* const* arenas, int rank, int world, const void* blobs, long long timeout_ticks);
+int ppo_peer_close(PpoPeers& P);
+int ppo_peer_status(const PpoPeers& P, int* rank, int* world, uint32_t* timeouts, hipStream_t st);
+void ppo_peer_free(PpoPeers& P);
+inline long long g_ppo_peer_timeout_ticks = 20ll * 100000000ll;     // stack sets (pvae_set_option(NULL, "p2p_timeout_ms")); 100 MHz
+// The exchanged form of ppo_adam_launch: one launch, the N ranks' gradients summed in rank order and scaled by float(1 / N)
+int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
+                             int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
+                             float* stats_out, hipStream_t st);
 int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
                       const float* log_std_m, const float* log_std_v);      // the alignment and pairing rules of *_ppo_bind
 // Rows [r0, r1) of up to kZeroPanels panels (columns [0, width) of row stride ld) set to zero: a <= 4-row forward runs on

@@ -125,10 +125,11 @@ int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params*
     return 0;
 }
 
-// one minibatch (arguments checked by the caller)
-int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-             const pvae_fc_ppo_params* p, int adam_t, const float* eps, int noise, uint64_t seed, uint64_t offset,
-             float* stats_out, hipStream_t st) {
+// The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
+// gradient arenas (arguments checked by the caller); `launches_out` counts what went out
+int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
+                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t seed, uint64_t offset, hipStream_t st,
+                  int* launches_out) {
     const pvae_ctx::Ppo& q = c->ppo;
     const pvae_config& cfg = c->L.cfg;
     const int Db = cfg.dim_body, Z = cfg.latent;
@@ -186,20 +187,43 @@ int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, co
         if ((rc = ppo_backward_net(c, PVAE_NET_TE, rows, true, false, q.grad, st, &launches))) return rc;
     }
     if (train_v && (rc = fc_value_backward(q.value, 0, rows, st, &launches))) return rc;
-    {
-        PpoAdamSegs sg;
-        memset((void*)&sg, 0, sizeof(sg));
-        auto add = [&](float* pp, const float* gg, float* mm, float* vv, long long n) {
-            sg.p[sg.n] = pp; sg.g[sg.n] = gg; sg.m[sg.n] = mm; sg.v[sg.n] = vv; sg.n4[sg.n] = n / 4; ++sg.n;
-        };
-        if (train_te) add(c->params + TE.off, q.grad + TE.off, q.m + TE.off, q.v + TE.off, TE.count);
-        if (train_md) add(c->params + MD.off, q.grad + MD.off, q.m + MD.off, q.v + MD.off, MD.count);
-        if (train_v) add(vs.params, vs.grad, vs.m, vs.v, vs.arena_floats);
-        if ((rc = ppo_adam_launch(sg, p, adam_t, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m, q.log_std_v, stats_out, st)))
-            return rc;
-        ++launches;
-    }
-    c->ppo.launches = launches;
+    *launches_out = launches;
+    return 0;
+}
+
+// the trained nets' segments: what the Adam launch runs over (TE, MD: their parts of the arena; value: its own arena)
+void ppo_segments(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
+    const pvae_ctx::Ppo& q = c->ppo;
+    const int mask = p->train_mask ? p->train_mask : 7;
+    const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    const NetLayout& MD = c->L.net[PVAE_NET_MD];
+    memset((void*)&sg, 0, sizeof(sg));
+    auto add = [&](float* pp, const float* gg, float* mm, float* vv, long long n) {
+        sg.p[sg.n] = pp; sg.g[sg.n] = gg; sg.m[sg.n] = mm; sg.v[sg.n] = vv; sg.n4[sg.n] = n / 4; ++sg.n;
+    };
+    if (mask & kTrainTE) add(c->params + TE.off, q.grad + TE.off, q.m + TE.off, q.v + TE.off, TE.count);
+    if (mask & kTrainMD) add(c->params + MD.off, q.grad + MD.off, q.m + MD.off, q.v + MD.off, MD.count);
+    if (mask & kTrainValue) add(vs.params, vs.grad, vs.m, vs.v, vs.arena_floats);
+}
+
+// one minibatch (arguments checked by the caller): the first half, then the Adam launch -- its exchanged form while a
+// gradient exchange between workers is open (pvae_ppo_peer_open)
+int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
+             const pvae_fc_ppo_params* p, int adam_t, const float* eps, int noise, uint64_t seed, uint64_t offset,
+             float* stats_out, hipStream_t st) {
+    pvae_ctx::Ppo& q = c->ppo;
+    int launches = 0;
+    int rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, seed, offset, st, &launches);
+    if (rc) return rc;
+    PpoAdamSegs sg;
+    ppo_segments(c, vs, p, sg);
+    const int colsum = p->log_std_kind == 1;
+    rc = q.peers.open ? ppo_adam_exchange_launch(q.peers, c->p2p.timeout_ticks, sg, p, adam_t, rows, b->k, q.scratch, colsum,
+                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, st)
+                      : ppo_adam_launch(sg, p, adam_t, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m, q.log_std_v,
+                                        stats_out, st);
+    if (rc) return rc;
+    q.launches = launches + 1;
     return 0;
 }
 
@@ -335,6 +359,86 @@ int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, i
         }
     params_touched(c, (hipStream_t)stream);
     return 0;
+}
+
+int pvae_ppo_grad(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
+                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
+                  float* stats_out, float* ls_grad, void* stream) {
+    FcValueStack vs;
+    int rc = check_ppo(c, b, p, first, rows, stats_out, &vs);
+    if (rc) return rc;
+    const int colsum = p->log_std_kind == 1;
+    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+    int launches = 0;
+    if ((rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, rng_seed, rng_offset, (hipStream_t)stream, &launches)))
+        return rc;
+    if ((rc = ppo_grad_finish_launch(rows, b->k, c->ppo.scratch, colsum, ls_grad, stats_out, (hipStream_t)stream, &launches)))
+        return rc;
+    c->ppo.launches = launches;
+    return 0;
+}
+
+int pvae_ppo_apply(pvae_ctx* c, const pvae_fc_ppo_params* p, float grad_scale, const float* ls_grad, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!p) return fail(-1, "null params");
+    const pvae_ctx::Ppo& q = c->ppo;
+    if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
+    if (p->log_std_kind != 0 && p->log_std_kind != 1) return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
+    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
+    if (p->train_mask < 0 || p->train_mask > 7) return fail(-1, "train_mask names a net that does not exist (bits: 1 TE, 2 MD, 4 value)");
+    const int colsum = p->log_std_kind == 1;
+    if (colsum && (!q.log_std || !q.log_std_m || !q.log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_ppo_bind)");
+    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+    FcValueStack vs;
+    if ((rc = fc_value_stack(q.value, &vs))) return rc;
+    PpoAdamSegs sg;
+    ppo_segments(c, vs, p, sg);
+    if ((rc = ppo_apply_launch(sg, p, p->adam_t, c->L.cfg.dim_action, grad_scale, ls_grad, colsum, q.log_std, q.log_std_m,
+                               q.log_std_v, (hipStream_t)stream)))
+        return rc;
+    c->ppo.launches = 1;
+    params_touched(c, (hipStream_t)stream);
+    return 0;
+}
+
+// the learner's two gradient arenas as the exchange maps them: the one of pvae_ppo_bind, and the value stack set's
+static int ppo_peer_arenas(pvae_ctx* c, float** arenas, long long* floats) {
+    if (!c) return fail(-1, "null ctx");
+    const pvae_ctx::Ppo& q = c->ppo;
+    if (!q.grad || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
+    FcValueStack vs;
+    const int rc = fc_value_stack(q.value, &vs);
+    if (rc) return rc;
+    arenas[0] = q.grad; floats[0] = c->L.arena_floats;
+    arenas[1] = vs.grad; floats[1] = vs.arena_floats;
+    return 0;
+}
+
+int pvae_ppo_peer_export(pvae_ctx* c, void* blob) {
+    float* arenas[2];
+    long long floats[2];
+    const int rc = ppo_peer_arenas(c, arenas, floats);
+    if (rc) return rc;
+    return ppo_peer_export(c->ppo.peers, arenas, floats, 2, c->L.cfg.dim_action, blob);
+}
+
+int pvae_ppo_peer_open(pvae_ctx* c, int rank, int world, const void* blobs) {
+    float* arenas[2];
+    long long floats[2];
+    const int rc = ppo_peer_arenas(c, arenas, floats);
+    if (rc) return rc;
+    return ppo_peer_open(c->ppo.peers, arenas, rank, world, blobs, c->p2p.timeout_ticks);
+}
+
+int pvae_ppo_peer_close(pvae_ctx* c) {
+    if (!c) return fail(-1, "null ctx");
+    return ppo_peer_close(c->ppo.peers);
+}
+
+int pvae_ppo_peer_status(pvae_ctx* c, int* rank, int* world, uint32_t* timeouts, void* stream) {
+    if (!c) return fail(-1, "null ctx");
+    return ppo_peer_status(c->ppo.peers, rank, world, timeouts, (hipStream_t)stream);
 }
 
 int pvae_ppo_launches(pvae_ctx* c, int32_t* per_step) {

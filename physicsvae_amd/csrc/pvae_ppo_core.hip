@@ -105,6 +105,13 @@ ppo_finish_kernel(const float* part, int nparts, int stride, float inv_rows, flo
     ppo_finish(part, nparts, stride, inv_rows, out, threadIdx.x);
 }
 
+// column j of a state-independent log-std's gradient: the partial rows added in partial-row order
+__device__ inline float ppo_ls_colsum(const float* __restrict__ part, int nparts, int stride, int j) {
+    double gs = 0.0;                           // (a few hundred signed terms per column: in double, so that the order does not show)
+    for (int i = 0; i < nparts; ++i) gs += (double)part[(size_t)i * stride + kPartStats + j];
+    return (float)gs;
+}
+
 // Adam over the trained segments (adam_update4 with the AdamScalars the trainer's adam_flat_kernel gets: the same bits)
 // + ONE extra workgroup, the last: the stats and, for a state-independent log-std, that vector's gradient (the column
 // sums, added in partial-row order) and its Adam update.  A segment is a run of float4 elements with its own parameter,
@@ -123,9 +130,7 @@ ppo_adam_kernel(PpoAdam a) {
         if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
         if (a.ls)
             for (int j = threadIdx.x; j < a.k; j += 256) {
-                double gs = 0.0;               // (a few hundred signed terms per column: in double, so that the order does not show)
-                for (int i = 0; i < a.nparts; ++i) gs += (double)a.part[(size_t)i * a.part_stride + kPartStats + j];
-                const float g = (float)gs;
+                const float g = ppo_ls_colsum(a.part, a.nparts, a.part_stride, j);
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
                 adam_update(g, p, m, v, a.s);
                 a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
@@ -145,6 +150,151 @@ ppo_adam_kernel(PpoAdam a) {
         reinterpret_cast<v4f*>(a.seg.p[k])[q] = pp;
         reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
         reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// the step in two halves, and the exchanged Adam launch (include/pvae.h "Gradient exchange between workers")
+// ---------------------------------------------------------------------------------------
+// first half's end: the log-std gradient where the caller can reduce it over the workers (the stats: ppo_finish_kernel)
+__global__ void __launch_bounds__(256)
+ppo_ls_grad_kernel(const float* part, int nparts, int stride, int k, float* __restrict__ ls_grad) {
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < k; j += gridDim.x * 256) ls_grad[j] = ppo_ls_colsum(part, nparts, stride, j);
+}
+
+// Adam on float4 element q of segment k with the gradient gg: the local parameters and moments, as ppo_adam_kernel
+__device__ inline void ppo_adam_elem(const PpoAdam& a, int k, long long q, const v4f& gg) {
+    v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
+    v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
+    v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
+    adam_update4(gg, pp, mm, vv, a.s);
+    reinterpret_cast<v4f*>(a.seg.p[k])[q] = pp;
+    reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
+    reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
+}
+__device__ inline v4f scale4(const v4f& g, float s) {       // (pinned: no contraction with Adam's first operation)
+    return v4f{__fmul_rn(g[0], s), __fmul_rn(g[1], s), __fmul_rn(g[2], s), __fmul_rn(g[3], s)};
+}
+
+// second half: ppo_adam_kernel on scale * gradient, the log-std vector from scale * ls_grad; no stats (the first half wrote them)
+__global__ void __launch_bounds__(256)
+ppo_apply_kernel(PpoAdam a, float scale, const float* __restrict__ ls_grad) {
+    if (blockIdx.x == gridDim.x - 1) {
+        if (a.ls)
+            for (int j = threadIdx.x; j < a.k; j += 256) {
+                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
+                adam_update(__fmul_rn(ls_grad[j], scale), p, m, v, a.s);
+                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
+            }
+        return;
+    }
+    const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
+        int k = 0;
+        while (i >= a.end4[k]) ++k;
+        const long long q = i - (k ? a.end4[k - 1] : 0);
+        ppo_adam_elem(a, k, q, scale4(reinterpret_cast<const v4f*>(a.seg.g[k])[q], scale));
+    }
+}
+
+// The exchanged form of ppo_adam_kernel: N workers' gradients, each in its own process' buffers and mapped into this one
+// (PpoPeers), summed IN RANK ORDER, scaled by float(1 / N), and Adam applied to the LOCAL parameters and moments -- every
+// rank updates every element, so the replicas and their moments stay whole and bit-identical.  The hand-off is
+// p2p_exchange_kernel's (pvae_exchange.hip): the gradient was written by earlier launches of the stream, so
+//   1. workgroup 0 stores this rank's log-std gradient to its slot in the flag block, fences (system-scope release) and
+//      tells every peer "ready": epoch -> peer's ready[me];
+//   2. every workgroup waits for all peers' "ready" (p2p_wait: bounded), acquires, and reads every handed-off byte with
+//      `buffer_load ... sc0 sc1` through descriptors over the segment in each rank's arena;
+//   3. the extra last workgroup finishes the stats (this worker's own) and updates the log-std vector from the N slots;
+//   4. the last workgroup to finish (ticket) tells every peer "done" and waits for theirs: when the launch ends the next
+//      step's backward may overwrite the gradient buffers.
+// A wait that gives up aborts this rank's update -- nothing moves, the error word counts it, "done" is still sent.
+// Every workgroup of the launch spins until the peers arrive, so the grid stays far below what fills the device
+// (kExchangeMaxBlocks): workers that share one GPU must be able to run their launches side by side.
+constexpr int kExchangeMaxBlocks = 256;
+struct PpoAdamPeers {
+    unsigned* f[PVAE_P2P_MAX_RANKS];                         // flag blocks
+    const float* arena[kPpoPeerArenas][PVAE_P2P_MAX_RANKS];  // gradient arenas
+    int seg_arena[kAdamSegs]; long long seg_off[kAdamSegs];  // where segment i's gradient lies: arena, float offset
+    int me; unsigned epoch; long long timeout_ticks;
+    float inv_n;
+};
+template <int N>
+__global__ void __launch_bounds__(256)
+ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
+    unsigned* mine = x.f[x.me];
+    const int tid = threadIdx.x, me = x.me;
+    if (blockIdx.x == 0) {
+        if (a.ls)
+            for (int j = tid; j < a.k; j += 256)
+                __hip_atomic_store((float*)(mine + kPpoPeerLs) + j, ppo_ls_colsum(a.part, a.nparts, a.part_stride, j),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid < N && tid != me) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");             // (system scope; the launches that wrote the gradient ended before this one began)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            p2p_st(x.f[tid] + kPpoPeerReady + me, x.epoch);
+        }
+    }
+    __shared__ int abort_;
+    if (tid == 0) abort_ = 0;
+    __syncthreads();
+    if (tid < N && tid != me) {
+        if (!p2p_wait(mine + kPpoPeerReady + tid, x.epoch, x.timeout_ticks, mine + kPpoPeerErr)) abort_ = 1;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    }
+    __syncthreads();
+    const bool go = !abort_;
+    if (blockIdx.x == gridDim.x - 1) {
+        if (tid < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, tid);
+        if (a.ls && go)
+            for (int j = tid; j < a.k; j += 256) {
+                float g = 0.f;                 // (the own column is summed here again: no workgroup waits for another of its launch)
+#pragma unroll
+                for (int q = 0; q < N; ++q) {
+                    const float gq = q == me ? ppo_ls_colsum(a.part, a.nparts, a.part_stride, j)
+                                             : __hip_atomic_load((const float*)(x.f[q] + kPpoPeerLs) + j, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_SYSTEM);
+                    g = q == 0 ? gq : g + gq;                         // rank order
+                }
+                float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
+                adam_update(__fmul_rn(g, x.inv_n), p, m, v, a.s);
+                a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
+            }
+    } else if (go) {
+        for (int k = 0; k < a.seg.n; ++k) {
+            const long long n4 = a.seg.n4[k];
+            __amdgpu_buffer_rsrc_t rg[N];
+#pragma unroll
+            for (int q = 0; q < N; ++q)
+                rg[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x.arena[x.seg_arena[k]][q] + x.seg_off[k]), 0,
+                                                          (unsigned)(n4 * 16), 0x00020000);
+            for (long long i = blockIdx.x * 256ll + tid; i < n4; i += (gridDim.x - 1) * 256ll) {
+                v4f g[N];
+#pragma unroll
+                for (int q = 0; q < N; ++q)
+                    g[q] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rg[q], (unsigned)(i * 16), 0, 17));
+                v4f sum = g[0];
+#pragma unroll
+                for (int q = 1; q < N; ++q) sum += g[q];              // rank order
+                ppo_adam_elem(a, k, i, scale4(sum, x.inv_n));
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __shared__ unsigned last;
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        last = atomicAdd(mine + kPpoPeerTicket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    if (tid == 0) mine[kPpoPeerTicket] = 0;
+    if (tid < N && tid != me) {
+        p2p_st(x.f[tid] + kPpoPeerDone + me, x.epoch);
+        p2p_wait(mine + kPpoPeerDone + tid, x.epoch, x.timeout_ticks, mine + kPpoPeerErr);
     }
 }
 
@@ -384,9 +534,9 @@ int ppo_head_launch(const PpoHead& h, hipStream_t st) {
     return 0;
 }
 
-int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
-    PpoAdam a;
+// the arguments of the Adam launch in its three forms; returns the float4 elements of all segments
+static long long fill_adam(PpoAdam& a, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k,
+                           const float* part, int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out) {
     memset((void*)&a, 0, sizeof(a));
     a.seg = segs;
     long long total4 = 0;
@@ -396,9 +546,81 @@ int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int ad
     a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
     a.k = k;
     if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
+    return total4;
+}
+
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
+    PpoAdam a;
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out);
     long long grid = (total4 + 255) / 256;
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(ppo_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out, hipStream_t st,
+                           int* launches) {
+    const int nparts = head_waves(pad32(rows)), stride = part_stride(k, colsum != 0);
+    hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, nparts, stride, (float)(1.0 / rows), stats_out);
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+    if (colsum) {
+        hipLaunchKernelGGL(ppo_ls_grad_kernel, dim3((k + 255) / 256), dim3(256), 0, st, part, nparts, stride, k, ls_grad);
+        HIP_TRY(hipGetLastError());
+        ++*launches;
+    }
+    return 0;
+}
+
+int ppo_apply_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int k, float grad_scale,
+                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, hipStream_t st) {
+    PpoAdam a;
+    const long long total4 = fill_adam(a, segs, p, adam_t, 1, k, nullptr, colsum, ls, ls_m, ls_v, nullptr);
+    long long grid = (total4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(ppo_apply_kernel, dim3((int)grid + 1), dim3(256), 0, st, a, grad_scale, ls_grad);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
+                             int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
+                             float* stats_out, hipStream_t st) {
+    if (!P.open) return fail(-2, "the PPO gradient exchange is not open");
+    if (colsum && k != P.k) return fail(-2, "log-std vector of %d values, the exchange was exported for %d", k, P.k);
+    PpoAdam a;
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out);
+    PpoAdamPeers x;
+    memset((void*)&x, 0, sizeof(x));
+    for (int q = 0; q < P.world; ++q) {
+        x.f[q] = P.peer_flags[q];
+        for (int r = 0; r < P.n_arenas; ++r) x.arena[r][q] = P.arena[r][q];
+    }
+    for (int i = 0; i < segs.n; ++i) {
+        int r = 0;
+        for (; r < P.n_arenas; ++r) {
+            const float* base = P.arena[r][P.rank];
+            if (segs.g[i] >= base && segs.g[i] + 4 * segs.n4[i] <= base + P.floats[r]) break;
+        }
+        if (r == P.n_arenas) return fail(-2, "the gradient buffers were re-bound after the exchange was exported");
+        // (the kernel addresses a segment through a 32-bit buffer descriptor)
+        if (segs.n4[i] >= ((long long)1 << 28)) return fail(-1, "segment of %lld floats: the exchanged launch takes < 2^30", 4 * segs.n4[i]);
+        x.seg_arena[i] = r; x.seg_off[i] = segs.g[i] - P.arena[r][P.rank];
+    }
+    x.me = P.rank; x.epoch = ++P.epoch; x.timeout_ticks = timeout_ticks;
+    x.inv_n = (float)(1.0 / P.world);
+    long long grid = (total4 + 255) / 256;
+    if (grid > kExchangeMaxBlocks) grid = kExchangeMaxBlocks;
+    if (grid < 1) grid = 1;
+    switch (P.world) {
+#define PVAE_PPO_PEER_CASE(N) case N: hipLaunchKernelGGL((ppo_adam_exchange_kernel<N>), dim3((int)grid + 1), dim3(256), 0, st, a, x); break;
+        PVAE_PPO_PEER_CASE(1) PVAE_PPO_PEER_CASE(2) PVAE_PPO_PEER_CASE(3) PVAE_PPO_PEER_CASE(4)
+        PVAE_PPO_PEER_CASE(5) PVAE_PPO_PEER_CASE(6) PVAE_PPO_PEER_CASE(7) PVAE_PPO_PEER_CASE(8)
+#undef PVAE_PPO_PEER_CASE
+        default: return fail(-1, "world %d", P.world);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

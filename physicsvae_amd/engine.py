@@ -979,6 +979,49 @@ class HipEngine:
         _lib.check(self.lib.pvae_ppo_launches(self.ctx, C.byref(n)), "pvae_ppo_launches")
         return n.value
 
+    # -- gradient exchange between workers (include/pvae.h "Gradient exchange between workers") --------
+    def ppo_grad_step(self, batch, params, first, rows, index=None, eps=None, noise=True, seed=0, offset=0, stats_out=None):
+        """`pvae_ppo_grad`: `ppo_step` up to, not including, its Adam launch -- the gradient lies in `ppo_grad` and the value
+        engine's `ppo_grad`, nothing else moved.  Returns (stats [5], ls_grad [Da]: the log-std vector's gradient, written
+        for a trained vector only)."""
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        if stats_out is None:
+            stats_out = torch.empty(5, dtype=torch.float32, device=self.device)
+        _check_index(index, int(b.n_rows), self.device)
+        eps = self._ppo_eps(eps, (int(rows), self.arch.Z))
+        ls_grad = _ppo_ls_grad(self, self.arch.Da)
+        _lib.check(self.lib.pvae_ppo_grad(self.ctx, C.byref(b), index.data_ptr() if index is not None else None, int(first),
+                                          int(rows), C.byref(params), eps.data_ptr() if eps is not None else None,
+                                          1 if noise else 0, int(seed), int(offset), stats_out.data_ptr(), ls_grad.data_ptr(),
+                                          self._stream()), "pvae_ppo_grad")
+        return stats_out, ls_grad
+
+    def ppo_apply(self, params, grad_scale=1.0, ls_grad=None):
+        """`pvae_ppo_apply`: Adam (time step `params.adam_t`) over the trained nets on `grad_scale` times what the gradient
+        buffers hold, and over a trained log-std vector on `grad_scale * ls_grad`."""
+        self._need_gpu()
+        _lib.check(self.lib.pvae_ppo_apply(self.ctx, C.byref(params), float(grad_scale),
+                                           ls_grad.data_ptr() if ls_grad is not None else None, self._stream()), "pvae_ppo_apply")
+
+    def ppo_grad_arenas(self):
+        """The gradient buffers a transport outside the library reduces: this engine's and the value engine's."""
+        return [self.ppo_grad, self._ppo_keep[1].ppo_grad]
+
+    def ppo_peer_export(self):
+        return _ppo_peer_export(self, self.lib.pvae_ppo_peer_export, "pvae_ppo_peer_export")
+
+    def ppo_peer_open(self, rank, world, blobs):
+        _ppo_peer_open(self, self.lib.pvae_ppo_peer_open, "pvae_ppo_peer_open", rank, world, blobs)
+
+    def ppo_peer_close(self):
+        if self.ctx is not None:
+            _lib.check(self.lib.pvae_ppo_peer_close(self.ctx), "pvae_ppo_peer_close")
+
+    def ppo_peer_status(self, sync=True):
+        """(rank, world, waits that gave up) of the PPO gradient exchange; (0, 0, n) when none is open."""
+        return _ppo_peer_status(self, self.lib.pvae_ppo_peer_status, "pvae_ppo_peer_status", sync)
+
     # -- train-batch preparation (include/pvae.h "Train-batch preparation for PhysicsVAE") ------------
     def _ppo_draws(self, n, eps, noise, seed, offset, out, want):
         """(pvae_ppo_draws, eps kept alive, latent_eps or None): `eps` [n, Z] supplied draws or None (Philox); `want`: the
@@ -1233,6 +1276,47 @@ class StackSetEngine:
         _lib.check(self.lib.pvae_fc_ppo_launches(self.ctx, C.byref(n)), "pvae_fc_ppo_launches")
         return n.value
 
+    # -- gradient exchange between workers (include/pvae.h "Gradient exchange between workers") --------
+    def ppo_grad_step(self, batch, params, first, rows, index=None, stats_out=None):
+        """`pvae_fc_ppo_grad`: `ppo_step` up to, not including, its Adam launch -- the gradient lies in `ppo_grad`, nothing
+        else moved.  Returns (stats [5], ls_grad [k]: the log-std vector's gradient, written for a trained vector only)."""
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        if stats_out is None:
+            stats_out = torch.empty(5, dtype=torch.float32, device=self.device)
+        _check_index(index, int(b.n_rows), self.device)
+        ls_grad = _ppo_ls_grad(self, self.n_outs[0])
+        _lib.check(self.lib.pvae_fc_ppo_grad(self.ctx, C.byref(b), index.data_ptr() if index is not None else None, int(first),
+                                             int(rows), C.byref(params), stats_out.data_ptr(), ls_grad.data_ptr(),
+                                             self._stream()), "pvae_fc_ppo_grad")
+        return stats_out, ls_grad
+
+    def ppo_apply(self, params, grad_scale=1.0, ls_grad=None):
+        """`pvae_fc_ppo_apply`: Adam (time step `params.adam_t`) over the trained stacks on `grad_scale` times what `ppo_grad`
+        holds, and over a trained log-std vector on `grad_scale * ls_grad`."""
+        self._need_gpu()
+        _lib.check(self.lib.pvae_fc_ppo_apply(self.ctx, C.byref(params), float(grad_scale),
+                                              ls_grad.data_ptr() if ls_grad is not None else None, self._stream()),
+                   "pvae_fc_ppo_apply")
+
+    def ppo_grad_arenas(self):
+        """The gradient buffers a transport outside the library reduces."""
+        return [self.ppo_grad]
+
+    def ppo_peer_export(self):
+        return _ppo_peer_export(self, self.lib.pvae_fc_ppo_peer_export, "pvae_fc_ppo_peer_export")
+
+    def ppo_peer_open(self, rank, world, blobs):
+        _ppo_peer_open(self, self.lib.pvae_fc_ppo_peer_open, "pvae_fc_ppo_peer_open", rank, world, blobs)
+
+    def ppo_peer_close(self):
+        if self.ctx is not None:
+            _lib.check(self.lib.pvae_fc_ppo_peer_close(self.ctx), "pvae_fc_ppo_peer_close")
+
+    def ppo_peer_status(self, sync=True):
+        """(rank, world, waits that gave up) of the PPO gradient exchange; (0, 0, n) when none is open."""
+        return _ppo_peer_status(self, self.lib.pvae_fc_ppo_peer_status, "pvae_fc_ppo_peer_status", sync)
+
     # -- train-batch preparation (include/pvae.h "Train-batch preparation") --------------------------
     def _rollout(self, ro, need):
         return make_rollout(ro, need, self.device, self.n_in, self.n_outs[0])
@@ -1379,6 +1463,37 @@ def set_fc_per_stack(on):
 
 
 PPO_COLUMNS = ("actions", "old_dist", "old_logp", "advantages", "value_targets", "vf_preds")
+
+
+# -- the PPO learners' gradient exchange between workers: what HipEngine and StackSetEngine share ------------------------------
+def _ppo_ls_grad(engine, k):
+    """The k floats `*_ppo_grad` writes the log-std vector's gradient to (allocated once, kept with the engine)."""
+    if getattr(engine, "ppo_ls_grad", None) is None:
+        engine.ppo_ls_grad = torch.zeros(k, dtype=torch.float32, device=engine.device)
+    return engine.ppo_ls_grad
+
+
+def _ppo_peer_export(engine, fn, what):
+    """The blob the peers open (IPC handles of the bound gradient buffers and the flag block, sizes).  `ppo_bind` first."""
+    engine._need_gpu()
+    buf = C.create_string_buffer(_lib.P2P_BLOB_BYTES)
+    _lib.check(fn(engine.ctx, buf), what)
+    return buf.raw
+
+
+def _ppo_peer_open(engine, fn, what, rank, world, blobs):
+    """Map the peers' gradient buffers and flag blocks (`blobs`: every rank's, in rank order) and run the attach-time check."""
+    engine._need_gpu()
+    assert len(blobs) == world and all(len(b) == _lib.P2P_BLOB_BYTES for b in blobs)
+    _lib.check(fn(engine.ctx, int(rank), int(world), b"".join(blobs)), what)
+
+
+def _ppo_peer_status(engine, fn, what, sync):
+    if engine.ctx is None:
+        return (0, 0, 0)
+    r, w, t = C.c_int(), C.c_int(), C.c_uint32()
+    _lib.check(fn(engine.ctx, C.byref(r), C.byref(w), C.byref(t) if sync else None, engine._stream()), what)
+    return (r.value, w.value, t.value)
 
 
 def make_ppo_batch(batch, device, k, n_in=None):

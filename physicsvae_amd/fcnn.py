@@ -195,14 +195,29 @@ class FullyConnectedPolicy(nn.Module):
                 "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
                 "value_targets": res["value_targets"], "last_value": res["last_value"]}
 
-    def ppo_learn(self, batch, config, perm=None):
+    def _ppo_dp_state(self):
+        """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: parameters, the log-std vector
+        and Adam's moments (the step counter travels beside them)."""
+        eng = self.engine
+        kind, base, log_std, train_ls = self._ppo_log_std()
+        eng.ppo_bind(log_std, train_ls)
+        vector = log_std if kind != "state_dependent" and self._policy_fn._model[-1].type != "constant" else None
+        return [t for t in (eng.params, eng.ppo_m, eng.ppo_v, vector, eng.ppo_ls_m if train_ls else None,
+                            eng.ppo_ls_v if train_ls else None) if t is not None]
+
+    def ppo_learn(self, batch, config, perm=None, dp=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_fc_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step
         forward + PPO loss + backward + Adam in 9 launches, nothing synchronised.  `batch`: device tensors under RLlib's
         sample-batch keys (obs, actions, action_dist_inputs, action_logp, advantages, value_targets, vf_preds); `perm`: int32
         [num_sgd_iter, n_rows] on the device, the row order of every pass (None: row order).  Returns the per-step stats
         [steps, 5] (total, policy loss, vf loss, kl, entropy) on the device.  Adam's moments and time step live in this
-        module (`reset_ppo_optimizer`); frozen stacks (`requires_grad_(False)`) are left alone, parameters and moments."""
+        module (`reset_ppo_optimizer`); frozen stacks (`requires_grad_(False)`) are left alone, parameters and moments.
+        `dp`: a `parallel.PPODataParallel` this module is attached to -- every step's gradient is then averaged over the
+        workers before Adam (the rule: `ppo.py`'s module docstring); the call is collective, the workers' row counts are
+        gathered once and a ValueError names the ranks that would issue another number of steps.  The stats stay this
+        worker's own.  With "p2p" the one library call is unchanged; with "torch" every minibatch is `pvae_fc_ppo_grad`,
+        an all-reduce, `pvae_fc_ppo_apply`."""
         from . import ppo as P
         eng = self.engine
         eng._need_gpu()
@@ -223,7 +238,13 @@ class FullyConnectedPolicy(nn.Module):
         params = config.params(kind, base, adam_t=t + 1, train_mask=0 if mask == full else mask)
         if perm is not None:
             perm = perm.to(eng.device, torch.int32).contiguous()
-        stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm)
+        if dp is not None:
+            dp.check_steps(int(cols[0].n_rows), config, eng.device)
+        if dp is not None and dp.transport == "torch":
+            stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=params.train_mask),
+                           int(cols[0].n_rows), config, perm, train_ls)
+        else:
+            stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm)
         self.__dict__["_ppo_t"] = t + stats.shape[0]
         self._cur_value = None
         return stats

@@ -850,7 +850,21 @@ class PhysicsVAE(nn.Module):
                 "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
                 "value_targets": res["value_targets"], "last_value": res["last_value"], "latent_eps": res["latent_eps"]}
 
-    def ppo_learn(self, batch, config, perm=None, eps=None):
+    def _ppo_dp_state(self):
+        """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: the parameter arena and the
+        value branch's, the log-std vector and the PPO step's Adam moments (the step counter travels beside them)."""
+        eng = self.engine
+        self._ppo_refusals()
+        als = self.__dict__["_als"]
+        train_ls = als.type == "state_independent" and als.log_std.requires_grad
+        ve = self._ppo_value_engine()
+        log_std = als.on_device(eng.device)
+        eng.ppo_bind(ve, log_std, train_ls)
+        vector = log_std if als.type != "constant" else None        # (a constant one is configuration, the same everywhere)
+        return [t for t in (eng.params, ve.params, eng.ppo_m, eng.ppo_v, ve.ppo_m, ve.ppo_v, vector,
+                            eng.ppo_ls_m if train_ls else None, eng.ppo_ls_v if train_ls else None) if t is not None]
+
+    def ppo_learn(self, batch, config, perm=None, eps=None, dp=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step the
         forward of rmt:742-771 without the world model, the PPO loss, backward and Adam, nothing synchronised.  `batch`:
@@ -860,7 +874,12 @@ class PhysicsVAE(nn.Module):
         Returns the per-step stats [steps, 5] (`ppo.STATS`) on the device.  Adam's moments and time step live in this module
         (`reset_ppo_optimizer`) apart from the supervised trainer's; the encoder, the decoder and the value branch are each
         trained or frozen as a whole (`requires_grad`); a frozen net's parameters and moments are left alone.  The first call
-        re-homes the value branch into a stack set (`_ppo_value_engine`)."""
+        re-homes the value branch into a stack set (`_ppo_value_engine`).  `dp`: a `parallel.PPODataParallel` this module is
+        attached to -- every step's gradient is then averaged over the workers before Adam (the rule: `ppo.py`'s module
+        docstring; the rank does not enter the Philox stream: give every worker's module its own seed); the call is
+        collective, the workers' row counts are gathered once and a ValueError names the ranks that would issue another
+        number of steps.  The stats stay this worker's own.  With "p2p" the one library call is unchanged; with "torch" every
+        minibatch is `pvae_ppo_grad`, an all-reduce of both gradient arenas, `pvae_ppo_apply`."""
         from . import ppo as P
         eng = self.engine
         self._ppo_refusals()
@@ -882,8 +901,18 @@ class PhysicsVAE(nn.Module):
         if perm is not None:
             perm = perm.to(eng.device, torch.int32).contiguous()
         st = self._st
-        stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm, eps=eps,
-                            noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
+        draws = dict(eps=eps, noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
+        if dp is not None:
+            dp.check_steps(int(cols[0].n_rows), config, eng.device)
+        if dp is not None and dp.transport == "torch":
+            n = int(cols[0].n_rows)
+            steps = P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter)
+            draws["eps"] = eng._ppo_eps(eps, (steps, config.sgd_minibatch_size, eng.arch.Z))
+            kind = "state_independent" if train_ls else "constant"
+            stats = dp.sgd(eng, cols, lambda i: config.params(kind, 0.0, adam_t=t + 1 + i, train_mask=params.train_mask), n,
+                           config, perm, train_ls, **draws)
+        else:
+            stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm, **draws)
         st._rng_calls += stats.shape[0]
         self.__dict__["_ppo_t"] = t + stats.shape[0]
         st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone

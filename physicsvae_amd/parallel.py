@@ -313,6 +313,116 @@ def _all_reduce_async(self, tensor):
 DataParallel.all_reduce_async = _all_reduce_async
 
 
+class PPODataParallel:
+    """Gradient exchange between the workers of the fused PPO learners (`ppo.py`'s module docstring has the rule;
+    `FullyConnectedPolicy.ppo_learn(..., dp=this)`, `PhysicsVAE.ppo_learn(..., dp=this)`).  One process per worker,
+    `torch.distributed` initialised.  transport "p2p": the workers map one another's gradient buffers (hipIpc; the blobs
+    travel over `group`) and the step's Adam launch sums them itself; "torch": per minibatch the gradient buffers go
+    through `dist.all_reduce` between the step's two halves -- nccl between GPUs, gloo anywhere."""
+
+    TRANSPORTS = ("p2p", "torch")
+
+    def __init__(self, rank=0, world=1, group=None, transport="p2p"):
+        if transport not in self.TRANSPORTS:
+            raise ValueError("transport %r: one of %s" % (transport, self.TRANSPORTS))
+        self.rank, self.world, self.group, self.transport = int(rank), int(world), group, transport
+        if self.world > 1 and not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("PPODataParallel with %d workers needs torch.distributed initialised" % self.world)
+
+    def _agree(self, engine, ok):
+        if self.world == 1:
+            return bool(ok)
+        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=engine.device)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
+        return int(flag.item()) == 1
+
+    def attach(self, model):
+        """Collective.  Rank 0's parameters, log-std, PPO moments and Adam step counter on every worker; for "p2p" the
+        exchange is opened (export, all-gather of the blobs, open with its attach-time check).  Every step is agreed by a
+        MIN over a success flag, so either every worker returns or every worker raises."""
+        engine = model.engine
+        engine._need_gpu()
+        state = model._ppo_dp_state()                    # (binds the PPO buffers)
+        if self.world > 1:
+            for t in state:
+                dist.broadcast(t, src=0, group=self.group)
+            box = [model.__dict__.get("_ppo_t", 0)]
+            dist.broadcast_object_list(box, src=0, group=self.group)
+            model.__dict__["_ppo_t"] = int(box[0])
+            if hasattr(engine, "params_changed"):
+                engine.params_changed()
+        if self.transport != "p2p":
+            return
+        if engine.ppo_peer_status(sync=False)[1]:
+            raise RuntimeError("a PPO gradient exchange is already open on this model: detach first")
+        blob, err = None, None
+        try:
+            blob = engine.ppo_peer_export()
+        except Exception as exc:                                   # noqa: BLE001
+            err = str(exc)
+        blobs = [blob]
+        if self.world > 1:
+            blobs = [None] * self.world
+            dist.all_gather_object(blobs, blob, group=self.group)
+        ok = all(b is not None for b in blobs)
+        if ok:
+            try:
+                engine.ppo_peer_open(self.rank, self.world, blobs)
+            except Exception as exc:                               # noqa: BLE001
+                ok, err = False, str(exc)
+        if not self._agree(engine, ok):
+            engine.ppo_peer_close()
+            raise RuntimeError("the peer-mapped PPO gradient exchange could not be set up (%s)" % (err or "another rank failed"))
+
+    def detach(self, model):
+        """Collective: every worker's queued steps complete, then the peers are unmapped."""
+        engine = model.engine
+        torch.cuda.synchronize(engine.device)
+        if self.world > 1:
+            dist.barrier(group=self.group)
+        engine.ppo_peer_close()
+
+    def timeouts(self, model):
+        """Waits of the in-library exchange that gave up on this worker (each one an update that did not happen)."""
+        return model.engine.ppo_peer_status()[2]
+
+    def check_steps(self, n_rows, config, device):
+        """Once per `ppo_learn`: the workers all-gather their row counts; a ValueError names the ranks that would issue
+        another number of steps (`ppo.dp_check_steps`).  Returns the number of steps."""
+        from . import ppo as P
+        rows = [int(n_rows)]
+        if self.world > 1:
+            t = torch.tensor([int(n_rows)], dtype=torch.int64, device=device)
+            parts = [torch.empty_like(t) for _ in range(self.world)]
+            dist.all_gather(parts, t, group=self.group)
+            rows = [int(x.item()) for x in parts]
+        return P.dp_check_steps(rows, config.sgd_minibatch_size, config.num_sgd_iter)
+
+    def sgd(self, engine, cols, params_at, n_rows, config, perm, train_ls, **draws):
+        """The SGD loop of `*_ppo_sgd` on the "torch" transport: per minibatch `ppo_grad_step`, a SUM all-reduce of the
+        gradient buffers and of a trained log-std vector's gradient, `ppo_apply` with grad_scale = 1 / N.  `params_at(i)`:
+        step i's pvae_fc_ppo_params; `draws` (PhysicsVAE): eps [steps, minibatch, Z] or None, noise, seed, offset."""
+        mb = int(config.sgd_minibatch_size)
+        steps = config.num_sgd_iter * ((n_rows + mb - 1) // mb)
+        stats = torch.empty(steps, 5, dtype=torch.float32, device=engine.device)
+        eps = draws.pop("eps", None)
+        offset = draws.pop("offset", 0)
+        i = 0
+        for p in range(config.num_sgd_iter):
+            index = perm[p] if perm is not None else None
+            for first in range(0, n_rows, mb):
+                rows = min(mb, n_rows - first)
+                prm = params_at(i)
+                kw = dict(draws, eps=None if eps is None else eps[i, :rows], offset=offset + i) if draws else {}
+                _, ls_grad = engine.ppo_grad_step(cols, prm, first, rows, index, stats_out=stats[i], **kw)
+                if self.world > 1:
+                    for g in engine.ppo_grad_arenas() + ([ls_grad] if train_ls else []):
+                        dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group)
+                engine.ppo_apply(prm, 1.0 / self.world, ls_grad if train_ls else None)
+                i += 1
+        return stats
+
+
 def init_from_env(backend=None):
     """torchrun-style rendezvous (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT).
     Returns (rank, world, local_rank).  No-op for a single process."""

@@ -28,6 +28,26 @@ in time order (what RLlib postprocesses as one trajectory), rows seg_start[s] ..
 On the device: `FullyConnectedPolicy.ppo_prepare` (`pvae_fc_ppo_prepare`) and `PhysicsVAE.ppo_prepare` (`pvae_ppo_prepare`,
 whose evaluate pass also names the latent draws); `segment_table` builds the segment table on the host from RLlib's
 eps_id / dones / new_obs columns.
+
+More than one worker (`run: DDPPO`, `num_workers: 8` in both specs).  DDPPO is decentralised: every worker runs the learner
+on its own train batch, and after every minibatch's backward pass the workers average their gradients, so that each takes
+the same Adam step.  The rule, with N workers and g_r the gradient that worker r's own minibatch gives (the mean over its
+own rows, as above), is that every worker applies Adam to
+
+    g = (((g_0 + g_1) + g_2) + ... + g_{N-1}) * float32(1 / N)
+
+  * the sum is in float32, in rank order; the rule holds element by element over every trained segment and the
+    state-independent log-std vector; with N == 1 it is g_0 bit for bit (`dp_mean_torch` is this formula in torch);
+  * the row counts of a minibatch may differ between the workers: the result is then the MEAN OF THE WORKERS' MEANS, as
+    DistributedDataParallel gives it, not the row-weighted mean over all rows;
+  * the stats stay each worker's own (RLlib reports learner stats per worker); advantages are standardised per worker, so
+    `ppo_prepare` needs nothing;
+  * every worker must issue the same number of steps (`dp_steps`; `ppo_learn` checks it once per call);
+  * the rank does not enter the Philox stream: distinct latent draws per worker come from distinct seeds, as for any two
+    modules.
+`ppo_learn(..., dp=parallel.PPODataParallel(...))` runs it: inside the fused step's Adam launch over peer-mapped gradient
+buffers (transport "p2p"), or per minibatch `*_ppo_grad`, a SUM all-reduce over `torch.distributed`, `*_ppo_apply` with
+grad_scale = 1 / N (transport "torch": what nccl runs between GPUs and gloo anywhere).
 """
 import math
 
@@ -237,3 +257,31 @@ def batch_columns(batch):
     if missing:
         raise KeyError("sample batch lacks %s" % ", ".join(missing))
     return {v: batch[k] for k, v in SAMPLE_BATCH_KEYS.items()}
+
+
+def dp_mean_torch(grads):
+    """The gradient-averaging rule of the module docstring in torch: `grads` is the list of the workers' gradients in rank
+    order (tensors of one shape and dtype); returns (((g_0 + g_1) + g_2) + ...) * dtype(1 / N).  One worker: g_0 itself."""
+    total = grads[0].clone()
+    for g in grads[1:]:
+        total = total + g
+    return total * torch.tensor(1.0 / len(grads), dtype=total.dtype, device=total.device)
+
+
+def dp_steps(n_rows, minibatch, num_sgd_iter):
+    """Steps of one `ppo_learn` call on a train batch of `n_rows` rows: every pass ends with a short minibatch."""
+    n_rows, minibatch, num_sgd_iter = int(n_rows), int(minibatch), int(num_sgd_iter)
+    assert n_rows >= 1 and minibatch >= 1 and num_sgd_iter >= 1
+    return num_sgd_iter * ((n_rows + minibatch - 1) // minibatch)
+
+
+def dp_check_steps(rows_by_rank, minibatch, num_sgd_iter):
+    """Every worker must issue the same number of steps (each step is one exchange): returns that number, or raises a
+    ValueError that names the ranks whose train batches give another count than rank 0's."""
+    steps = [dp_steps(n, minibatch, num_sgd_iter) for n in rows_by_rank]
+    odd = [r for r, s in enumerate(steps) if s != steps[0]]
+    if odd:
+        raise ValueError("train batches of %s rows at sgd_minibatch_size %d give %s steps: rank(s) %s would issue another "
+                         "number of gradient exchanges than rank 0" % (list(map(int, rows_by_rank)), minibatch, steps,
+                                                                      ", ".join(map(str, odd))))
+    return steps[0]
