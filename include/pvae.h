@@ -849,7 +849,13 @@ int pvae_gae_sizeof(int which);
  *   pvae_ppo_launches  kernel launches of the last step.
  *   pvae_ppo_sizeof    sizeof(pvae_fc_ppo_params) / sizeof(pvae_fc_ppo_batch) / sizeof(pvae_config): which = 0 / 1 / 2
  * Needs lookahead 1, prior ZERO_MEAN or NONE, no helper stack.  Bad arguments, an unbound buffer or rows > max_batch return a
- * negative code and launch nothing. */
+ * negative code and launch nothing.  Within that, nothing else about the configuration is refused, and all of it is tested
+ * against float64 (tests/test_gpu_ppo_vae_shapes.py, the evaluate pass below included): input subsets on either stack
+ * (te_inputs / md_inputs; the columns outside a window stay exactly zero in parameters, gradients and both moments, and
+ * under md_inputs = BODY the encoder's whole gradient is exactly zero), stacks given layer by layer (layer_width / layer_act:
+ * a width and an activation per layer, depths that differ between encoder, decoder and value branch), both priors (NONE:
+ * the encoder's output is Z wide), noise = 0 (the logvar half of the encoder's output layer then has gradient exactly zero),
+ * every train_mask, 1 .. 4 rows, Z = 1 and Da = 1. */
 size_t pvae_ppo_workspace_bytes(const pvae_config* cfg);
 int pvae_ppo_bind(pvae_ctx* ctx, float* grad, float* m, float* v, void* scratch, size_t scratch_bytes, float* log_std,
                   float* log_std_m, float* log_std_v, pvae_fc* value);
