@@ -984,6 +984,76 @@ int pvae_ppo_prepare(pvae_ctx* ctx, const pvae_fc_rollout* rollout, const pvae_g
                      void* stream);
 int pvae_ppo_gae_launches(pvae_ctx* ctx, int32_t* evaluate, int32_t* rest);
 
+/* ---- Action sampling: the rollout worker's policy step (RLlib's compute_actions) for both PPO policies -----------------
+ * The producer of the sampler's own columns that both *_ppo_prepare calls take as given: from the observations of the
+ * n_rows vectorised environments of one step to the sampled actions, action_dist_inputs = [mean | log_std], action_logp and
+ * vf_preds, in ONE library call with no host synchronisation.  Both specs sample a diagonal Gaussian (loco_imitation.yaml:1,35
+ * and loco_runtime_physics_vae.yaml:1,36: `run: DDPPO`, `clip_actions: true`); the reference leaves this to RLlib's
+ * TorchDiagGaussian + StochasticSampling, so there is no reference line to cite.
+ *
+ * The rule, for row r with the policy's mean[r], l[r] = log_std (by kind, exactly as the evaluate epilogue forms it, ls_base +
+ * included) and standard-normal noise n[r], all [k]:
+ *   explore 1:  action[j] = fmaf(expf(l[j]), n[j], mean[j]);  action_logp = the log-density of the STORED float32 action by the
+ *               evaluate epilogue's arithmetic, term for term and in its summation order -- never formed from n --, so that
+ *               *_ppo_evaluate over the same observation and the returned action gives the same bits and the learner's
+ *               first step sees a ratio of 1
+ *   explore 0:  action = mean bit for bit, action_logp = 0, no noise drawn, read or written
+ *   always:     old_dist = [mean | l] and vf_preds = value: the evaluate epilogue's bits
+ * The stored actions are unclipped (what a sample batch holds); with clip = 1 a second output env_actions =
+ * min(max(action, clip_low), clip_high) is what the environment takes.
+ *
+ * Noise: supplied ([n_rows][k]) or Philox4x32-10 at (rng_seed, rng_offset + chunk), counter row = the row within its chunk,
+ * group = 0x80000000 + (j >> 2) for columns 4 (j >> 2) .. + 3: the high bit keeps the action noise apart from PhysicsVAE's
+ * latent draws (groups < Z / 4) under one (seed, offset).  The noise used is written to noise_out, as the latent draws are:
+ * Philox goes through hardware transcendentals and cannot be reproduced on the host.
+ *
+ * Destination rows.  Row r of the call is written to row dst = out_row ? out_row[r] : r of EVERY output column (out_row
+ * clamped into [0, n_dst_rows): a bad table gives wrong numbers, never an access outside the columns); with obs_dst the
+ * row's observation is copied to obs_dst[dst] as well, so that after T steps a train batch's columns are complete with no
+ * copy.  Inputs (obs, noise, draws->eps) are read at r.
+ *
+ * Launches: exactly those of the evaluate pass over the same rows (per chunk of max_batch rows: copy-in, one per layer
+ * depth -- for PhysicsVAE TE layers, sampler, MD layers, value layers --, ONE epilogue, the sampling one in place of the
+ * evaluate one), reported by *_gae_launches under `evaluate` (rest = 0).  Plain stores, no atomics, no allocation: the
+ * same inputs give the same bits.  The parameters are not written.
+ *
+ *   pvae_fc_ppo_act      a stack set [policy, value(, log-std)]; params->log_std_kind / log_std_base as for
+ *                        pvae_fc_ppo_evaluate (gamma, lambda, standardize are not read); pvae_fc_ppo_bind must have been
+ *                        called for kinds 0 and 1 (the log-std vector is the one bound there)
+ *   pvae_ppo_act         PhysicsVAE; `draws`: the latent draws as for pvae_ppo_evaluate (eps read at r, eps_out written at
+ *                        dst: [n_dst_rows][Z]); pvae_ppo_bind must have been called; needs what pvae_ppo_evaluate needs
+ *   pvae_ppo_act_sizeof  sizeof(pvae_ppo_act_in) / sizeof(pvae_ppo_act_out) as the library was compiled: which = 0 / 1
+ * Bad arguments (a null struct, k that is not the policy's width, a log_std_kind that does not fit the stacks, an unbound
+ * buffer, explore or clip not 0 or 1, n_rows < 1, n_dst_rows < n_rows without out_row, clip_low > clip_high, clip without
+ * env_actions or env_actions without clip, a null obs or a null required output) return a negative code and launch nothing. */
+typedef struct pvae_ppo_act_in {
+    const float* obs;             /* [n_rows][n_in] (PhysicsVAE: n_in = 2 Db) */
+    const float* noise;           /* [n_rows][k] standard-normal draws, or NULL: Philox; never read with explore 0 */
+    const int32_t* out_row;       /* [n_rows] destination rows, or NULL: row r goes to row r */
+    int64_t n_rows;               /* >= 1; above max_batch the call runs in chunks */
+    int64_t n_dst_rows;           /* rows of every output column; without out_row >= n_rows */
+    int32_t k;                    /* actions per row */
+    int32_t explore;              /* 0 or 1 */
+    uint64_t rng_seed, rng_offset; /* Philox: chunk i draws at (rng_seed, rng_offset + i) */
+    int32_t clip;                 /* 0 or 1; 1 and out->env_actions go together: both or neither */
+    float clip_low, clip_high;    /* clip 1: clip_low <= clip_high */
+    int32_t reserved;
+} pvae_ppo_act_in;
+typedef struct pvae_ppo_act_out { /* every pointer: a column of n_dst_rows rows */
+    float* actions;               /* [n_dst_rows][k], unclipped */
+    float* env_actions;           /* [n_dst_rows][k], or NULL (clip 0) */
+    float* old_dist;              /* [n_dst_rows][2k] = [mean | log_std] */
+    float* old_logp;              /* [n_dst_rows] */
+    float* vf_preds;              /* [n_dst_rows] */
+    float* noise_out;             /* [n_dst_rows][k] the noise used, or NULL: not wanted; not written with explore 0 */
+    float* obs_dst;               /* [n_dst_rows][n_in], or NULL: the observations are not copied */
+} pvae_ppo_act_out;
+int pvae_fc_ppo_act(pvae_fc* fc, const pvae_ppo_act_in* in, const pvae_gae_params* params, const pvae_ppo_act_out* out,
+                    void* stream);
+int pvae_ppo_act(pvae_ctx* ctx, const pvae_ppo_act_in* in, const pvae_gae_params* params, const pvae_ppo_draws* draws,
+                 const pvae_ppo_act_out* out, void* stream);
+int pvae_ppo_act_sizeof(int which);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

@@ -117,6 +117,19 @@ class PpoDraws(C.Structure):
                 ("rng_seed", C.c_uint64), ("rng_offset", C.c_uint64)]
 
 
+class PpoActIn(C.Structure):
+    """pvae_ppo_act_in: one policy step's observations, the action noise (supplied or Philox), the destination rows."""
+    _fields_ = [("obs", C.c_void_p), ("noise", C.c_void_p), ("out_row", C.c_void_p), ("n_rows", C.c_int64),
+                ("n_dst_rows", C.c_int64), ("k", C.c_int32), ("explore", C.c_int32), ("rng_seed", C.c_uint64),
+                ("rng_offset", C.c_uint64), ("clip", C.c_int32), ("clip_low", C.c_float), ("clip_high", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class PpoActOut(C.Structure):
+    """pvae_ppo_act_out: device pointers to the columns a policy step writes, each of n_dst_rows rows."""
+    _fields_ = [(n, C.c_void_p) for n in ("actions", "env_actions", "old_dist", "old_logp", "vf_preds", "noise_out", "obs_dst")]
+
+
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
 
 _P = C.c_void_p
@@ -244,6 +257,9 @@ _SIGS = {
     "pvae_ppo_prepare": (C.c_int, [_P, C.POINTER(FcRollout), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(FcPrepared),
                                    _P, C.c_size_t, _P]),
     "pvae_ppo_gae_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pvae_fc_ppo_act": (C.c_int, [_P, C.POINTER(PpoActIn), C.POINTER(GaeParams), C.POINTER(PpoActOut), _P]),
+    "pvae_ppo_act": (C.c_int, [_P, C.POINTER(PpoActIn), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(PpoActOut), _P]),
+    "pvae_ppo_act_sizeof": (C.c_int, [C.c_int]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),

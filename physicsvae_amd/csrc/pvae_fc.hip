@@ -626,20 +626,22 @@ int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, 
     return 0;
 }
 
-// rows of the rollout through all stacks in chunks of max_batch: copy-in, one launch per depth, the epilogue
-int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, hipStream_t st,
-              int& launches) {
+// rows [n_rows][n_in] of `obs` through all stacks in chunks of max_batch: copy-in, one launch per depth, then the chunk's
+// epilogue -- epi(panels, first row, chunk index) launches it (the evaluate one, or the sampling one of pvae_fc_ppo_act)
+template <class Epi>
+int eval_rows(pvae_fc* c, const float* obs, long long n_rows, int k, const pvae_gae_params* p, hipStream_t st, int& launches,
+              Epi&& epi) {
     const FcLayout& L = c->L;
-    const int k = ro->k;
-    for (long long first = 0; first < ro->n_rows; first += L.cfg.max_batch) {
-        const int rows = (int)(ro->n_rows - first < L.cfg.max_batch ? ro->n_rows - first : L.cfg.max_batch);
+    uint64_t i = 0;
+    for (long long first = 0; first < n_rows; first += L.cfg.max_batch, ++i) {
+        const int rows = (int)(n_rows - first < L.cfg.max_batch ? n_rows - first : L.cfg.max_batch);
         Run r{c, st, rows, pad32(rows)};
         for (int s = 0; s < L.S; ++s) r.want[s] = true;
         set_range(r, L.S);
         int rc;
-        if ((rc = copy_in(r, ro->obs + (size_t)first * L.cfg.n_in))) return rc;
+        if ((rc = copy_in(r, obs + (size_t)first * L.cfg.n_in))) return rc;
         if ((rc = run_forward(r, nullptr))) return rc;
-        PpoEval e;
+        PpoPanels e;
         memset(&e, 0, sizeof(e));
         const int lp = (int)L.stack[0].size() - 1, lv = (int)L.stack[1].size() - 1;
         e.mean = act_ptr(c, 0, lp); e.ld_mean = panel_ld(c, 0, lp);
@@ -650,13 +652,23 @@ int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, c
         } else {
             e.ls = c->log_std; e.ld_ls = 0;
         }
-        e.actions = ro->actions + (size_t)first * k;
         e.rows = rows; e.k = k;
-        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
-        if ((rc = ppo_eval_launch(e, st))) return rc;
+        if ((rc = epi(e, first, i))) return rc;
         launches += r.launches + 1;
     }
     return 0;
+}
+int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, hipStream_t st,
+              int& launches) {
+    const int k = ro->k;
+    return eval_rows(c, ro->obs, ro->n_rows, k, p, st, launches, [&](const PpoPanels& pan, long long first, uint64_t) {
+        PpoEval e;
+        memset(&e, 0, sizeof(e));
+        static_cast<PpoPanels&>(e) = pan;
+        e.actions = ro->actions + (size_t)first * k;
+        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
+        return ppo_eval_launch(e, st);
+    });
 }
 
 // one stack alone, as PhysicsVAE's learner and the bootstrap pass run the value function
@@ -1018,6 +1030,33 @@ int pvae_fc_ppo_prepare(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_pa
         return rc;
     c->eval_launches = ev; c->gae_launches = rest;
     return 0;
+}
+
+int pvae_fc_ppo_act(pvae_fc* c, const pvae_ppo_act_in* in, const pvae_gae_params* p, const pvae_ppo_act_out* out, void* stream) {
+    if (!c) return fail(-1, "null stack set");
+    if (!in || !p || !out) return fail(-1, "null in, params or out");
+    // the model's side of the checks is evaluate's: the same rows, the action column the one written here
+    pvae_fc_rollout ro;
+    pvae_fc_prepared ev;
+    act_as_evaluate(in, out, ro, ev);
+    int rc = check_eval(c, &ro, p, &ev, true);
+    if (rc) return rc;
+    if ((rc = check_act(in, out))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int launches = 0;
+    rc = eval_rows(c, in->obs, in->n_rows, in->k, p, st, launches, [&](const PpoPanels& pan, long long first, uint64_t i) {
+        PpoAct a;
+        fill_act(a, pan, in, out, first, i, c->L.cfg.n_in);
+        return ppo_act_launch(a, st);
+    });
+    if (rc) return rc;
+    c->eval_launches = launches; c->gae_launches = 0;
+    return 0;
+}
+
+int pvae_ppo_act_sizeof(int which) {
+    return which == 0 ? (int)sizeof(pvae_ppo_act_in) : which == 1 ? (int)sizeof(pvae_ppo_act_out)
+                                                                  : fail(-1, "which must be 0 or 1");
 }
 
 int pvae_fc_gae_launches(pvae_fc* c, int32_t* evaluate, int32_t* rest) {

@@ -672,20 +672,46 @@ int zero_rows_launch(const ZeroRows& z, hipStream_t st);
 // `done`: row r with done[r] is zeros and its source row is never read
 int pad_copy_launch(const float* src, int n, int rows, float* dst, int ld, int rows_pad, const int32_t* index, long long n_rows,
                     const uint8_t* done, hipStream_t st);
-// The evaluate epilogue of one chunk on any panels: vf[r], dist[r] = [mean | ls] and logp[r] of actions[r] for rows
-// r < rows (pointers: the chunk's first row), and, eps_dst given, the chunk's draws eps_src [rows][Z] copied out.
-// mean == NULL: the bootstrap use, vf[r] = done[r] ? 0 : value[r].
-struct PpoEval {
+// The outputs of one evaluated chunk where its stacks left them: row r of mean / ls / value at r * ld_* (ls: the bound
+// vector with ld_ls 0, or the third stack's panel with ls_base), and PhysicsVAE's latent draws eps_src [rows][Z].
+struct PpoPanels {
     const float* mean; const float* ls; const float* value;
     long long ld_mean, ld_ls, ld_value;
     float ls_base;
+    int rows, k;
+    const float* eps_src; int Z;
+};
+// The evaluate epilogue of one chunk on any panels: vf[r], dist[r] = [mean | ls] and logp[r] of actions[r] for rows
+// r < rows (pointers: the chunk's first row), and, eps_dst given, the chunk's draws eps_src [rows][Z] copied out.
+// mean == NULL: the bootstrap use, vf[r] = done[r] ? 0 : value[r].
+struct PpoEval : PpoPanels {
     const float* actions;
     const uint8_t* done;
-    int rows, k;
     float* vf; float* dist; float* logp;
-    const float* eps_src; float* eps_dst; int Z;
+    float* eps_dst;
 };
 int ppo_eval_launch(const PpoEval& e, hipStream_t st);
+// The sampling epilogue of one chunk (include/pvae.h "Action sampling"): the evaluate epilogue with the action drawn
+// instead of read.  Row r of the chunk goes to row dst = out_row ? clamp(out_row[r], [0, n_dst_rows)) : row0 + r of the
+// caller's columns, whose BASE pointers the output fields are; noise / obs / out_row: the chunk's first row.
+struct PpoAct : PpoPanels {
+    const float* noise;                   // [rows][k] supplied draws, or null: Philox (explore only)
+    const int32_t* out_row;               // [rows], or null
+    long long row0, n_dst_rows;
+    int explore, clip;
+    float clip_low, clip_high;
+    unsigned long long seed, offset;
+    float* actions; float* env_actions; float* dist; float* logp; float* vf; float* noise_out;
+    const float* obs; float* obs_dst; int n_in;
+    float* eps_dst;
+};
+int ppo_act_launch(const PpoAct& a, hipStream_t st);
+// what both sampling entry points ask of their in / out structs beyond their model's check_eval
+int check_act(const pvae_ppo_act_in* in, const pvae_ppo_act_out* out);
+// the evaluate call over the same rows whose action column is the one a sampling call writes: what check_eval is given
+void act_as_evaluate(const pvae_ppo_act_in* in, const pvae_ppo_act_out* out, pvae_fc_rollout& ro, pvae_fc_prepared& ev);
+void fill_act(PpoAct& a, const PpoPanels& pan, const pvae_ppo_act_in* in, const pvae_ppo_act_out* out, long long first,
+              uint64_t chunk, int n_in);
 // GAE: the argument checks, and the GAE launch + (params->standardize) the rescale launch; `launches` counts them
 int check_gae_params(const pvae_gae_params* p);
 int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out);

@@ -256,19 +256,21 @@ int check_eval(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p,
 
 int eval_chunk(const pvae_ctx* c, const FcValueStack& vs) { return std::min(c->L.cfg.max_batch, vs.max_batch); }
 
-// rows of the rollout through encoder, sampler, decoder and value stack in chunks of max_batch:
-// copy-in | TE layers | sampler | MD layers | value layers | epilogue
-int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_ppo_draws* d,
-              const pvae_fc_prepared* out, hipStream_t st, int& launches) {
+// rows [n_rows][2 Db] of `obs` through encoder, sampler, decoder and value stack in chunks of max_batch:
+// copy-in | TE layers | sampler | MD layers | value layers | the chunk's epilogue -- epi(panels, first row, chunk index)
+// launches it (the evaluate one, or the sampling one of pvae_ppo_act)
+template <class Epi>
+int eval_rows(pvae_ctx* c, const FcValueStack& vs, const float* obs, long long n_rows, int k, const pvae_ppo_draws* d,
+              hipStream_t st, int& launches, Epi&& epi) {
     const pvae_config& cfg = c->L.cfg;
-    const int Z = cfg.latent, k = ro->k, chunk = eval_chunk(c, vs);
+    const int Z = cfg.latent, chunk = eval_chunk(c, vs);
     const Layer& md_last = c->L.net[PVAE_NET_MD].layers.back();
     uint64_t i = 0;
-    for (long long first = 0; first < ro->n_rows; first += chunk, ++i) {
-        const int rows = (int)(ro->n_rows - first < chunk ? ro->n_rows - first : chunk);
+    for (long long first = 0; first < n_rows; first += chunk, ++i) {
+        const int rows = (int)(n_rows - first < chunk ? n_rows - first : chunk);
         int rc;
         ppo_enter(c, rows);
-        if ((rc = ppo_copy_in(c, vs, ro->obs, nullptr, first, ro->n_rows, rows, st))) return rc;
+        if ((rc = ppo_copy_in(c, vs, obs, nullptr, first, n_rows, rows, st))) return rc;
         ++launches;
         if ((rc = ppo_forward_net(c, PVAE_NET_TE, rows, st, &launches))) return rc;
         if ((rc = ppo_sampler(c, d->eps ? d->eps + (size_t)first * Z : nullptr, rows, d->noise, d->rng_seed, d->rng_offset + i, st,
@@ -276,19 +278,30 @@ int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, co
             return rc;
         if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
         if ((rc = fc_value_forward(c->ppo.value, 0, rows, st, &launches))) return rc;
-        PpoEval e;
+        PpoPanels e;
         memset(&e, 0, sizeof(e));
         e.mean = c->ws + c->W.net[PVAE_NET_MD].act.back(); e.ld_mean = md_last.n_out_pad;
         e.ls = c->ppo.log_std;
         e.value = vs.value; e.ld_value = vs.ld_value;
-        e.actions = ro->actions + (size_t)first * k;
         e.rows = rows; e.k = k;
-        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
-        if (d->eps_out) { e.eps_src = c->ws + c->W.eps; e.eps_dst = d->eps_out + (size_t)first * Z; e.Z = Z; }
-        if ((rc = ppo_eval_launch(e, st))) return rc;
+        e.eps_src = c->ws + c->W.eps; e.Z = Z;
+        if ((rc = epi(e, first, i))) return rc;
         ++launches;
     }
     return 0;
+}
+int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_ppo_draws* d,
+              const pvae_fc_prepared* out, hipStream_t st, int& launches) {
+    const int k = ro->k;
+    return eval_rows(c, vs, ro->obs, ro->n_rows, k, d, st, launches, [&](const PpoPanels& pan, long long first, uint64_t) {
+        PpoEval e;
+        memset(&e, 0, sizeof(e));
+        static_cast<PpoPanels&>(e) = pan;
+        e.actions = ro->actions + (size_t)first * k;
+        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
+        if (d->eps_out) e.eps_dst = d->eps_out + (size_t)first * pan.Z;
+        return ppo_eval_launch(e, st);
+    });
 }
 
 }  // namespace
@@ -480,6 +493,31 @@ int pvae_ppo_prepare(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_para
                       ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))
         return rc;
     c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
+    return 0;
+}
+
+int pvae_ppo_act(pvae_ctx* c, const pvae_ppo_act_in* in, const pvae_gae_params* p, const pvae_ppo_draws* d,
+                 const pvae_ppo_act_out* out, void* stream) {
+    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
+    if (!in || !p || !out) return fail(-1, "null in, params or out");
+    // the model's side of the checks is evaluate's: the same rows, the action column the one written here
+    pvae_fc_rollout ro;
+    pvae_fc_prepared ev;
+    act_as_evaluate(in, out, ro, ev);
+    FcValueStack vs;
+    int rc = check_eval(c, &ro, p, d, &ev, true, &vs);
+    if (rc) return rc;
+    if ((rc = check_act(in, out))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int launches = 0;
+    rc = eval_rows(c, vs, in->obs, in->n_rows, in->k, d, st, launches, [&](const PpoPanels& pan, long long first, uint64_t i) {
+        PpoAct a;
+        fill_act(a, pan, in, out, first, i, vs.n_in);
+        a.eps_dst = d->eps_out;
+        return ppo_act_launch(a, st);
+    });
+    if (rc) return rc;
+    c->ppo.eval_launches = launches;
     return 0;
 }
 

@@ -1,8 +1,9 @@
 // pvae_ppo_core.hip -- what the on-device PPO learner holds that no model owns (include/pvae.h "PPO learner step",
-// "Train-batch preparation"): the loss head and its finishing reduction, the Adam + stats launch, the evaluate epilogue,
-// the pad copy, the zero-rows launch, GAE and standardisation, their argument checks, and the entry points that need no
-// model at all (pvae_ppo_loss, pvae_gae).  The stack set's learner (pvae_fc.hip) and PhysicsVAE's (pvae_ppo.hip) fill the
-// argument structs of pvae_internal.h from their own panels and call the launch functions here: one kernel per job.
+// "Train-batch preparation", "Action sampling"): the loss head and its finishing reduction, the Adam + stats launch, the
+// evaluate and the sampling epilogue, the pad copy, the zero-rows launch, GAE and standardisation, their argument checks,
+// and the entry points that need no model at all (pvae_ppo_loss, pvae_gae).  The stack set's learner (pvae_fc.hip) and
+// PhysicsVAE's (pvae_ppo.hip) fill the argument structs of pvae_internal.h from their own panels and call the launch
+// functions here: one kernel per job.
 #include "pvae_internal.h"
 
 #include <mutex>
@@ -333,6 +334,17 @@ ppo_zero_rows_kernel(ZeroRows z) {
 // vf[r] = done[r] ? 0 : value[r].  The output pointers are those of the chunk's first row.  eps_dst (PhysicsVAE's evaluate
 // pass): the latent draws of the chunk, eps_src [rows][Z], copied to the caller's rows.
 constexpr int kEvalMaxBlocks = 1024;
+// the log-density's arithmetic, shared by the evaluate and the sampling epilogue so that both give the same bits:
+// one column's terms into the lane's sums, and lane 0's closing expression over the wave sums
+__device__ inline void logp_column(float a, float mu, float l, float& zz, float& lss) {
+    const float inv_sig = expf(-l);
+    const float z = (a - mu) * inv_sig;
+    zz = fmaf(z, z, zz);
+    lss += l;
+}
+__device__ inline float logp_close(float zz, float lss, int k) {
+    return -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                               // log(2 pi)
+}
 __global__ void __launch_bounds__(256)
 ppo_eval_epilogue_kernel(PpoEval e) {
     const int lane = threadIdx.x & 63;
@@ -349,20 +361,76 @@ ppo_eval_epilogue_kernel(PpoEval e) {
         float* dist = e.dist + (size_t)r * 2 * k;
         float zz = 0.f, lss = 0.f;
         for (int j = lane; j < k; j += 64) {
-            const float l = e.ls_base + ls[j], inv_sig = expf(-l);
-            const float z = (act[j] - mu[j]) * inv_sig;
-            zz = fmaf(z, z, zz);
-            lss += l;
+            const float l = e.ls_base + ls[j];
+            logp_column(act[j], mu[j], l, zz, lss);
             dist[j] = mu[j];
             dist[k + j] = l;
         }
         zz = wave_sum(zz); lss = wave_sum(lss);
         if (lane == 0) {
-            e.logp[r] = -0.5f * zz - lss - 0.5f * k * 1.8378770664093453f;                  // log(2 pi)
+            e.logp[r] = logp_close(zz, lss, k);
             e.vf[r] = e.value[r * e.ld_value];
         }
         if (e.eps_dst)
             for (int j = lane; j < e.Z; j += 64) e.eps_dst[(size_t)r * e.Z + j] = e.eps_src[(size_t)r * e.Z + j];
+    }
+}
+
+// The sampling epilogue of one chunk (include/pvae.h "Action sampling"): a wave per row, lane l holds columns l, l + 64,
+// ... as in the evaluate epilogue, so that the log-density's sums run in its order.  Lanes 4q .. 4q + 3 hold the four
+// columns of one Philox group: lane 4q makes the call (row = the chunk's row, group = 0x80000000 + column / 4: the high
+// bit keeps the action noise apart from the latent draws, whose groups are < Z / 4) and the other three read their
+// component from it; a tail group is used in part.  The log-density is that of the STORED float32 action, never formed
+// from the noise.  Every destination row is clamped into [0, n_dst_rows); plain stores, no atomics.
+__global__ void __launch_bounds__(256)
+ppo_act_epilogue_kernel(PpoAct a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
+    const int k = a.k;
+    for (int r = wave; r < a.rows; r += waves) {
+        const long long dst = batch_row(a.out_row, a.row0, a.n_dst_rows, r);
+        const float* mu = a.mean + r * a.ld_mean;
+        const float* ls = a.ls + r * a.ld_ls;
+        float* act = a.actions + (size_t)dst * k;
+        float* dist = a.dist + (size_t)dst * 2 * k;
+        float zz = 0.f, lss = 0.f;
+        for (int j0 = 0; j0 < k; j0 += 64) {                     // (wave-uniform trip count: the shuffles below need every lane)
+            const int j = j0 + lane;
+            const bool live = j < k;
+            float n = 0.f;
+            if (a.explore) {
+                if (a.noise) {
+                    if (live) n = a.noise[(size_t)r * k + j];
+                } else {
+                    v4f g = v4f{0.f, 0.f, 0.f, 0.f};
+                    if ((lane & 3) == 0 && live) g = philox_normal4(a.seed, a.offset, (uint32_t)r, 0x80000000u + (uint32_t)(j >> 2));
+                    const int src = lane & ~3;
+                    const float g0 = __shfl(g[0], src, 64), g1 = __shfl(g[1], src, 64);
+                    const float g2 = __shfl(g[2], src, 64), g3 = __shfl(g[3], src, 64);
+                    const int c = lane & 3;
+                    n = c == 0 ? g0 : c == 1 ? g1 : c == 2 ? g2 : g3;
+                }
+            }
+            if (live) {
+                const float m = mu[j], l = a.ls_base + ls[j];
+                const float x = a.explore ? fmaf(expf(l), n, m) : m;
+                logp_column(x, m, l, zz, lss);
+                act[j] = x;
+                if (a.env_actions) a.env_actions[(size_t)dst * k + j] = fminf(fmaxf(x, a.clip_low), a.clip_high);
+                dist[j] = m;
+                dist[k + j] = l;
+                if (a.explore && a.noise_out) a.noise_out[(size_t)dst * k + j] = n;
+            }
+        }
+        zz = wave_sum(zz); lss = wave_sum(lss);
+        if (lane == 0) {
+            a.logp[dst] = a.explore ? logp_close(zz, lss, k) : 0.f;
+            a.vf[dst] = a.value[r * a.ld_value];
+        }
+        if (a.eps_dst)
+            for (int j = lane; j < a.Z; j += 64) a.eps_dst[(size_t)dst * a.Z + j] = a.eps_src[(size_t)r * a.Z + j];
+        if (a.obs_dst)
+            for (int j = lane; j < a.n_in; j += 64) a.obs_dst[(size_t)dst * a.n_in + j] = a.obs[(size_t)r * a.n_in + j];
     }
 }
 
@@ -660,6 +728,46 @@ int ppo_eval_launch(const PpoEval& e, hipStream_t st) {
     hipLaunchKernelGGL(ppo_eval_epilogue_kernel, dim3(blocks), dim3(256), 0, st, e);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ppo_act_launch(const PpoAct& a, hipStream_t st) {
+    int blocks = (a.rows + 3) / 4;
+    if (blocks > kEvalMaxBlocks) blocks = kEvalMaxBlocks;
+    hipLaunchKernelGGL(ppo_act_epilogue_kernel, dim3(blocks), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int check_act(const pvae_ppo_act_in* in, const pvae_ppo_act_out* out) {
+    if (in->explore != 0 && in->explore != 1) return fail(-1, "explore must be 0 or 1, got %d", in->explore);
+    if (in->n_dst_rows < 1 || in->n_dst_rows > 0x7fffffffll) return fail(-1, "n_dst_rows %lld out of range", (long long)in->n_dst_rows);
+    if (!in->out_row && in->n_dst_rows < in->n_rows)
+        return fail(-1, "n_dst_rows %lld < n_rows %lld without out_row", (long long)in->n_dst_rows, (long long)in->n_rows);
+    if (in->clip != 0 && in->clip != 1) return fail(-1, "clip must be 0 or 1, got %d", in->clip);
+    if ((in->clip != 0) != (out->env_actions != nullptr)) return fail(-1, "clip and env_actions go together: both or neither");
+    if (in->clip && !(in->clip_low <= in->clip_high)) return fail(-1, "clip_low %g > clip_high %g", in->clip_low, in->clip_high);
+    return 0;
+}
+
+void act_as_evaluate(const pvae_ppo_act_in* in, const pvae_ppo_act_out* out, pvae_fc_rollout& ro, pvae_fc_prepared& ev) {
+    memset(&ro, 0, sizeof(ro));
+    ro.obs = in->obs; ro.actions = out->actions; ro.n_rows = in->n_rows; ro.k = in->k;
+    memset(&ev, 0, sizeof(ev));
+    ev.vf_preds = out->vf_preds; ev.old_dist = out->old_dist; ev.old_logp = out->old_logp;
+}
+
+void fill_act(PpoAct& a, const PpoPanels& pan, const pvae_ppo_act_in* in, const pvae_ppo_act_out* out, long long first,
+              uint64_t chunk, int n_in) {
+    memset((void*)&a, 0, sizeof(a));
+    static_cast<PpoPanels&>(a) = pan;
+    a.noise = in->explore && in->noise ? in->noise + (size_t)first * in->k : nullptr;
+    a.out_row = in->out_row ? in->out_row + first : nullptr;
+    a.row0 = first; a.n_dst_rows = in->n_dst_rows;
+    a.explore = in->explore; a.clip = in->clip; a.clip_low = in->clip_low; a.clip_high = in->clip_high;
+    a.seed = in->rng_seed; a.offset = in->rng_offset + chunk;
+    a.actions = out->actions; a.env_actions = in->clip ? out->env_actions : nullptr;
+    a.dist = out->old_dist; a.logp = out->old_logp; a.vf = out->vf_preds; a.noise_out = out->noise_out;
+    a.obs = in->obs + (size_t)first * n_in; a.obs_dst = out->obs_dst; a.n_in = n_in;
 }
 
 int check_gae_params(const pvae_gae_params* p) {

@@ -1078,6 +1078,25 @@ class HipEngine:
         res["latent_eps"] = used
         return res
 
+    def ppo_act(self, obs, params, explore=True, noise=None, clip=None, eps=None, latent_noise=True, seed=0, offset=0,
+                out=None, out_row=None):
+        """`pvae_ppo_act`: one policy step -- the sampled actions, old_dist = [a_hat | log_std], old_logp of the stored
+        action, vf_preds, the action noise used and latent_eps [., Z], the latent draws used -- in the launches of the
+        evaluate pass over the same rows.  `eps` [n, Z] / `latent_noise`: the latent draws as `ppo_evaluate` takes them;
+        the action noise and the latent draws share (seed, offset + chunk).  The rest as `make_act`.  `ppo_bind` must have
+        been called.  Returns the dict of columns; nothing synchronises."""
+        self._need_gpu()
+        i, o, res, keep = make_act(obs, 2 * self.arch.Db, self.arch.Da, self.device, explore, noise, clip, seed, offset, out,
+                                   out_row, latent=self.arch.Z)
+        d = _lib.PpoDraws()
+        eps = self._ppo_eps(eps, (int(i.n_rows), self.arch.Z))
+        d.eps = eps.data_ptr() if eps is not None else None
+        d.eps_out = res["latent_eps"].data_ptr()
+        d.noise, d.rng_seed, d.rng_offset = 1 if latent_noise else 0, int(seed), int(offset)
+        _lib.check(self.lib.pvae_ppo_act(self.ctx, C.byref(i), C.byref(params), C.byref(d), C.byref(o), self._stream()),
+                   "pvae_ppo_act")
+        return res
+
     def gae_launches(self):
         """(evaluate, rest): kernel launches of the last ppo_prepare / ppo_evaluate -- the pass over the rows, and bootstrap +
         GAE + standardisation."""
@@ -1357,6 +1376,16 @@ class StackSetEngine:
             res.update({name: rollout[name] for name in ("vf_preds", "old_dist", "old_logp")})
         return res
 
+    def ppo_act(self, obs, params, explore=True, noise=None, clip=None, seed=0, offset=0, out=None, out_row=None):
+        """`pvae_fc_ppo_act`: one policy step -- the sampled actions, old_dist = [mean | log_std], old_logp of the stored
+        action, vf_preds and the action noise used -- in the launches of the evaluate pass over the same rows.  `params`:
+        `PPOConfig.gae_params(kind, base)` (the log-std kind; the vector of kinds 0 / 1 is the one `ppo_bind` bound); the
+        rest as `make_act`.  Returns the dict of columns; nothing synchronises."""
+        self._need_gpu()
+        i, o, res, keep = make_act(obs, self.n_in, self.n_outs[0], self.device, explore, noise, clip, seed, offset, out, out_row)
+        _lib.check(self.lib.pvae_fc_ppo_act(self.ctx, C.byref(i), C.byref(params), C.byref(o), self._stream()), "pvae_fc_ppo_act")
+        return res
+
     def gae_launches(self):
         """(evaluate, rest): kernel launches of the last ppo_prepare / ppo_evaluate -- the pass over the rows, and bootstrap +
         GAE + standardisation."""
@@ -1453,6 +1482,57 @@ def prepare_plan(rollout):
         raise ValueError("the sampler's vf_preds, old_dist and old_logp go together: all three or none")
     names = (() if all(given) else ("vf_preds", "old_dist", "old_logp")) + ("last_value", "advantages", "value_targets")
     return names, all(given)
+
+
+def make_act(obs, n_in, k, device, explore, noise, clip, seed, offset, out, out_row, latent=None):
+    """(pvae_ppo_act_in, pvae_ppo_act_out, {name: column}, [tensors kept alive]) of one policy step (include/pvae.h "Action
+    sampling").  obs [n, n_in]; `noise` [n, k] supplied action noise or None (Philox at (seed, offset + chunk)); `clip`:
+    None or (low, high); `out`: the caller's columns by name -- actions, env_actions (with clip), old_dist, old_logp,
+    vf_preds, action_noise, latent_eps (`latent` = Z: PhysicsVAE) and optionally obs --, every one of the same number of
+    rows, allocated with n rows where missing (obs never; action_noise only when exploring); `out_row`: int32 [n] on the
+    device, the row of those columns each input row is written to (None: row r to row r).  Shared by both engines."""
+    f32 = torch.float32
+    obs = obs.reshape(obs.shape[0], -1).to(device, f32).contiguous()
+    n = int(obs.shape[0])
+    assert tuple(obs.shape) == (n, n_in), "obs must be [n, %d], got %s" % (n_in, tuple(obs.shape))
+    out = dict(out or {})
+    n_dst = next((int(t.shape[0]) for t in out.values() if t is not None), n)
+    i, o, keep = _lib.PpoActIn(), _lib.PpoActOut(), [obs]
+    if explore and noise is not None:
+        noise = noise.to(device, f32).contiguous()
+        assert tuple(noise.shape) == (n, k), "noise must be [%d, %d], got %s" % (n, k, tuple(noise.shape))
+        keep.append(noise)
+        i.noise = noise.data_ptr()
+    if out_row is not None:
+        _check_index(out_row, n_dst, device)
+        assert out_row.numel() == n, "out_row must name one destination row per input row"
+        keep.append(out_row)
+        i.out_row = out_row.data_ptr()
+    i.obs, i.n_rows, i.n_dst_rows, i.k, i.explore = obs.data_ptr(), n, n_dst, k, 1 if explore else 0
+    i.rng_seed, i.rng_offset = int(seed), int(offset)
+    if clip is not None:
+        i.clip, i.clip_low, i.clip_high = 1, float(clip[0]), float(clip[1])
+    shapes = {"actions": (n_dst, k), "old_dist": (n_dst, 2 * k), "old_logp": (n_dst,), "vf_preds": (n_dst,)}
+    if clip is not None:
+        shapes["env_actions"] = (n_dst, k)
+    if explore or out.get("action_noise") is not None:
+        shapes["action_noise"] = (n_dst, k)
+    if latent is not None:
+        shapes["latent_eps"] = (n_dst, latent)
+    if out.get("obs") is not None:
+        shapes["obs"] = (n_dst, n_in)
+    res = {}
+    for name, shape in shapes.items():
+        t = out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=f32, device=device)
+        assert t.dtype == f32 and t.device == torch.device(device) and t.is_contiguous() and tuple(t.shape) == shape, \
+            "out[%r] must be contiguous float32 %s on %s" % (name, shape, device)
+        res[name] = t
+        field = {"action_noise": "noise_out", "obs": "obs_dst", "latent_eps": None}.get(name, name)
+        if field is not None:
+            setattr(o, field, t.data_ptr())
+    return i, o, res, keep
 
 
 def set_fc_per_stack(on):

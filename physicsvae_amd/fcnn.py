@@ -92,6 +92,11 @@ class FullyConnectedPolicy(nn.Module):
             self.__dict__["_ls_base"] = torch.as_tensor(np.asarray(self._log_std_base, dtype=np.float64) * np.ones(n_act),
                                                         dtype=torch.float32, device=self.engine.device)
         self._cur_value = None
+        self._rng_seed, self._rng_calls = 0, 0
+
+    def seed(self, seed):
+        """Key of the on-chip Philox stream `compute_actions` draws the action noise from when none is supplied."""
+        self._rng_seed, self._rng_calls = int(seed), 0
 
     # -- nn.Module plumbing ---------------------------------------------------------------
     def _apply(self, fn, recurse=True):
@@ -194,6 +199,33 @@ class FullyConnectedPolicy(nn.Module):
         return {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
                 "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
                 "value_targets": res["value_targets"], "last_value": res["last_value"]}
+
+    def compute_actions(self, obs, explore=True, noise=None, clip=None, out=None, step=None):
+        """The rollout worker's policy step, on the device (`pvae_fc_ppo_act`; the rule: `ppo.py`'s module docstring): from
+        the observations [B, n_in] of the B vectorised environments to a dict under RLlib's keys -- `actions` [B, k]
+        (unclipped), `action_dist_inputs` [B, 2k] = [mean | log_std], `action_logp` [B] and `vf_preds` [B], the columns
+        `ppo_prepare` takes as given -- plus `action_noise` [B, k], the noise used (absent with `explore` False), and, with
+        `clip` = (low, high), `env_actions`, what the environment takes.  One library call in the launches of the
+        evaluate pass, no torch op, nothing synchronised; B above `max_batch` runs in chunks.  `noise`: [B, k] standard
+        normals on the device (None: Philox from `seed()`'s key; the call counter advances by the number of chunks either
+        way, chunk i drawing at counter + 1 + i).  `out` / `step`: a `ppo.RolloutBuffer` and the step of its fragment
+        this call is -- every column (the observations too) is then written in place into the buffer's rows and the
+        returned tensors are views of them."""
+        from . import ppo as P
+        eng = self.engine
+        eng._need_gpu()
+        assert (out is None) == (step is None), "out (a RolloutBuffer) and step go together"
+        kind, base, log_std, train_ls = self._ppo_log_std()
+        eng.ppo_bind(log_std, train_ls)
+        cols, out_row = out.step_out(step, clip) if out is not None else (None, None)
+        res = eng.ppo_act(obs.float(), P.make_gae_params(0.0, 0.0, False, kind, base), explore=explore, noise=noise, clip=clip,
+                          seed=self._rng_seed, offset=self._rng_calls + 1, out=cols, out_row=out_row)
+        self._rng_calls += (int(obs.shape[0]) + eng.max_batch - 1) // eng.max_batch
+        self._cur_value = None
+        res = P.act_result(res, out, step)
+        if not explore:
+            res.pop("action_noise", None)
+        return res
 
     def _ppo_dp_state(self):
         """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: parameters, the log-std vector

@@ -850,6 +850,40 @@ class PhysicsVAE(nn.Module):
                 "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
                 "value_targets": res["value_targets"], "last_value": res["last_value"], "latent_eps": res["latent_eps"]}
 
+    def compute_actions(self, obs, explore=True, noise=None, eps=None, clip=None, out=None, step=None):
+        """The rollout worker's policy step, on the device (`pvae_ppo_act`; the rule: `ppo.py`'s module docstring): from the
+        observations [B, 2 Db] of the B vectorised environments to a dict under RLlib's keys -- `actions` [B, Da]
+        (unclipped), `action_dist_inputs` [B, 2 Da] = [a_hat | log_std], `action_logp` [B] and `vf_preds` [B], the columns
+        `ppo_prepare` takes as given -- plus `action_noise` [B, Da], the noise used (absent with `explore` False),
+        `latent_eps` [B, Z], the latent draws used, and, with `clip` = (low, high), `env_actions`, what the environment
+        takes.  One library call in the launches of the evaluate pass, no torch op, nothing synchronised; B above
+        `max_batch` runs in chunks.  `noise` [B, Da] / `eps` [B, Z]: supplied standard normals (None: Philox from the
+        module's seed -- the action noise and the latent draws share the offset, the Philox group's high bit keeps them
+        apart; `latent_prior_noise` False: z = mu); `_rng_calls` advances by the number of chunks either way, as
+        `ppo_prepare` does.  `out` / `step`: a `ppo.RolloutBuffer` (made with `latent=Z`) and the step of its fragment this
+        call is -- every column (the observations too) is then written in place into the buffer's rows and the returned
+        tensors are views of them.  Refused by name where the fused PPO step is (`_ppo_refusals`)."""
+        from . import ppo as P
+        eng = self.engine
+        self._ppo_refusals()
+        eng._need_gpu()
+        assert (out is None) == (step is None), "out (a RolloutBuffer) and step go together"
+        als = self.__dict__["_als"]
+        train_ls = als.type == "state_independent" and als.log_std.requires_grad
+        eng.ppo_bind(self._ppo_value_engine(), als.on_device(eng.device), train_ls)
+        cols, out_row = out.step_out(step, clip) if out is not None else (None, None)
+        st = self._st
+        kind = "state_independent" if als.type == "state_independent" else "constant"
+        res = eng.ppo_act(obs.float(), P.make_gae_params(0.0, 0.0, False, kind), explore=explore, noise=noise, clip=clip,
+                          eps=eps, latent_noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1,
+                          out=cols, out_row=out_row)
+        st._rng_calls += (int(obs.shape[0]) + eng.max_batch - 1) // eng.max_batch
+        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
+        res = P.act_result(res, out, step)
+        if not explore:
+            res.pop("action_noise", None)
+        return res
+
     def _ppo_dp_state(self):
         """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: the parameter arena and the
         value branch's, the log-std vector and the PPO step's Adam moments (the step counter travels beside them)."""

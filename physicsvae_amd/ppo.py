@@ -48,6 +48,28 @@ own rows, as above), is that every worker applies Adam to
 `ppo_learn(..., dp=parallel.PPODataParallel(...))` runs it: inside the fused step's Adam launch over peer-mapped gradient
 buffers (transport "p2p"), or per minibatch `*_ppo_grad`, a SUM all-reduce over `torch.distributed`, `*_ppo_apply` with
 grad_scale = 1 / N (transport "torch": what nccl runs between GPUs and gloo anywhere).
+
+The rollout worker's policy step (RLlib's `compute_actions`): `FullyConnectedPolicy.compute_actions` (`pvae_fc_ppo_act`) and
+`PhysicsVAE.compute_actions` (`pvae_ppo_act`) produce the sampler's own columns that `ppo_prepare` takes as given.  The
+rule, for row r with the policy's mean[r], l[r] = log_std[r] (by kind, as the evaluate pass forms it, `ls_base +` included
+for a state-dependent stack) and standard-normal noise n[r], all [k] (`sample_actions_torch` is this in torch):
+
+    explore=True    action[j]   = fma(exp(l[j]), n[j], mean[j])
+                    action_logp = the log-density above of the STORED float32 action: z = (action - mean) exp(-l), then
+                                  -0.5 sum z^2 - sum l - 0.5 k log(2 pi), in the evaluate pass's arithmetic and summation
+                                  order -- never formed from n -- so that `*_ppo_evaluate` over the same observation and the
+                                  returned action gives the same bits and the learner's first step sees a ratio of 1
+    explore=False   action = mean bit for bit, action_logp = 0 (RLlib 1.11's StochasticSampling AS RECALLED: the zero has
+                    not been checked against a ray installation, none was at hand); no noise drawn or read
+    always          action_dist_inputs = [mean | l], vf_preds = value: the evaluate pass's bits
+
+  * the stored `actions` are unclipped, as RLlib's sample batch holds them; with clip bounds (both specs: `clip_actions:
+    true`, range +-3) a second output env_actions = min(max(action, low), high) is what the environment takes;
+  * the noise is supplied ([rows, k], device) or drawn from Philox under the module's (seed, offset): row r's own counter,
+    group 0x80000000 + (j >> 2) for columns 4 (j >> 2) .. + 3 -- the high bit keeps the action noise apart from PhysicsVAE's
+    latent draws (groups < Z / 4) --, chunk i of a call at offset + i; the noise used comes back as `action_noise`, as
+    `latent_eps` does, because Philox goes through hardware transcendentals and cannot be reproduced on the host;
+  * `RolloutBuffer` holds the train batch's columns on the device and lets every step write its rows in place.
 """
 import math
 
@@ -173,6 +195,93 @@ def segment_table(eps_id, dones, new_obs, unroll_id=None):
 # they take as given
 ROLLOUT_KEYS = ("obs", "actions", "rewards", "seg_start", "seg_done", "next_obs_last")
 SAMPLER_KEYS = ("vf_preds", "action_dist_inputs", "action_logp")
+
+
+def sample_actions_torch(mean, log_std, noise, explore=True):
+    """The sampling rule of the module docstring in plain torch, any dtype and device: (actions [B, k], logp [B]).  mean /
+    log_std / noise [B, k] (log_std broadcast by the caller; `noise` is not read when `explore` is False)."""
+    if not explore:
+        return mean.clone(), torch.zeros(mean.shape[0], dtype=mean.dtype, device=mean.device)
+    k = mean.shape[1]
+    actions = torch.exp(log_std) * noise + mean
+    z = (actions - mean) * torch.exp(-log_std)
+    logp = -0.5 * (z * z).sum(1) - log_std.sum(1) - 0.5 * k * math.log(2 * math.pi)
+    return actions, logp
+
+
+class RolloutBuffer:
+    """The train batch of one worker iteration as preallocated device columns: `n_envs` vectorised environments times
+    `fragment_length` steps, env-major -- row = env * fragment_length + t -- so that every environment's fragment is one
+    contiguous run in time order, the layout `segment_table` and `ppo_prepare` read.  `compute_actions(obs, out=buffer,
+    step=t)` writes step t of every environment straight into its rows (row t of `row_table`, built once on the device, is
+    the call's destination table): observations, actions, action_dist_inputs, action_logp, vf_preds, the noise used and,
+    with `latent` = Z (PhysicsVAE), latent_eps; nothing is copied per step.  `rollout(...)` then gives the dict
+    `ppo_prepare` takes.  `env_actions` is there for a clipped policy step."""
+
+    def __init__(self, n_envs, fragment_length, n_in, k, device, latent=None):
+        self.n_envs, self.fragment_length, self.n_in, self.k = int(n_envs), int(fragment_length), int(n_in), int(k)
+        assert self.n_envs >= 1 and self.fragment_length >= 1
+        self.device, self.latent = torch.device(device), latent
+        n = self.n_rows = self.n_envs * self.fragment_length
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        self.columns = {"obs": z(n, n_in), "actions": z(n, k), "env_actions": z(n, k), "old_dist": z(n, 2 * k),
+                        "old_logp": z(n), "vf_preds": z(n), "action_noise": z(n, k)}
+        if latent is not None:
+            self.columns["latent_eps"] = z(n, int(latent))
+        env = torch.arange(self.n_envs, dtype=torch.int32)
+        t = torch.arange(self.fragment_length, dtype=torch.int32)
+        self.row_table = (env[None, :] * self.fragment_length + t[:, None]).contiguous().to(self.device)     # [T, n_envs]
+        self._written = [False] * self.fragment_length
+
+    def reset(self):
+        """Start the next fragment: no step is written."""
+        self._written = [False] * self.fragment_length
+
+    def step_out(self, step, clip):
+        """(columns, destination rows) of step `step` for the engines' `ppo_act`; marks the step written."""
+        step = int(step)
+        assert 0 <= step < self.fragment_length, "step %d outside the fragment [0, %d)" % (step, self.fragment_length)
+        self._written[step] = True
+        cols = {k: v for k, v in self.columns.items() if clip is not None or k != "env_actions"}
+        return cols, self.row_table[step]
+
+    def step_view(self, name, step):
+        """Step `step` of a column, one row per environment (a strided view)."""
+        col = self.columns[name]
+        return col.view(self.n_envs, self.fragment_length, *col.shape[1:])[:, int(step)]
+
+    def rollout(self, rewards, dones, next_obs_last):
+        """The fragment as `ppo_prepare` takes it: `ROLLOUT_KEYS`, all three `SAMPLER_KEYS` and, for PhysicsVAE,
+        `latent_eps`.  rewards [n_envs, fragment_length] (any device); dones [n_envs, fragment_length] on the host (the
+        segment table is built there, `segment_table`: every environment's fragment is split after each done step);
+        next_obs_last [n_envs, n_in]: the observation after each environment's last step, read only where that step did
+        not end an episode.  Every step must have been written since the last `reset()`."""
+        missing = [t for t, w in enumerate(self._written) if not w]
+        assert not missing, "steps %s of the fragment were never written (compute_actions(..., out=buffer, step=t))" % missing
+        T, n = self.fragment_length, self.n_rows
+        dones = np.asarray(dones.cpu() if torch.is_tensor(dones) else dones).astype(bool).reshape(self.n_envs, T)
+        rewards = torch.as_tensor(rewards, dtype=torch.float32).reshape(n).to(self.device)
+        rows = np.arange(n)
+        seg_start, seg_done, last = segment_table(rows // T, dones.reshape(n), rows.reshape(n, 1))       # new_obs: the row's own index
+        last = last.reshape(-1).astype(np.int64)
+        next_obs_last = torch.as_tensor(next_obs_last, dtype=torch.float32).reshape(self.n_envs, self.n_in).to(self.device)
+        boot = torch.zeros(len(last), self.n_in, dtype=torch.float32, device=self.device)
+        at_end = torch.from_numpy(np.flatnonzero(last % T == T - 1)).to(self.device)
+        boot[at_end] = next_obs_last[torch.from_numpy(last // T).to(self.device)[at_end]]
+        c = self.columns
+        ro = {"obs": c["obs"], "actions": c["actions"], "rewards": rewards, "seg_start": torch.from_numpy(seg_start),
+              "seg_done": torch.from_numpy(seg_done).to(self.device), "next_obs_last": boot, "vf_preds": c["vf_preds"],
+              "action_dist_inputs": c["old_dist"], "action_logp": c["old_logp"]}
+        if self.latent is not None:
+            ro["latent_eps"] = c["latent_eps"]
+        return ro
+
+
+def act_result(res, buffer=None, step=None):
+    """What `compute_actions` returns, under RLlib's keys, from the engines' columns; with a buffer: its rows of `step`."""
+    names = {"actions": "actions", "old_dist": "action_dist_inputs", "old_logp": "action_logp", "vf_preds": "vf_preds",
+             "action_noise": "action_noise", "env_actions": "env_actions", "latent_eps": "latent_eps"}
+    return {key: (res[name] if buffer is None else buffer.step_view(name, step)) for name, key in names.items() if name in res}
 
 
 def _terms(mean, log_std, value, actions, old_dist, old_logp, advantages, value_targets, vf_preds, cfg):
