@@ -11,11 +11,13 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpvae_gfx950.so")
 UNITS = ["pvae.hip", "pvae_net.hip", "pvae_step.hip", "pvae_lookahead.hip", "pvae_infer.hip", "pvae_exchange.hip",
          "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip", "pvae_ppo.hip"]
-HEADERS = ["pvae_internal.h", "pvae_gemm.h", "pvae_layout.h", "pvae_fc_layout.h"]
+GEMM_HEADERS = ["pvae_gemm_common.h", "pvae_stage.h", "pvae_gemm_src.h", "pvae_gemm_reg.h", "pvae_gemm_ws.h",
+                "pvae_gemm_wgrad.h", "pvae_adam.h", "pvae_gemm_fused.h", "pvae_gemm_epi.h", "pvae_gemm_launch.h"]   # what pvae_gemm.h includes
+HEADERS = ["pvae_internal.h", "pvae_gemm.h"] + GEMM_HEADERS + ["pvae_layout.h", "pvae_fc_layout.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(HERE), "include", "pvae.h")
 # -amdgpu-kernarg-preload-count: leading scalar / pointer kernel arguments arrive in SGPRs at wave launch (gfx950)
-# instead of by an s_load inside the kernel (pvae_gemm.h PVAE_GA_PARAMS; tools/kernarg_preload_probe.hip)
+# instead of by an s_load inside the kernel (pvae_gemm_common.h PVAE_GA_PARAMS; tools/kernarg_preload_probe.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-Wall",
          "-Wno-unused-function"]
 

@@ -242,12 +242,12 @@ int panel_ld(const pvae_fc* c, int s, int i) { return i == 0 ? c->L.n0 : c->L.st
 
 struct FwdProb { GemmArgs ga; EpiFc e; int grid; };
 
-// forward problem out[M][N] = act(X W^T + b); `t16`: 16x16 tiles
-FwdProb fwd_prob(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, bool t16, const EpiFc& e) {
-    const GemmGrid g = t16 ? make_grid(M, N, 16, 16) : make_grid(M, N, 32, 32);
-    FwdProb p{GemmArgs{X, ldx, W, ldw, K, g.tiles_q, g.tiles_p, g.p_per_xcd}, e, g.grid};
-    p.ga.krot = 0; p.ga.rowxcd = 0;
-    p.ga.tile16 = t16 ? 1 : 0;
+// forward problem out[M][N] = act(X W^T + b) on 16x16 or 32x32 tiles (tile16: the group kernel's switch between them)
+constexpr TileRule kFwdRule{false, false, TileRule::kForward, true};
+FwdProb fwd_prob(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, TileGeom geom, const EpiFc& e) {
+    const TilePlan t = plan_tiles(geom, kFwdRule, X, ldx, W, ldw, M, N, K);
+    FwdProb p{t.ga, e, t.grid};
+    p.ga.tile16 = geom == kTile16;
     return p;
 }
 
@@ -307,7 +307,7 @@ int run_forward(Run& r, float* const* dense) {
     const bool gemv = r.rows <= 4;
     // (the first layers' tile geometry is decided on the WHOLE shared block, whichever stacks run and however they are
     //  launched: a stack's first layer gives the same bits alone, in a range, or in the full block)
-    const bool t16_0 = forward_uses_16x16(r.rows_pad, L.n0);
+    const TileGeom geom0 = tile_geometry(kFwdRule, r.rows_pad, L.n0);
     for (int i = 0; i < L.max_layers; ++i) {
         std::vector<FwdProb> tp;
         std::vector<FcGemvProb> gp;
@@ -326,7 +326,7 @@ int run_forward(Run& r, float* const* dense) {
                 if (l.last && dense && dense[s] && r.want[s]) { e.dense[k] = dense[s]; e.ldd[k] = l.n_out; }
                 N += l.n_out_pad;
             }
-            tp.push_back(fwd_prob(in, L.ld0, c->params + a.w_off, L.ld0, r.rows_pad, N, L.ld0, t16_0, e));
+            tp.push_back(fwd_prob(in, L.ld0, c->params + a.w_off, L.ld0, r.rows_pad, N, L.ld0, geom0, e));
         } else {
             for (int s = 0; s < L.S; ++s) {
                 if (!r.want[s] || i >= (int)L.stack[s].size()) continue;
@@ -344,8 +344,8 @@ int run_forward(Run& r, float* const* dense) {
                     e.out = act_ptr(c, s, i); e.ldo = panel_ld(c, s, i); e.bias = c->params + l.b_off; e.rows = r.rows;
                     e.nseg = 1; e.act[0] = l.act; e.valid[0] = l.n_out; e.end[0] = l.n_out_pad;
                     e.dense[0] = d; e.ldd[0] = l.n_out;
-                    const bool t16 = i == 0 ? t16_0 : forward_uses_16x16(r.rows_pad, l.n_out_pad);
-                    tp.push_back(fwd_prob(x, ldx, c->params + l.w_off, l.ld, r.rows_pad, l.n_out_pad, l.ld, t16, e));
+                    const TileGeom geom = i == 0 ? geom0 : tile_geometry(kFwdRule, r.rows_pad, l.n_out_pad);
+                    tp.push_back(fwd_prob(x, ldx, c->params + l.w_off, l.ld, r.rows_pad, l.n_out_pad, l.ld, geom, e));
                 }
             }
         }
@@ -360,14 +360,12 @@ struct DProb { GemmArgs ga; EpiMask e; int grid; };
 template <class EpiW> struct WProb { GemmArgs ga; EpiW e; int grid, nbias; };
 
 DProb d_prob(const float* dZ, int ldz, const float* W, int ldw, int M, int Kin, int N, const EpiMask& e) {
-    DgradPlan d = plan_dgrad(dZ, ldz, W, ldw, M, Kin, N);
-    d.ga.krot = 0; d.ga.rowxcd = 0;
+    const TilePlan d = plan_dgrad(dZ, ldz, W, ldw, M, Kin, N, true);
     return DProb{d.ga, e, d.grid};
 }
 template <class EpiW>
 WProb<EpiW> w_prob(const float* dZ, int ldz, const float* X, int ldx, int N, int Kin, int M, float* g, float* gb) {
-    WgradPlan w = plan_wgrad(dZ, ldz, X, ldx, N, Kin, M);
-    w.ga.krot = 0; w.ga.rowxcd = 0;
+    const WgradPlan w = plan_wgrad(dZ, ldz, X, ldx, N, Kin, M, true);
     EpiW e{g, Kin};
     e.gb = gb;
     return WProb<EpiW>{w.ga, e, w.grid, w.nbias};

@@ -181,8 +181,8 @@ def stack_case_by_id(name):
 
 
 def layer_problems(case):
-    """What the host plan (pvae_fc.hip run_forward / run_backward_layers) hands the tile selectors of pvae_gemm.h for the
-    full stack set: [("first" | "deep", M, N)] forward, [(M, Kin)] input gradients of the deeper layers and
+    """What the host plan (pvae_fc.hip run_forward / run_backward_layers) hands the tile selectors of pvae_gemm_launch.h
+    for the full stack set: [("first" | "deep", M, N)] forward, [(M, Kin)] input gradients of the deeper layers and
     [(N, Kin, M)] weight gradients."""
     m = pad32(case.rows)
     fwd, dgrad, wgrad = [("first", m, sum(pad64(w[0] if w else n) for w, _, n in case.stacks))], [], []

@@ -1,6 +1,6 @@
 """What tests/test_gpu_fc_shapes.py claims, checked without a GPU: every case of tests/fc_cases.py meets its drop cap and
-its coverage conditions; the cases reach every class of the tile selectors of pvae_gemm.h (restated here: whoever retunes
-a selector learns from this file that the sweep must follow); the float32 torch restatement of every computation stays
+its coverage conditions; the cases reach every class of the tile selectors of pvae_gemm_launch.h (restated in
+tile_rules.py: whoever retunes a selector learns from this file that the sweep must follow); the float32 torch restatement of every computation stays
 within ONE QUARTER of the bound the GPU test asserts against the float64 twin, so the standing bounds (outputs and stats
 1e-5, gradients 1e-4, GAE columns 1e-5) carry over from the reference's own error alone; and the twin agrees with the
 `Twin` of tests/test_gpu_fcnn.py, the oracle already trusted."""
@@ -15,22 +15,10 @@ from ppo_cases import KINK, coverage
 from test_gpu_fcnn import Twin
 from test_gpu_gae import dense_case, dense_want
 from test_gpu_ppo import check_stats
+from tile_rules import dgrad_uses_16x16, forward_uses_16x16, wgrad_uses_32x32    # pvae_gemm_launch.h's selectors at the default options
 from util import max_err_scaled
 
 OUT_BOUND, GRAD_BOUND = 1e-5, 1e-4           # what the GPU test asserts; a float32 restatement must stay under a quarter
-
-
-# the selectors, as the library evaluates them with its default options
-def forward_uses_16x16(m, n):                # pvae_gemm.h:2659 forward_uses_16x16
-    return (m // 32) * (n // 32) < 128
-
-
-def dgrad_uses_16x16(m, k_in):               # pvae_gemm.h:2753 dgrad_uses_16x16 (option "dgrad16" at its default, 1)
-    return (m // 32) * (k_in // 32) < 128
-
-
-def wgrad_uses_32x32(n, k_in, m):            # pvae_gemm.h:2802 wgrad_uses_32x32 (option "wgrad32" at its default, 1)
-    return (n // 64) * (k_in // 64) <= 128 and m % 64 == 0
 
 
 def test_every_stack_case_meets_its_drop_cap_and_the_mix_is_as_stated():

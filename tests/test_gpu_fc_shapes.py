@@ -1,6 +1,6 @@
 """Randomised-shape sweep of the stack set (pvae_fc.hip) and the PPO learner's launches (pvae_ppo_core.hip) against float64:
 (a) the grouped forward / backward on random and directed stack sets -- unequal depths, per-layer widths and activations,
-every tile geometry the selectors of pvae_gemm.h choose, every GEMV instantiation; (b) the fused PPO step at action
+every tile geometry the selectors of pvae_gemm_launch.h choose, every GEMV instantiation; (b) the fused PPO step at action
 counts K = 1 .. 130, few rows, every train_mask, and the SGD loop; (c) the loss head alone at K up to 200 and past its wave
 cap; (d) GAE and the standardisation past their grid caps; (e) evaluate and prepare at K = 1 / 65 / 130 and in chunks
 larger than the epilogue's and the copy's grids; (f) a stack without a hidden layer.  The cases come from

@@ -1006,13 +1006,13 @@ def test_launcher_with_more_ranks_than_gpus_shares_the_devices(monkeypatch):
 
 def test_build_command_keeps_the_kernarg_preload_switch():
     """The contraction kernels take what a workgroup needs for its first tile load as leading scalar parameters
-    (pvae_gemm.h PVAE_GA_PARAMS / PVAE_GA2_PARAMS) so that gfx950 preloads them into SGPRs at wave launch; that only
+    (pvae_gemm_common.h PVAE_GA_PARAMS / PVAE_GA2_PARAMS) so that gfx950 preloads them into SGPRs at wave launch; that only
     happens when hipcc is given -amdgpu-kernarg-preload-count (0.26 us per dependent launch otherwise)."""
     import inspect
     from physicsvae_amd import build as B
     assert "-amdgpu-kernarg-preload-count=16" in B.FLAGS and B.FLAGS[B.FLAGS.index("-amdgpu-kernarg-preload-count=16") - 1] == "-mllvm"
     assert "FLAGS" in inspect.getsource(B.build)                 # every translation unit is compiled with them
-    hdr = open(os.path.join(ROOT, "physicsvae_amd", "csrc", "pvae_gemm.h")).read()
+    hdr = "".join(open(os.path.join(B.CSRC, h)).read() for h in B.HEADERS)       # (pvae_gemm.h is an include list)
     for kernel in ("gemm_splitk_ws_kernel(PVAE_GA_PARAMS(a_)", "gemm_splitk_reg16_kernel(PVAE_GA_PARAMS(a_)",
                    "bwd_pair_kernel(PVAE_GA2_PARAMS", "wgrad_pair_kernel(PVAE_GA2_PARAMS"):
         assert kernel in hdr, kernel

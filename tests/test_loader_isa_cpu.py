@@ -1,7 +1,7 @@
 """The loader waves of the wave-specialised forward / input-gradient kernels share their SIMDs with compute waves that
 issue fp32 MFMAs back to back, which hold the vector issue (tools/dual_pipe.hip).  Their steady state must therefore issue
 NO vector-ALU instruction: every LDS-DMA takes a wave-uniform SGPR base and a lane offset computed once in front of the
-loop, one VGPR per DMA piece of a tile (pvae_gemm.h, lds_dma16_sbase).  This test compiles pvae_net.hip to gfx950 assembly
+loop, one VGPR per DMA piece of a tile (pvae_gemm_ws.h, lds_dma16_sbase).  This test compiles pvae_net.hip to gfx950 assembly
 with the flags of physicsvae_amd/build.py and reads the loader loops of the dense instances.  No GPU needed; skipped
 where there is no hipcc."""
 import os
