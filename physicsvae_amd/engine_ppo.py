@@ -1,0 +1,496 @@
+"""The PPO learner surface of both engines (`PpoSurface`), the structs its calls take (`make_ppo_batch`, `make_rollout`,
+`make_prepared`, `make_act`, the evaluate / prepare plans) and the entry points that need no engine (`ppo_loss`, `gae`).
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+PPO_COLUMNS = ("actions", "old_dist", "old_logp", "advantages", "value_targets", "vf_preds")
+NO_DRAWS = (None, (), None)                  # what `_ppo_struct_draws` returns, for a model without a latent
+
+
+class PpoSurface:
+    """The PPO learner surface of an engine, written once: `HipEngine` (PhysicsVAE, C symbols `pvae_ppo_*`) and
+    `StackSetEngine` (`pvae_fc_ppo_*`) both inherit it.  The two libraries' calls differ only in what the engine class
+    supplies:
+
+        _PPO, _PPO_GAE_LAUNCHES    the symbol prefix, and the one name that does not follow it
+        _PPO_NEEDS_LOG_STD         `ppo_bind` insists on a log-std vector (the stack set's third stack can stand in for it)
+        _ppo_dims                  (inputs per observation, actions per row, latent width or None), set by `__init__`
+        _ppo_inline_draws(), _ppo_struct_draws()
+                                   how latent draws become call arguments, for a model that has a latent: the `_ppo_*`
+                                   bodies take `draws` = None (nothing is passed) or what these two understand
+        ppo_batch(batch)           the engine's `make_ppo_batch`
+
+    and, where its argument list carries draws or a companion engine, a one-line method of that signature over the
+    `_ppo_*` body here.  Companion engines (PhysicsVAE's value engine) are kept in `_ppo_keep` behind the log-std vector;
+    `ppo_bind`, `ppo_reset` and `ppo_grad_arenas` forward to them.  Expects of the engine: `lib`, `ctx`, `cfg`, `device`,
+    `arena_floats`."""
+
+    _PPO = _PPO_GAE_LAUNCHES = None
+    _PPO_NEEDS_LOG_STD = False
+
+    # -- what every call of either engine starts with ------------------------------------------------
+    def _need_gpu(self):
+        if self.ctx is None:
+            raise RuntimeError("%s was created on %s: the HIP hot path needs a GPU "
+                               "(there is no CPU fallback)" % (type(self).__name__, self.device))
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ppo(self, name, *args):
+        """`<prefix><name>(ctx, *args)`, checked under the C function's name.  (The calls made once per step or per
+        action spell these two lines out: a frame less on a host path of tens of microseconds.)"""
+        what = self._PPO + name
+        return _lib.check(getattr(self.lib, what)(self.ctx, *args), what)
+
+    # -- PPO learner step (include/pvae.h "PPO learner step", "PPO learner step of PhysicsVAE") --------
+    def ppo_bind(self, log_std=None, train_log_std=False):
+        """Allocate (once, lazily) the gradient arena, Adam's moments and the scratch buffer of the PPO step and bind them.
+        `log_std`: the vector of k values of a constant / state-independent log-std (None: state-dependent, a third
+        stack); `train_log_std`: it is trained (its moments live here too)."""
+        return self._ppo_bind(log_std, train_log_std)
+
+    def _ppo_bind(self, log_std, train_log_std, *companions):
+        self._need_gpu()
+        if getattr(self, "ppo_grad", None) is None:
+            z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)      # noqa: E731
+            self.ppo_grad, self.ppo_m, self.ppo_v = z(self.arena_floats), z(self.arena_floats), z(self.arena_floats)
+            self.ppo_scratch_bytes = int(getattr(self.lib, self._PPO + "workspace_bytes")(C.byref(self.cfg)))
+            self.ppo_scratch = z(self.ppo_scratch_bytes // 4 + 4)
+            self.ppo_ls_m = self.ppo_ls_v = None
+        k = self._ppo_dims[1]
+        if log_std is not None or self._PPO_NEEDS_LOG_STD:
+            assert log_std.dtype == torch.float32 and log_std.device == self.device and log_std.is_contiguous() \
+                and log_std.numel() == k, "log_std must be %d contiguous floats on %s" % (k, self.device)
+            if train_log_std and self.ppo_ls_m is None:
+                self.ppo_ls_m, self.ppo_ls_v = torch.zeros_like(log_std), torch.zeros_like(log_std)
+        ctxs = []
+        for e in companions:
+            e._ppo_bind(None, False)
+            ctxs.append(e.ctx)
+        self._ppo_keep = (log_std,) + companions           # (kept alive while bound)
+        moments = (self.ppo_ls_m, self.ppo_ls_v) if (log_std is not None and train_log_std) else (None, None)
+        what = self._PPO + "bind"
+        _lib.check(getattr(self.lib, what)(
+            self.ctx, self.ppo_grad.data_ptr(), self.ppo_m.data_ptr(), self.ppo_v.data_ptr(), self.ppo_scratch.data_ptr(),
+            self.ppo_scratch_bytes, log_std.data_ptr() if log_std is not None else None,
+            moments[0].data_ptr() if moments[0] is not None else None,
+            moments[1].data_ptr() if moments[1] is not None else None, *ctxs), what)
+
+    def ppo_reset(self):
+        """Adam's moments of the PPO step back to zero (the gradient arena and the scratch are rewritten by every step)."""
+        for t in (getattr(self, "ppo_m", None), getattr(self, "ppo_v", None), getattr(self, "ppo_ls_m", None),
+                  getattr(self, "ppo_ls_v", None)):
+            if t is not None:
+                t.zero_()
+        for e in (getattr(self, "_ppo_keep", None) or ())[1:]:
+            e.ppo_reset()
+
+    def ppo_step(self, batch, params, first, rows, index=None, stats_out=None):
+        """`*_ppo_step`: one minibatch -- rows `index[first : first + rows]` of the batch (index None: rows first ..) --
+        forward, loss, backward and Adam in one call; returns the five stats (a device tensor, nothing synchronises)."""
+        return self._ppo_step(batch, params, first, rows, index, stats_out)
+
+    def _ppo_step(self, batch, params, first, rows, index, stats_out, draws=None, grad=False):
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        if stats_out is None:
+            stats_out = torch.empty(5, dtype=torch.float32, device=self.device)
+        _check_index(index, int(b.n_rows), self.device)
+        eps, draws = (None, ()) if draws is None else self._ppo_inline_draws(draws, (int(rows),))
+        outs = (stats_out, self._ppo_ls_grad()) if grad else (stats_out,)
+        what = self._PPO + ("grad" if grad else "step")
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(b), index.data_ptr() if index is not None else None, int(first),
+                                           int(rows), C.byref(params), *draws, *[t.data_ptr() for t in outs], self._stream()), what)
+        return outs if grad else stats_out
+
+    def ppo_sgd(self, batch, params, minibatch, num_sgd_iter, perm=None):
+        """`*_ppo_sgd`: `num_sgd_iter` passes over the batch in minibatches of `minibatch` rows (the last one short),
+        pass p in the order `perm[p]` (int32 [num_sgd_iter, n_rows] on the device; None: row order); `params.adam_t` is the
+        first step's time step.  Returns stats [steps, 5] on the device; every launch is enqueued, nothing synchronises."""
+        return self._ppo_sgd(batch, params, minibatch, num_sgd_iter, perm)
+
+    def _ppo_sgd(self, batch, params, minibatch, num_sgd_iter, perm, draws=None):
+        self._need_gpu()
+        b, keep = batch if isinstance(batch, tuple) else self.ppo_batch(batch)
+        n = int(b.n_rows)
+        steps = int(num_sgd_iter) * ((n + int(minibatch) - 1) // int(minibatch))
+        stats = torch.empty(max(steps, 0), 5, dtype=torch.float32, device=self.device)
+        if perm is not None:
+            assert tuple(perm.shape) == (int(num_sgd_iter), n), "perm must be [num_sgd_iter, n_rows]"
+        _check_index(perm, n, self.device)
+        eps, draws = (None, ()) if draws is None else self._ppo_inline_draws(draws, (steps, int(minibatch)))
+        what = self._PPO + "sgd"
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(b), perm.data_ptr() if perm is not None else None, int(minibatch),
+                                           int(num_sgd_iter), C.byref(params), *draws, stats.data_ptr(), self._stream()), what)
+        return stats
+
+    def ppo_launches(self):
+        """Kernel launches of the last PPO step."""
+        n = C.c_int32()
+        self._ppo("launches", C.byref(n))
+        return n.value
+
+    # -- gradient exchange between workers (include/pvae.h "Gradient exchange between workers") --------
+    def ppo_grad_step(self, batch, params, first, rows, index=None, stats_out=None):
+        """`*_ppo_grad`: `ppo_step` up to, not including, its Adam launch -- the gradient lies in `ppo_grad` (and the
+        companion engines' `ppo_grad`), nothing else moved.  Returns (stats [5], ls_grad [k]: the log-std vector's
+        gradient, written for a trained vector only)."""
+        return self._ppo_step(batch, params, first, rows, index, stats_out, grad=True)
+
+    def _ppo_ls_grad(self):
+        """The k floats `*_ppo_grad` writes the log-std vector's gradient to (allocated once, kept with the engine)."""
+        if getattr(self, "ppo_ls_grad", None) is None:
+            self.ppo_ls_grad = torch.zeros(self._ppo_dims[1], dtype=torch.float32, device=self.device)
+        return self.ppo_ls_grad
+
+    def ppo_apply(self, params, grad_scale=1.0, ls_grad=None):
+        """`*_ppo_apply`: Adam (time step `params.adam_t`) over the trained stacks on `grad_scale` times what the gradient
+        buffers hold, and over a trained log-std vector on `grad_scale * ls_grad`."""
+        self._need_gpu()
+        what = self._PPO + "apply"
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(params), float(grad_scale),
+                                           ls_grad.data_ptr() if ls_grad is not None else None, self._stream()), what)
+
+    def ppo_grad_arenas(self):
+        """The gradient buffers a transport outside the library reduces: this engine's and its companions'."""
+        return [self.ppo_grad] + [e.ppo_grad for e in self._ppo_keep[1:]]
+
+    def ppo_peer_export(self):
+        """The blob the peers open (IPC handles of the bound gradient buffers and the flag block, sizes).  `ppo_bind` first."""
+        self._need_gpu()
+        buf = C.create_string_buffer(_lib.P2P_BLOB_BYTES)
+        self._ppo("peer_export", buf)
+        return buf.raw
+
+    def ppo_peer_open(self, rank, world, blobs):
+        """Map the peers' gradient buffers and flag blocks (`blobs`: every rank's, in rank order) and run the attach-time check."""
+        self._need_gpu()
+        assert len(blobs) == world and all(len(b) == _lib.P2P_BLOB_BYTES for b in blobs)
+        self._ppo("peer_open", int(rank), int(world), b"".join(blobs))
+
+    def ppo_peer_close(self):
+        if self.ctx is not None:
+            self._ppo("peer_close")
+
+    def ppo_peer_status(self, sync=True):
+        """(rank, world, waits that gave up) of the PPO gradient exchange; (0, 0, n) when none is open."""
+        if self.ctx is None:
+            return (0, 0, 0)
+        r, w, t = C.c_int(), C.c_int(), C.c_uint32()
+        self._ppo("peer_status", C.byref(r), C.byref(w), C.byref(t) if sync else None, self._stream())
+        return (r.value, w.value, t.value)
+
+    # -- train-batch preparation (include/pvae.h "Train-batch preparation", "... for PhysicsVAE") ------
+    def ppo_evaluate(self, rollout, params, out=None):
+        """`*_ppo_evaluate`: the current policy and value function over a device-resident rollout, in chunks of
+        `max_batch` rows -- vf_preds [N], old_dist [N, 2k] = [mean | log_std], old_logp [N] of `actions` (when the rollout
+        has obs and actions) and last_value [S], the bootstrap values (when it has seg_done and boot_obs; 0 for a done
+        segment, whose boot_obs row is never read).  `params`: `PPOConfig.gae_params(kind, base)`; the log-std vector of a
+        constant / state-independent kind is the one `ppo_bind` bound.  Returns the dict of what was computed."""
+        return self._ppo_evaluate(rollout, params, out)
+
+    def _ppo_evaluate(self, rollout, params, out, draws=None):
+        self._need_gpu()
+        n_in, k, _ = self._ppo_dims
+        ro, need, names = evaluate_plan(rollout, self.device)
+        r, keep = make_rollout(ro, need, self.device, n_in, k)
+        o, res = make_prepared(int(r.n_rows), int(r.n_segs), names, out, self.device, k)
+        eps, d, used = NO_DRAWS if draws is None else self._ppo_struct_draws(draws, int(r.n_rows), out, "vf_preds" in names)
+        what = self._PPO + "evaluate"
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(r), C.byref(params), *d, C.byref(o), self._stream()), what)
+        if used is not None:
+            res["latent_eps"] = used
+        return res
+
+    def ppo_prepare(self, rollout, params, out=None):
+        """`*_ppo_prepare`: evaluate (unless the rollout carries the sampler's own vf_preds, old_dist and old_logp: all
+        three or none), bootstrap, GAE and -- with `params.standardize` -- the standardisation, all enqueued on the current
+        stream; nothing synchronises.  Returns {vf_preds, old_dist, old_logp, last_value, advantages, value_targets}; the
+        sampler's columns, when given, come back as they are.  `out`: tensors to write into, by those names."""
+        return self._ppo_prepare(rollout, params, out)
+
+    def _ppo_prepare(self, rollout, params, out, draws=None):
+        self._need_gpu()
+        n_in, k, _ = self._ppo_dims
+        r, keep = make_rollout(rollout, ("obs", "actions", "rewards", "seg_start", "boot_obs"), self.device, n_in, k)
+        names, given = prepare_plan(rollout)
+        o, res = make_prepared(int(r.n_rows), int(r.n_segs), names, out, self.device, k)
+        if given and draws is not None:
+            draws = (None,) + tuple(draws[1:])            # (nothing is evaluated: supplied draws are not looked at)
+        eps, d, used = NO_DRAWS if draws is None else self._ppo_struct_draws(draws, int(r.n_rows), out, not given)
+        scratch, nbytes = gae_scratch_for(self, r.n_segs)
+        what = self._PPO + "prepare"
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(r), C.byref(params), *d, C.byref(o), scratch.data_ptr(), nbytes,
+                                           self._stream()), what)
+        if given:
+            res.update({name: rollout[name] for name in ("vf_preds", "old_dist", "old_logp")})
+        if draws is not None:
+            res["latent_eps"] = used
+        return res
+
+    def ppo_act(self, obs, params, explore=True, noise=None, clip=None, seed=0, offset=0, out=None, out_row=None):
+        """`*_ppo_act`: one policy step -- the sampled actions, old_dist = [mean | log_std], old_logp of the stored
+        action, vf_preds and the action noise used -- in the launches of the evaluate pass over the same rows.  `params`:
+        `PPOConfig.gae_params(kind, base)` (the log-std kind; the vector of kinds 0 / 1 is the one `ppo_bind` bound); the
+        rest as `make_act`.  Returns the dict of columns; nothing synchronises."""
+        return self._ppo_act(obs, params, explore, noise, clip, seed, offset, out, out_row)
+
+    def _ppo_act(self, obs, params, explore, noise, clip, seed, offset, out, out_row, draws=None):
+        self._need_gpu()
+        n_in, k, latent = self._ppo_dims
+        i, o, res, keep = make_act(obs, n_in, k, self.device, explore, noise, clip, seed, offset, out, out_row, latent=latent)
+        eps, d, _ = NO_DRAWS if draws is None else self._ppo_struct_draws(draws, int(i.n_rows), used=res["latent_eps"])
+        what = self._PPO + "act"
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(i), C.byref(params), *d, C.byref(o), self._stream()), what)
+        return res
+
+    def gae_launches(self):
+        """(evaluate, rest): kernel launches of the last ppo_prepare / ppo_evaluate -- the pass over the rows, and bootstrap +
+        GAE + standardisation."""
+        e, r = C.c_int32(), C.c_int32()
+        what = self._PPO_GAE_LAUNCHES
+        _lib.check(getattr(self.lib, what)(self.ctx, C.byref(e), C.byref(r)), what)
+        return e.value, r.value
+
+
+def make_rollout(ro, need, device, n_in, k):
+    """(pvae_fc_rollout, [tensors kept alive]) from a dict of device tensors: obs, actions, rewards, seg_start (int32
+    [S + 1]), seg_done (bool / uint8 [S]), boot_obs ([S, n_in]) and, optionally, the sampler's vf_preds / old_dist /
+    old_logp.  `need`: the names that must be there.  A `seg_start` given on the host is checked (its ends) and
+    uploaded; one on the device is taken under the caller's contract: it runs from 0 to the number of rows.  Shared by
+    the stack set's and PhysicsVAE's train-batch preparation (`n_in` inputs per observation, `k` actions per row)."""
+    f32 = torch.float32
+    r, keep = _lib.FcRollout(), []
+    n = next((int(ro[c].shape[0]) for c in ("actions", "rewards", "obs") if ro.get(c) is not None), 1)
+    s = int(ro["seg_done"].shape[0])
+    shapes = {"obs": (n, n_in), "actions": (n, k), "rewards": (n,), "boot_obs": (s, n_in), "vf_preds": (n,),
+              "old_dist": (n, 2 * k), "old_logp": (n,)}
+    for name in need:
+        if ro.get(name) is None:
+            raise KeyError("rollout lacks %s" % name)
+    for name, shape in shapes.items():
+        t = ro.get(name)
+        if t is None:
+            continue
+        t = t.reshape(t.shape[0], -1) if name in ("obs", "boot_obs") else t
+        t = t.to(device, f32).contiguous()
+        assert tuple(t.shape) == shape, "%s must be %s, got %s" % (name, shape, tuple(t.shape))
+        keep.append(t)
+        setattr(r, name, t.data_ptr())
+    done = ro["seg_done"]
+    done = done.to(device).contiguous()
+    assert done.dtype in (torch.bool, torch.uint8) and done.dim() == 1, "seg_done must be bool or uint8 [S]"
+    keep.append(done)
+    r.seg_done = done.data_ptr()
+    r.n_rows, r.n_segs, r.k = n, s, k
+    r.seg_first, r.seg_last = 0, n
+    if ro.get("seg_start") is not None:
+        seg, (r.seg_first, r.seg_last) = _seg_start(ro["seg_start"], s, n, device)
+        keep.append(seg)
+        r.seg_start = seg.data_ptr()
+    return r, keep
+
+
+def make_prepared(n, s, names, out, device, k):
+    """(pvae_fc_prepared, {name: tensor}) for the columns `names` of n rows and s segments: taken from `out` where it has
+    them, allocated otherwise."""
+    shapes = {"vf_preds": (n,), "old_dist": (n, 2 * k), "old_logp": (n,), "last_value": (s,), "advantages": (n,),
+              "value_targets": (n,)}
+    o, res = _lib.FcPrepared(), {}
+    for name in names:
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(shapes[name], dtype=torch.float32, device=device)
+        assert t.dtype == torch.float32 and t.device == device and t.is_contiguous() and tuple(t.shape) == shapes[name], \
+            "out[%r] must be contiguous float32 %s on %s" % (name, shapes[name], device)
+        res[name] = t
+        setattr(o, name, t.data_ptr())
+    return o, res
+
+
+def gae_scratch_for(engine, n_segs):
+    """(the engine's GAE scratch, grown when n_segs asks for more; the bytes `pvae_fc_gae_workspace_bytes` wants)"""
+    need = int(engine.lib.pvae_fc_gae_workspace_bytes(int(n_segs)))
+    if getattr(engine, "gae_scratch", None) is None or engine.gae_scratch.numel() * 8 < need:
+        engine.gae_scratch = torch.zeros(need // 8 + 2, dtype=torch.float64, device=engine.device)
+    return engine.gae_scratch, need
+
+
+def evaluate_plan(rollout, device):
+    """What an evaluate call computes from what the rollout holds: (rollout dict, needed names, output names)."""
+    rows = rollout.get("obs") is not None
+    boot = rollout.get("boot_obs") is not None
+    ro = {c: rollout.get(c) for c in ("obs", "actions", "seg_done", "boot_obs")}
+    if not boot:
+        ro["seg_done"] = torch.zeros(1, dtype=torch.uint8, device=device)
+    need = (("obs", "actions") if rows else ()) + (("boot_obs",) if boot else ())
+    names = (("vf_preds", "old_dist", "old_logp") if rows else ()) + (("last_value",) if boot else ())
+    return ro, need, names
+
+
+def prepare_plan(rollout):
+    """The output names of a prepare call, and whether the sampler's own columns are given (all three or none)."""
+    given = [rollout.get(name) is not None for name in ("vf_preds", "old_dist", "old_logp")]
+    if any(given) and not all(given):
+        raise ValueError("the sampler's vf_preds, old_dist and old_logp go together: all three or none")
+    names = (() if all(given) else ("vf_preds", "old_dist", "old_logp")) + ("last_value", "advantages", "value_targets")
+    return names, all(given)
+
+
+def make_act(obs, n_in, k, device, explore, noise, clip, seed, offset, out, out_row, latent=None):
+    """(pvae_ppo_act_in, pvae_ppo_act_out, {name: column}, [tensors kept alive]) of one policy step (include/pvae.h "Action
+    sampling").  obs [n, n_in]; `noise` [n, k] supplied action noise or None (Philox at (seed, offset + chunk)); `clip`:
+    None or (low, high); `out`: the caller's columns by name -- actions, env_actions (with clip), old_dist, old_logp,
+    vf_preds, action_noise, latent_eps (`latent` = Z: PhysicsVAE) and optionally obs --, every one of the same number of
+    rows, allocated with n rows where missing (obs never; action_noise only when exploring); `out_row`: int32 [n] on the
+    device, the row of those columns each input row is written to (None: row r to row r).  Shared by both engines."""
+    f32 = torch.float32
+    obs = obs.reshape(obs.shape[0], -1).to(device, f32).contiguous()
+    n = int(obs.shape[0])
+    assert tuple(obs.shape) == (n, n_in), "obs must be [n, %d], got %s" % (n_in, tuple(obs.shape))
+    out = dict(out or {})
+    n_dst = next((int(t.shape[0]) for t in out.values() if t is not None), n)
+    i, o, keep = _lib.PpoActIn(), _lib.PpoActOut(), [obs]
+    if explore and noise is not None:
+        noise = noise.to(device, f32).contiguous()
+        assert tuple(noise.shape) == (n, k), "noise must be [%d, %d], got %s" % (n, k, tuple(noise.shape))
+        keep.append(noise)
+        i.noise = noise.data_ptr()
+    if out_row is not None:
+        _check_index(out_row, n_dst, device)
+        assert out_row.numel() == n, "out_row must name one destination row per input row"
+        keep.append(out_row)
+        i.out_row = out_row.data_ptr()
+    i.obs, i.n_rows, i.n_dst_rows, i.k, i.explore = obs.data_ptr(), n, n_dst, k, 1 if explore else 0
+    i.rng_seed, i.rng_offset = int(seed), int(offset)
+    if clip is not None:
+        i.clip, i.clip_low, i.clip_high = 1, float(clip[0]), float(clip[1])
+    shapes = {"actions": (n_dst, k), "old_dist": (n_dst, 2 * k), "old_logp": (n_dst,), "vf_preds": (n_dst,)}
+    if clip is not None:
+        shapes["env_actions"] = (n_dst, k)
+    if explore or out.get("action_noise") is not None:
+        shapes["action_noise"] = (n_dst, k)
+    if latent is not None:
+        shapes["latent_eps"] = (n_dst, latent)
+    if out.get("obs") is not None:
+        shapes["obs"] = (n_dst, n_in)
+    res = {}
+    for name, shape in shapes.items():
+        t = out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=f32, device=device)
+        assert t.dtype == f32 and t.device == torch.device(device) and t.is_contiguous() and tuple(t.shape) == shape, \
+            "out[%r] must be contiguous float32 %s on %s" % (name, shape, device)
+        res[name] = t
+        field = {"action_noise": "noise_out", "obs": "obs_dst", "latent_eps": None}.get(name, name)
+        if field is not None:
+            setattr(o, field, t.data_ptr())
+    return i, o, res, keep
+
+
+def make_ppo_batch(batch, device, k, n_in=None):
+    """(pvae_fc_ppo_batch, [tensors kept alive]) from a dict of float32 device tensors; `n_in` None: no observations
+    (`pvae_ppo_loss`).  Nothing is copied unless a column is not contiguous float32 on `device`."""
+    device = torch.device(device)
+    n = int(batch["actions"].shape[0])
+    shapes = {"obs": (n, n_in), "actions": (n, k), "old_dist": (n, 2 * k), "old_logp": (n,), "advantages": (n,),
+              "value_targets": (n,), "vf_preds": (n,)}
+    b, keep = _lib.FcPpoBatch(), []
+    for name in (("obs",) if n_in is not None else ()) + PPO_COLUMNS:
+        t = batch[name]
+        if name == "obs":
+            t = t.reshape(t.shape[0], -1)
+        t = t.to(device, torch.float32).contiguous()
+        assert tuple(t.shape) == shapes[name], "%s must be %s, got %s" % (name, shapes[name], tuple(t.shape))
+        keep.append(t)
+        setattr(b, name, t.data_ptr())
+    b.n_rows, b.k = n, int(k)
+    return b, keep
+
+
+def _check_index(index, n_rows, device):
+    if index is not None:
+        assert index.dtype == torch.int32 and index.is_contiguous() and index.device == torch.device(device), \
+            "row indices must be contiguous int32 on %s" % device
+
+
+def ppo_loss(mean, log_std, value, batch, params, index=None):
+    """`pvae_ppo_loss`: the loss head alone on dense tensors.  mean [rows, k]; log_std [rows, k] (a row stride of 0 -- an
+    expanded vector -- is passed as it is); value [rows]; `batch`: the columns (dict, or what `make_ppo_batch` returned),
+    row r read at index[r].  Returns (stats [5], d_mean, d_log_std [rows, k], d_value): the gradients of stats[0]."""
+    lib = _lib.load()
+    dev = mean.device
+    assert dev.type == "cuda", "pvae_ppo_loss needs a GPU (there is no CPU fallback)"
+    rows, k = mean.shape
+    mean = mean.float().contiguous()
+    value = value.float().reshape(rows).contiguous()
+    assert tuple(log_std.shape) == (rows, k)
+    if not (log_std.dtype == torch.float32 and (k == 1 or log_std.stride(1) == 1) and log_std.stride(0) in (0, k)):
+        log_std = log_std.float().contiguous()
+    stride = 0 if (rows > 1 and log_std.stride(0) == 0) else k
+    b, keep = batch if isinstance(batch, tuple) else make_ppo_batch(batch, dev, k)
+    assert b.k == k
+    _check_index(index, int(b.n_rows), dev)
+    assert index is None or index.numel() >= rows
+    d_mean, d_ls, d_val = torch.empty_like(mean), torch.empty(rows, k, dtype=torch.float32, device=dev), torch.empty_like(value)
+    stats = torch.empty(5, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pvae_ppo_loss(mean.data_ptr(), log_std.data_ptr(), stride, value.data_ptr(), C.byref(b),
+                                     index.data_ptr() if index is not None else None, rows, C.byref(params),
+                                     d_mean.data_ptr(), d_ls.data_ptr(), d_val.data_ptr(), stats.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream), "pvae_ppo_loss")
+    return stats, d_mean, d_ls, d_val
+
+
+def _seg_start(seg_start, n_segs, n_rows, device):
+    """(int32 device tensor [S + 1], (first, last)): a table on the host has its ends read; one already on the device cannot
+    be read without a synchronisation and is taken under the caller's contract (0 .. n_rows)."""
+    device = torch.device(device)
+    seg = torch.as_tensor(seg_start)
+    assert seg.dim() == 1 and seg.shape[0] == n_segs + 1, "seg_start must be [S + 1] = [%d], got %s" % (n_segs + 1, tuple(seg.shape))
+    assert seg.dtype in (torch.int32, torch.int64), "seg_start must hold integers"
+    ends = (int(seg[0]), int(seg[-1])) if seg.device.type == "cpu" else (0, n_rows)
+    return seg.to(device, torch.int32).contiguous(), ends
+
+
+_gae_scratch = {}
+
+
+def gae(rewards, vf_preds, last_values, seg_start, gamma, lambda_, standardize=True, seg_done=None, out=None, info=None):
+    """`pvae_gae`: GAE and the standardisation on dense device columns, no stack set (the specification: `ppo.gae_torch`,
+    `ppo.standardize_torch`).  rewards / vf_preds [N], last_values [S] (read as 0 where `seg_done`), seg_start [S + 1].
+    Returns (advantages, value_targets); `out`: a pair of tensors to write into; `info`: a dict that receives the number
+    of kernel launches.  Nothing synchronises."""
+    from .ppo import make_gae_params
+    lib = _lib.load()
+    dev = rewards.device
+    assert dev.type == "cuda", "pvae_gae needs a GPU (there is no CPU fallback)"
+    n, s = int(rewards.shape[0]), int(last_values.shape[0])
+    cols = [t.to(dev, torch.float32).contiguous() for t in (rewards, vf_preds, last_values)]
+    assert tuple(cols[1].shape) == (n,) and cols[0].dim() == 1 and cols[2].dim() == 1
+    seg, ends = _seg_start(seg_start, s, n, dev)
+    if seg_done is not None:
+        seg_done = seg_done.to(dev).contiguous()
+        assert seg_done.dtype in (torch.bool, torch.uint8) and tuple(seg_done.shape) == (s,), "seg_done must be bool or uint8 [S]"
+    adv, vtarg = out if out is not None else (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    for t in (adv, vtarg):
+        assert t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and tuple(t.shape) == (n,)
+    need = int(lib.pvae_fc_gae_workspace_bytes(s))
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    scratch = _gae_scratch.get(key)
+    if scratch is None or scratch.numel() * 8 < need:
+        scratch = _gae_scratch[key] = torch.zeros(need // 8 + 2, dtype=torch.float64, device=dev)
+    params = make_gae_params(gamma, lambda_, standardize)
+    with torch.cuda.device(dev):
+        rc = _lib.check(lib.pvae_gae(cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(), seg.data_ptr(),
+                                     seg_done.data_ptr() if seg_done is not None else None, n, s, ends[0], ends[1],
+                                     C.byref(params), adv.data_ptr(), vtarg.data_ptr(), scratch.data_ptr(), need, key[1]),
+                        "pvae_gae")
+    if info is not None:
+        info["launches"] = rc
+    return adv, vtarg

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd as AG
-from .engine import StackSetEngine
+from .stack_set import StackSetEngine
 from .model import FC, _fc_stack, _portable, fc_spec
 
 DEFAULT_FC_64X2 = fc_spec(64, 2)

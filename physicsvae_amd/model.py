@@ -26,7 +26,8 @@ import torch.nn as nn
 
 from . import autograd as AG
 from ._lib import NET_MD, NET_MH, NET_NAMES, NET_PR, NET_TE, NET_WM, PRIOR_KINDS
-from .engine import Arch, HipEngine, Stack
+from .arch import Arch, Stack
+from .engine import HipEngine
 
 
 def fc_spec(width, depth, out_size="output", act_hidden="relu", act_out="linear"):
@@ -274,7 +275,7 @@ class PhysicsVAE(nn.Module):
             raise NotImplementedError(cfg["log_std_type"])                      # rmt:182-183
         if cfg["latent_prior_type"] not in PRIOR_KINDS:
             raise NotImplementedError("Unknown latent_prior_type:%s" % (cfg["latent_prior_type"],))    # rmt:624-625
-        # rmt:470, 485: any non-empty subset of ["body", "task"] -- a column window of the full-width first layer (engine.Arch)
+        # rmt:470, 485: any non-empty subset of ["body", "task"] -- a column window of the full-width first layer (arch.Arch)
         self._task_encoder_inputs = list(cfg["task_encoder_inputs"])
         self._motor_decoder_inputs = list(cfg["motor_decoder_inputs"])
 
@@ -794,7 +795,7 @@ class PhysicsVAE(nn.Module):
         already holds stay valid; `value_function()` reads the same values where they now live."""
         ve = self.__dict__.get("_value_engine")
         if ve is None:
-            from .engine import StackSetEngine
+            from .stack_set import StackSetEngine
             ve = StackSetEngine(self.dim_state, [(self.__dict__["_vb_stack"], 1)], self.engine.max_batch,
                                 device=self.engine.device)
             with torch.no_grad():

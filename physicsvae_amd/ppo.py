@@ -77,7 +77,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import engine as E
+from . import engine_ppo as E
 
 # RLlib's sample-batch keys -> the names of the loss's specification
 SAMPLE_BATCH_KEYS = {"obs": "obs", "actions": "actions", "action_dist_inputs": "old_dist", "action_logp": "old_logp",
@@ -338,7 +338,7 @@ class HipPPOLoss(torch.autograd.Function):
     """The loss head (`pvae_ppo_loss`, one launch + its finishing reduction) under autograd, for a learner that keeps its
     own optimizer: `total, stats = HipPPOLoss.apply(mean, log_std, value, batch, cfg, index)`.  mean / log_std [B, k]
     (log_std may be an expanded vector), value [B]; `batch`: the columns under the specification's names (or what
-    `engine.make_ppo_batch` returned), row r read at index[r] (None: at r).  The gradients are computed in the forward
+    `engine_ppo.make_ppo_batch` returned), row r read at index[r] (None: at r).  The gradients are computed in the forward
     launch and scaled by the incoming gradient in backward; `stats` carries no gradient.  No double backward."""
 
     @staticmethod

@@ -1,9 +1,11 @@
 """Digests of everything the on-device PPO learner computes, for comparing two builds of the library bit for bit: in one
 process, with fixed seeds, every entry point that runs the learner's kernels (the fused steps of the stack set and of
-PhysicsVAE, `pvae_ppo_loss`, `pvae_gae`, evaluate and prepare of both models) at the smallest shapes that still take every
-path -- k 5 (a padded column-sum stride), 70 rows in minibatches of 33 (a two-tile step with pad rows and a 4-row step on
-the GEMV / zero-rows path), segments of 1, 63, 64, 65 and 130 rows (a piece boundary and a carry), 70 rows in 40 segments at
-max_batch 32 (more than one chunk in the rows pass and in the bootstrap pass, the last one short).  Prints one JSON line:
+PhysicsVAE -- the whole learn, single steps, and gradient + apply --, `pvae_ppo_loss`, `pvae_gae`, evaluate, prepare and
+the action sampling of both models) at the smallest shapes that still take every path -- k 5 (a padded column-sum stride),
+70 rows in minibatches of 33 (a two-tile step with pad rows and a 4-row step on the GEMV / zero-rows path), segments of 1,
+63, 64, 65 and 130 rows (a piece boundary and a carry), 70 rows in 40 segments at max_batch 32 (more than one chunk in the
+rows pass and in the bootstrap pass, the last one short; the action sampling scatters its 70 rows over 80).  Only the
+engines' public methods are called, so the same file runs in an older tree.  Prints one JSON line:
 scenario -> output tensor -> sha256 of its raw bytes.  The library is the in-tree one, or the one PVAE_LIB_PATH names:
 
     python tools/ppo_digest.py > new.json;  PVAE_LIB_PATH=/path/to/other/libpvae_gfx950.so python tools/ppo_digest.py > old.json
@@ -105,6 +107,65 @@ def fc_sgd(out):
                      "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v})
 
 
+def state(eng, ls, ve=None):
+    d = {"params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "log_std": ls, "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v}
+    if ve is not None:
+        d.update({"value_params": ve.params, "value_m": ve.ppo_m, "value_v": ve.ppo_v})
+    return d
+
+
+def steps(out, name, eng, ls, b, params_at, index, train_ls, ve=None, draws=lambda rows: {}):
+    """Single steps (a two-tile one, then the 4-row tail) and, from the state they leave, gradient + apply at half scale."""
+    stats = [eng.ppo_step(b, params_at(1), 0, 33, index, **draws(33)), eng.ppo_step(b, params_at(2), 66, 4, index, **draws(4))]
+    out["%s_step %s" % name] = digest(dict(state(eng, ls, ve), stats=torch.stack(stats)))
+    one, ls_grad = eng.ppo_grad_step(b, params_at(3), 33, 33, index, **draws(33))
+    grads = {"grad%d" % i: g.clone() for i, g in enumerate(eng.ppo_grad_arenas())}
+    eng.ppo_apply(params_at(3), 0.5, ls_grad if train_ls else None)
+    out["%s_grad_apply %s" % name] = digest(dict(state(eng, ls, ve), stats=one, ls_grad=ls_grad, **grads))
+
+
+def fc_steps(out):
+    for kind in (0, 1, 2):
+        for with_index in (False, True):
+            rng = np.random.default_rng(700 + kind)
+            eng, ls = fc_engine(kind, 64, rng)
+            b = batch(rng, 70, 7)
+            params_at = lambda t: CFG.params(kind, -0.5 if kind == 2 else 0.0, adam_t=t)      # noqa: E731
+            steps(out, ("fc", "kind%d index%d" % (kind, with_index)), eng, ls, b, params_at,
+                  perms(rng, 1, 70)[0].contiguous() if with_index else None, kind == 1)
+
+
+def act_columns(n_dst, n_in, latent=None):
+    """Zeroed destination columns of `ppo_act` (the rows no input row is scattered to stay as they are)."""
+    widths = {"actions": K, "env_actions": K, "old_dist": 2 * K, "old_logp": None, "vf_preds": None, "action_noise": K, "obs": n_in}
+    if latent is not None:
+        widths["latent_eps"] = latent
+    return {name: torch.zeros((n_dst,) if w is None else (n_dst, w), dtype=torch.float32, device=DEV) for name, w in widths.items()}
+
+
+def act(out, name, eng, gp, rng, n_in, latent=None):
+    """70 rows at max_batch 32: three chunks.  Philox and supplied noise; in row order and scattered over 80 rows."""
+    obs = dev(rng.standard_normal((70, n_in)).astype(np.float32))
+    noise = dev(rng.standard_normal((70, K)).astype(np.float32))
+    rows = dev((rng.permutation(76)[:70] + 2).astype(np.int32))
+    for supplied in (False, True):
+        kw = {"noise": noise if supplied else None}
+        if latent is not None:
+            kw["eps"] = dev(rng.standard_normal((70, latent)).astype(np.float32)) if supplied else None
+        out["%s_act %s supplied%d" % (name[0], name[1], supplied)] = digest(
+            eng.ppo_act(obs, gp, clip=(-0.5, 0.5), seed=11, offset=5, **kw))
+        out["%s_act %s supplied%d scatter" % (name[0], name[1], supplied)] = digest(
+            eng.ppo_act(obs, gp, clip=(-0.5, 0.5), seed=11, offset=5, out=act_columns(80, n_in, latent), out_row=rows, **kw))
+    out["%s_act %s greedy" % name] = digest(eng.ppo_act(obs, gp, explore=False, seed=11, offset=5))
+
+
+def fc_act(out):
+    for kind in (0, 2):
+        rng = np.random.default_rng(800 + kind)
+        eng, _ = fc_engine(kind, 32, rng)
+        act(out, ("fc", "kind%d" % kind), eng, CFG.gae_params(kind, -0.5 if kind == 2 else 0.0), rng, 7)
+
+
 def loss(out):
     rng = np.random.default_rng(200)
     b = batch(rng, 40, 7)
@@ -185,10 +246,30 @@ def vae_prepare(out):
         out["vae_prepare_given prior_%s" % prior] = digest(eng.ppo_prepare(dict(ro, **sampler), gp))
 
 
+def vae_steps(out):
+    for prior in ("normal_zero_mean_one_std", False):
+        for kind in (0, 1):
+            for with_eps in (False, True):
+                rng = np.random.default_rng(900 + kind)
+                eng, ve, ls = vae_engine(prior, kind, 64, rng)
+                b = batch(rng, 70, 12)
+                eps = dev(rng.standard_normal((33, 4)).astype(np.float32))
+                draws = lambda rows: dict(eps=eps[:rows].contiguous() if with_eps else None, noise=True, seed=11, offset=5)   # noqa: E731
+                steps(out, ("vae", "prior_%s kind%d eps%d" % (prior, kind, with_eps)), eng, ls, b,
+                      lambda t: CFG.params(kind, 0.0, adam_t=t), perms(rng, 1, 70)[0].contiguous(), kind == 1, ve, draws)
+
+
+def vae_act(out):
+    for prior in ("normal_zero_mean_one_std", False):
+        rng = np.random.default_rng(1000)
+        eng, _, _ = vae_engine(prior, 0, 32, rng)
+        act(out, ("vae", "prior_%s" % prior), eng, CFG.gae_params(0), rng, 12, latent=4)
+
+
 def main():
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
     out = {}
-    for scenario in (fc_sgd, loss, gae, fc_prepare, vae_sgd, vae_prepare):
+    for scenario in (fc_sgd, fc_steps, fc_act, loss, gae, fc_prepare, vae_sgd, vae_steps, vae_act, vae_prepare):
         scenario(out)
     print(json.dumps(out, sort_keys=True))
 
