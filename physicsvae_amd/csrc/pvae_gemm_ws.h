@@ -49,12 +49,18 @@ __device__ inline void lds_dma16_sbase(const char* base_uniform, unsigned lane_b
                  : "v"(lane_byte_off), "s"(base_uniform), "s"(m0v)
                  : "memory");
 }
-// A/B switch of the diagnostic builds (build.py defines=["PVAE_LOADER_VADDR"] into ab_libs/): the dense loaders as they
-// were, one 64-bit vector add in front of every DMA.
+// A/B switches of the diagnostic builds (build.py defines=["PVAE_LOADER_VADDR"] into ab_libs/).  PVAE_LOADER_VADDR: the
+// dense loaders as they were, one 64-bit vector add in front of every DMA.  PVAE_WS_READS_AHEAD: the plain 32x32 body's
+// compute waves as they were, the next tile's fragment reads in front of a half-step's MFMAs instead of between them.
 #ifdef PVAE_LOADER_VADDR
 constexpr bool kLoaderScalarBase = false;
 #else
 constexpr bool kLoaderScalarBase = true;
+#endif
+#ifdef PVAE_WS_READS_AHEAD
+constexpr bool kReadsUnderMfma = false;
+#else
+constexpr bool kReadsUnderMfma = true;
 #endif
 // Lane offsets are 32-bit: a tile spans at most 64 rows x ld floats (checked where the launches are planned).
 inline bool ws_offsets_fit(int ldq, int ldp) { return ldq >= 0 && ldq < (1 << 24) && ldp >= 0 && ldp < (1 << 24); }
@@ -304,6 +310,42 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv, f.q[a][s2], acc[a][b], 0, 0, 0);
                     }
         };
+        // The plain kernel's half-step: the 16 MFMAs of the tile in registers with the NEXT tile's fragment reads between
+        // them, one read behind every second MFMA.  All four compute waves leave a barrier together; with the reads in
+        // front, their 16 KB queue on the one LDS port while the in-order wave cannot issue an MFMA until its last read
+        // has issued, and the matrix pipe drains twice per super-step.  Opened with MFMAs, the pipe is busy from the
+        // barrier on and the reads return under it.  (MFMA i of a tile: s2 = i / 4, a = (i / 2) & 1, b = i & 1 -- the
+        // order of mfmas(), so every accumulator sees the same sequence.)
+        constexpr int kReads = P_ROW ? 4 : 6;                      // ds_read instructions per fragment set
+        constexpr int kGap = 2;                                    // MFMAs per read (1 and 3 measured the same)
+        auto fread_one = [&](const float* st, Frag& f, int r) {
+            if (r < 2) f.q[r] = *reinterpret_cast<const v4f*>(st + oq[r]);
+            else if (P_ROW) f.p[r - 2] = *reinterpret_cast<const v4f*>(st + kTile + oq[r - 2]);
+            else f.c[r - 2] = *reinterpret_cast<const v2f*>(st + kTile + (((kq + r - 2) ^ (lh & 1)) * 32) + 2 * li);
+        };
+        auto mfma_range = [&](const Frag& f, int lo, int hi) {
+#pragma unroll
+            for (int i = lo; i < hi; ++i) {
+                const int s2 = i >> 2, a = (i >> 1) & 1, b = i & 1;
+                const float pv = P_ROW ? f.p[b][s2] : f.c[s2][b];
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv, f.q[a][s2], acc[a][b], 0, 0, 0);
+            }
+        };
+        auto half_step = [&](const Frag& cur, Frag& nxt, const float* st) {
+            if (PVAE_PROBE(4)) {                          // probe: no MFMAs (one branch per half-step, as mfmas() has)
+                fread(st, nxt);
+                mfmas(cur);
+                return;
+            }
+#pragma unroll
+            for (int r = 0; r < kReads; ++r) {
+                mfma_range(cur, kGap * r, kGap * r + kGap);
+                __builtin_amdgcn_sched_barrier(0);
+                fread_one(st, nxt, r);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mfma_range(cur, kGap * kReads, 16);
+        };
         __builtin_amdgcn_s_barrier();                              // tile 0 landed
         asm volatile("" ::: "memory");
         PVAE_MARK(0, 1);
@@ -318,19 +360,42 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
         Frag F0, F1;
         fread(lds, F0);
         if constexpr (!Pro::kActive) {
-            for (int t0 = 0; t0 < nk; t0 += 2) {
-                // The fragments of tile t0 (read in the second half of the previous super-step) must have LEFT the LDS before
-                // this barrier: behind it the loaders restage that slot (tile t0+6) and the slot of t0-1 (tile t0+5), ONE
-                // phase after their last reads -- and nothing orders an LDS-DMA write behind a ds_read that is still queued
-                // (cdna_hip_programming.md: restage >= 2 phases after the last read, or 1 phase when an lgkmcnt retired the
-                // reads first).  Alone on the chip the reads return in ~100 cycles and the DMA data arrives >= 1000 cycles
-                // later; with other processes' workgroups on the same CU saturating its LDS port the window opens: round 5
-                // saw ~1 wrong 16- or 32-row tile per 100 hidden-layer launches with 4-8 processes on one GPU
-                // (tools/p2p_race_hunt.py; the one-barrier-per-tile ring restages two phases later and never showed it).
-                // The wait is free: the reads were issued before the 16 MFMAs of the previous half-step.
+            // The fragments of tile t0 (read in the second half of the previous super-step) must have LEFT the LDS before
+            // the barrier of a super-step: behind it the loaders restage that slot (tile t0+6) and the slot of t0-1 (tile
+            // t0+5), ONE phase after their last reads -- and nothing orders an LDS-DMA write behind a ds_read that is still
+            // queued (cdna_hip_programming.md: restage >= 2 phases after the last read, or 1 phase when an lgkmcnt retired
+            // the reads first).  Alone on the chip the reads return in ~100 cycles and the DMA data arrives >= 1000 cycles
+            // later; with other processes' workgroups on the same CU saturating its LDS port the window opens: round 5
+            // saw ~1 wrong 16- or 32-row tile per 100 hidden-layer launches with 4-8 processes on one GPU
+            // (tools/p2p_race_hunt.py; the one-barrier-per-tile ring restages two phases later and never showed it).
+            // The wait is free: the reads were issued among or before the 16 MFMAs of the previous half-step.
+            auto superstep_barrier = [&]() {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();                      // tiles t0+1 and t0+2 landed; slots of t0-1, t0 are free
                 asm volatile("" ::: "memory");
+            };
+            if constexpr (kReadsUnderMfma && QS::kAlwaysFast) {    // (dense operands; the gathered first layers keep their loop)
+                // Whole super-steps without a branch inside (behind a branch hipcc sinks the first half's reads into the
+                // second half, in front of its MFMAs), then the odd tile: one barrier per super-step, as the loaders count
+                // them.  A read is still never issued ahead of the barrier that certifies its tile: the reads of t0+1 and
+                // t0+2 both follow the barrier of their super-step (the last super-step reads a stale slot, never used).
+                int t0 = 0, s1 = 1, s2 = 2;                        // ring slots of tiles t0+1, t0+2
+                for (; t0 + 1 < nk; t0 += 2) {
+                    superstep_barrier();
+                    __builtin_amdgcn_sched_barrier(0);             // (and no MFMA of this super-step ahead of the barrier)
+                    half_step(F0, F1, lds + s1 * kStage);
+                    half_step(F1, F0, lds + s2 * kStage);
+                    s1 = s1 + 2 >= S ? s1 + 2 - S : s1 + 2;
+                    s2 = s2 + 2 >= S ? s2 + 2 - S : s2 + 2;
+                }
+                if (t0 < nk) {
+                    superstep_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    mfmas(F0);
+                }
+            } else {
+            for (int t0 = 0; t0 < nk; t0 += 2) {
+                superstep_barrier();
                 fread(lds + ((t0 + 1) % S) * kStage, F1);          // (past the end: stale slot, never used)
                 __builtin_amdgcn_sched_barrier(0);
                 mfmas(F0);
@@ -339,6 +404,7 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                     __builtin_amdgcn_sched_barrier(0);
                     mfmas(F1);
                 }
+            }
             }
         } else
         for (int t0 = 0; t0 < nk; t0 += 2) {

@@ -4,6 +4,14 @@
 // period of back-to-back dependent launches (HIP events) and the per-workgroup timeline relative to
 // the first workgroup's entry.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/timeline_probe.hip -o tools/timeline_probe.out
+// Arms of an A/B are builds of this file with the library's compile-time switches (pvae_gemm_ws.h), run alternating in one
+// session.  Round 8's four (profiles/r08_timeline_probe_superstep_arms.txt), with docs/patches/r08_ws_loader_tile_m0.patch
+// applied for the loader arm:
+//   A  -DPVAE_WS_DMA_M0_EACH -DPVAE_WS_READS_AHEAD   the k-loop as it was
+//   B  -DPVAE_WS_READS_AHEAD                         loaders only: a tile's four DMAs behind one M0 write
+//   C  -DPVAE_WS_DMA_M0_EACH                         compute waves only: fragment reads between the MFMAs (= the tree)
+//   D                                                both
+// (the tree without the patch has no loader switch: A is -DPVAE_WS_READS_AHEAD alone, C no define)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
