@@ -62,6 +62,20 @@ constexpr bool kReadsUnderMfma = false;
 #else
 constexpr bool kReadsUnderMfma = true;
 #endif
+// PVAE_WS_PROLOGUE_SERIAL: the plain dense 32x32 body's prologue as it was -- only k-tile 0 fetched by all eight waves, tile 1
+// by the loaders in front of barrier #0 and tiles 2-4 behind it.  PVAE_WS_PROLOGUE_AHEAD=0 / 1 / 2: how many of the loaders'
+// tiles 3 and 4 the new prologue requests in front of barrier #0 (1: tile 3 in front, tile 4 behind -- with both in front
+// barrier #0 moves 0.2 us later and the step gains nothing; profiles/r09_ab_prologue.txt).
+#ifdef PVAE_WS_PROLOGUE_SERIAL
+constexpr bool kWidePrologue = false;
+#else
+constexpr bool kWidePrologue = true;
+#endif
+#ifndef PVAE_WS_PROLOGUE_AHEAD
+#define PVAE_WS_PROLOGUE_AHEAD 1
+#endif
+constexpr int kPrologueAhead = PVAE_WS_PROLOGUE_AHEAD;     // of the loaders' tiles 3 and 4, how many go in front of barrier #0
+static_assert(kPrologueAhead >= 0 && kPrologueAhead <= 2, "tiles 3 and 4");
 // Lane offsets are 32-bit: a tile spans at most 64 rows x ld floats (checked where the launches are planned).
 inline bool ws_offsets_fit(int ldq, int ldp) { return ldq >= 0 && ldq < (1 << 24) && ldp >= 0 && ldp < (1 << 24); }
 // The dense loaders' walk over the k-tiles: tile bases (bytes) and ring slot advance by wrap-around increments, all of it
@@ -139,7 +153,38 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
     // instructions each): it is in flight ~0.1 us after the workgroup starts instead of queueing
     // behind the loaders' three-tile prologue (each global_load_lds holds its wave ~150 cycles, so
     // the prologue alone took 0.67 us -- tools/timeline_probe.hip).
-    if constexpr (kSB) {
+    // Plain dense body: so are k-tiles 1 and 2 -- six DMAs per wave through the two lane offsets of tile 0, ring slot and
+    // k-tile advanced by the loaders' walk (SGPRs).  All three are requested before anything is waited for: the first
+    // super-step's barrier certifies tiles 1 and 2, and behind a loaders-only prologue tile 2 was requested only after tile 0
+    // had landed (two memory round trips in a row in front of the first MFMA).  Slots 1-4 have never been read at this point,
+    // so the restaging rule of the super-step barrier (see the compute waves) is not involved.
+    constexpr bool kWide = kSB && !Pro::kActive && kWidePrologue;
+    DenseWalk walk(qb0, pb0, BK * 4, kstep_p * 4, nk);
+    unsigned vq[kWsPer], vp[kWsPer];                      // dense loaders: lane offsets of this wave's pieces of a tile
+    if constexpr (kWide) {
+        const int j = wave * 64 + lane;                   // 16-byte slot inside the 8 KB tile image
+        const unsigned vq0 = off_q(j), vp0 = off_p(j);
+        // A loader wave's second piece of a tile is its eighth of it; the offsets of its first piece are computed HERE, in
+        // front of the DMAs: behind them hipcc puts an s_waitcnt vmcnt(0) in front of the loader path's first vector-ALU
+        // instruction (it merges the compute path's pending epilogue preload into that block), and the loaders then request
+        // nothing more until everything above has landed.
+        static_assert(kWsLoaders == 4 && kWsPer == 2, "loader wave w takes pieces w - 4 and w");
+        if (wave >= 4) {
+            vq[0] = off_q(j - 256), vp[0] = off_p(j - 256);
+            vq[1] = vq0, vp[1] = vp0;
+        }
+        if (!PVAE_PROBE(6)) {
+            walk.seek(rot, 0);
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if (i < nk) {
+                    float* slot = lds + walk.slot * kStage;
+                    lds_dma16_sbase(i && PVAE_PROBE(2) ? qb0 : walk.q, vq0, slot + wave * 256);
+                    lds_dma16_sbase(i && PVAE_PROBE(2) ? pb0 : walk.p, vp0, slot + kTile + wave * 256);
+                    walk.template next<S>();              // (ends on tile 3 / slot 3, where the loaders go on)
+                }
+        }
+    } else if constexpr (kSB) {
         if (!PVAE_PROBE(6) && wave < 8) {
             const int j = wave * 64 + lane;               // 16-byte slot inside the 8 KB tile image
             lds_dma16_sbase(qb0 + (size_t)rot * (BK * 4), off_q(j), lds + wave * 256);
@@ -186,14 +231,14 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
         }
         // dense operands: lane offsets of this wave's pieces (distinct VGPRs), tile walk in SGPRs; issue() is called
         // for t = 1, 2, 3, ... in order, so the walk only ever steps to the next tile
-        unsigned vq[kWsPer], vp[kWsPer];
+        if constexpr (!kWide) {
 #pragma unroll
-        for (int u = 0; u < kWsPer; ++u) {
-            vq[u] = off_q((u0 + kWsLoaders * u) * 64 + lane);
-            vp[u] = off_p((u0 + kWsLoaders * u) * 64 + lane);
-        }
-        DenseWalk walk(qb0, pb0, BK * 4, kstep_p * 4, nk);
-        walk.seek(rot + 1 < nk ? rot + 1 : 0, 1);
+            for (int u = 0; u < kWsPer; ++u) {
+                vq[u] = off_q((u0 + kWsLoaders * u) * 64 + lane);
+                vp[u] = off_p((u0 + kWsLoaders * u) * 64 + lane);
+            }
+            walk.seek(rot + 1 < nk ? rot + 1 : 0, 1);
+        }                                                 // (wide prologue: offsets and walk stand as it left them)
         auto issue = [&](int t) {
             if (PVAE_PROBE(6)) return;                    // probe: loaders only keep the barriers
             if constexpr (kSB) {
@@ -226,9 +271,24 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                 }
             }
         };
+        if constexpr (kWide) {
+            // tile 3 rides on tile 0's flight time, tile 4 follows behind barrier #0 (kPrologueAhead).  This wave's share of
+            // tile 0 (its oldest two DMAs) has landed once only its shares of tiles 1, 2 (two each) and its pieces of the
+            // tiles requested here (2 * kWsPer each) are in flight.
+            static_assert(kWsPer == 2, "the counted waits of the prologue");
+            if (3 < nk && kPrologueAhead >= 1) issue(3);
+            if (4 < nk && kPrologueAhead >= 2) issue(4);
+            PVAE_MARK(256, 4);
+            if (4 < nk && kPrologueAhead >= 2) wait_vmcnt<12>();
+            else if (3 < nk && kPrologueAhead >= 1) wait_vmcnt<8>();
+            else if (2 < nk) wait_vmcnt<4>();
+            else if (nk == 2) wait_vmcnt<2>();
+            else wait_vmcnt<0>();
+        } else {
         if (1 < nk) issue(1);                                    // rides on tile 0's flight time
         PVAE_MARK(256, 4);
         if (1 < nk) wait_vmcnt<2 * kWsPer>(); else wait_vmcnt<0>();   // this wave's share of tile 0 landed
+        }
         PVAE_MARK(256, 5);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -239,9 +299,16 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
             // super-steps of TWO k-tiles per workgroup barrier.  At the barrier in front of tiles (t0, t0+1): t0+1 and t0+2
             // have landed, t0+3 and t0+4 are in flight; the slots of t0-1 and t0 (whose fragment reads the compute waves
             // have retired, see there) take t0+5 and t0+6.
-            if (2 < nk) issue(2);
-            if (3 < nk) issue(3);
-            if (4 < nk) issue(4);
+            // (Wide prologue: tiles 1 and 2 came from all eight waves -- this wave's shares are older than its tiles 3 and
+            // 4, so the same ladder certifies them at t0 = 0, and the compute waves wait for theirs in front of their loop.)
+            if constexpr (kWide) {
+                if (3 < nk && kPrologueAhead < 1) issue(3);
+                if (4 < nk && kPrologueAhead < 2) issue(4);
+            } else {
+                if (2 < nk) issue(2);
+                if (3 < nk) issue(3);
+                if (4 < nk) issue(4);
+            }
             for (int t0 = 0; t0 < nk; t0 += 2) {
                 const int younger = nk - 3 - t0;                   // tiles t0+3, t0+4 that exist
                 if (younger >= 2) wait_vmcnt<4 * kWsPer>();
@@ -279,8 +346,16 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
             oq[a] = row * 64 + (((4 * wave + lh) ^ (row & 15)) << 2);
         }
         const int kq = 16 * wave + 4 * lh;
-        wait_vmcnt<0>();                                           // this wave's share of tile 0 landed
-        epre = epi.preload(q0 + (tid >> 3), p0 + ((tid & 7) << 2));   // epilogue operands: arrive under the loop
+        // this wave's share of tile 0 landed (wide prologue: its shares of tiles 1 and 2, two DMAs each, may still be in
+        // flight -- one wave's DMAs retire in order, tools/lds_dma_order_probe.hip)
+        // Wide prologue: the epilogue operands are requested in front of that wait -- the vmcnt(0) in front of the loop waits for
+        // them as well, and requested behind the wait they were ~80 ns late for it (timeline probe).  Being younger than the
+        // DMAs they only make the counted wait stricter.
+        if constexpr (kWide) epre = epi.preload(q0 + (tid >> 3), p0 + ((tid & 7) << 2));
+        if (kWide && 2 < nk) wait_vmcnt<4>();
+        else if (kWide && 1 < nk) wait_vmcnt<2>();
+        else wait_vmcnt<0>();
+        if constexpr (!kWide) epre = epi.preload(q0 + (tid >> 3), p0 + ((tid & 7) << 2));   // epilogue operands: arrive under the loop
         typename Pro::State pst = pro.prepare(q0, tid);
         struct Frag { v4f q[2], p[2]; v2f c[4]; };
         auto fread = [&](const float* st, Frag& f) {
@@ -348,7 +423,13 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
         };
         __builtin_amdgcn_s_barrier();                              // tile 0 landed
         asm volatile("" ::: "memory");
-        PVAE_MARK(0, 1);
+#ifdef PVAE_TIMELINE
+        // (where mark 6 exists, mark 1 is taken here and stored with it: a store counts on vmcnt, and the wide prologue's
+        // vmcnt(0) in front of the loop would wait ~80 ns for it)
+        constexpr bool kSeenLater = !Pro::kActive && kReadsUnderMfma && QS::kAlwaysFast;
+        const unsigned long long t_seen = wall_clock64();
+        if (!kSeenLater && tid == 0) g_timeline[(size_t)blockIdx.x * 8 + 1] = t_seen;
+#endif
         if constexpr (Pro::kActive) {
             if (pro.needs(0)) {
                 pro.patch(lds, scratch, pst, 0, q0, tile_p, tile_q, tid);
@@ -374,12 +455,27 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                 __builtin_amdgcn_s_barrier();                      // tiles t0+1 and t0+2 landed; slots of t0-1, t0 are free
                 asm volatile("" ::: "memory");
             };
+            // wide prologue: this wave's shares of tiles 1 and 2 landed -- certified by the first super-step's barrier, which
+            // waits for the loaders' shares of the same tiles anyway; nothing is added inside the loop
+            if constexpr (kWide) wait_vmcnt<0>();
             if constexpr (kReadsUnderMfma && QS::kAlwaysFast) {    // (dense operands; the gathered first layers keep their loop)
                 // Whole super-steps without a branch inside (behind a branch hipcc sinks the first half's reads into the
                 // second half, in front of its MFMAs), then the odd tile: one barrier per super-step, as the loaders count
                 // them.  A read is still never issued ahead of the barrier that certifies its tile: the reads of t0+1 and
                 // t0+2 both follow the barrier of their super-step (the last super-step reads a stale slot, never used).
                 int t0 = 0, s1 = 1, s2 = 2;                        // ring slots of tiles t0+1, t0+2
+#ifdef PVAE_TIMELINE
+                // (timeline builds: the first super-step stands in front of the loop, for the mark at its barrier's exit)
+                if (1 < nk) {
+                    superstep_barrier();
+                    PVAE_MARK(0, 6);                               // first super-step open
+                    if (tid == 0) g_timeline[(size_t)blockIdx.x * 8 + 1] = t_seen;
+                    __builtin_amdgcn_sched_barrier(0);
+                    half_step(F0, F1, lds + s1 * kStage);
+                    half_step(F1, F0, lds + s2 * kStage);
+                    t0 = 2, s1 = 3, s2 = 4;
+                }
+#endif
                 for (; t0 + 1 < nk; t0 += 2) {
                     superstep_barrier();
                     __builtin_amdgcn_sched_barrier(0);             // (and no MFMA of this super-step ahead of the barrier)
@@ -390,6 +486,12 @@ __device__ inline void splitk_ws_body(float* lds, int bid, const GemmArgs& ga, E
                 }
                 if (t0 < nk) {
                     superstep_barrier();
+#ifdef PVAE_TIMELINE
+                    if (t0 == 0) {                                 // (a single k-tile: its only barrier)
+                        PVAE_MARK(0, 6);
+                        if (tid == 0) g_timeline[(size_t)blockIdx.x * 8 + 1] = t_seen;
+                    }
+#endif
                     __builtin_amdgcn_sched_barrier(0);
                     mfmas(F0);
                 }

@@ -12,6 +12,10 @@
 //   C  -DPVAE_WS_DMA_M0_EACH                         compute waves only: fragment reads between the MFMAs (= the tree)
 //   D                                                both
 // (the tree without the patch has no loader switch: A is -DPVAE_WS_READS_AHEAD alone, C no define)
+// Round 9's four (profiles/r09_timeline_probe_prologue.txt), built with the library's -mllvm -amdgpu-kernarg-preload-count=16:
+//   S  -DPVAE_WS_PROLOGUE_SERIAL      the prologue as it was: tile 0 by all eight waves, tiles 1-4 by the loaders
+//   M / L / N  -DPVAE_WS_PROLOGUE_AHEAD=0 / 1 / 2   tiles 0-2 by all eight waves, none / tile 3 / tiles 3 and 4 of the
+//      loaders' in front of barrier #0 (L = the tree)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -59,17 +63,24 @@ int main() {
         CK(hipMemcpy(h.data(), T, h.size() * 8, hipMemcpyDeviceToHost));     // marks of the last launch
         unsigned long long t0 = ~0ull;
         for (int w = 0; w < g.grid; ++w) t0 = std::min(t0, h[(size_t)w * 8 + 0]);
-        const char* names[6] = {"entered", "tile 0 seen by compute", "main loop done", "epilogue issued",
-                                "prologue loads issued", "tile 0 landed (loader)"};
+        const char* names[7] = {"entered", "tile 0 seen by compute", "main loop done", "epilogue issued",
+                                "prologue loads issued", "tile 0 landed (loader)", "first super-step open"};
         printf("K=%4d  %3d workgroups  mode %d  launch period %.2f us (back-to-back, same stream)\n", K, g.grid, c.mode,
                ms * 1e3 / iters);
-        for (int id : {0, 4, 5, 1, 2, 3}) {
+        for (int id : {0, 4, 5, 1, 6, 2, 3}) {
             std::vector<double> v;
             for (int w = 0; w < g.grid; ++w) v.push_back((double)(h[(size_t)w * 8 + id] - t0) * 0.01);
             std::sort(v.begin(), v.end());
             printf("   %-24s min %6.2f  median %6.2f  max %6.2f us after the first workgroup entered\n", names[id],
                    v.front(), v[v.size() / 2], v.back());
         }
+        // the compute waves' wait for tiles 1 and 2: each workgroup's own (first super-step open - tile 0 seen), which also
+        // holds the first fragment read (~0.1 us); 10 ns clock
+        std::vector<double> open;
+        for (int w = 0; w < g.grid; ++w) open.push_back((double)(h[(size_t)w * 8 + 6] - h[(size_t)w * 8 + 1]) * 10.0);
+        std::sort(open.begin(), open.end());
+        printf("   tile 0 seen -> first super-step open   min %6.1f  median %6.1f  max %6.1f ns\n", open.front(),
+               open[open.size() / 2], open.back());
         // k-tile period: each workgroup's own (main loop done - tile 0 seen) over its K / 64 k-tiles
         std::vector<double> per;
         for (int w = 0; w < g.grid; ++w)
