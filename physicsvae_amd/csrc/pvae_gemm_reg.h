@@ -32,7 +32,7 @@ namespace pvae {
 // ---- forward / dgrad: C[32 q][32 p] per workgroup, BK = 64, the 4 waves split K -------------
 //   Q is always ROW (X or dZ, k-contiguous).  P_ROW: W[p][k] (forward);  !P_ROW: W[k][p] (dgrad).
 // ABL (tools/pair_lab.hip, tools/pair_probe.hip only; 0 in production): 1 = no tile staging in the loop, 2 = no LDS
-// fragment reads, 4 = no MFMA, 8 = no barrier.
+// fragment reads, 4 = no MFMA, 8 = no barrier, 16 = no gradient store (wgrad_reg_body only: epi.apply skipped).
 // ---------------------------------------------------------------------------------------
 // Split-K partial tile of a wave -> its LDS reduction buffer red[32][RS], with 16-byte writes: the MFMA layout gives
 // each lane runs of consecutive p (P_ROW: acc[a][b] = 4 consecutive p of row 16a + li; output-contiguous operands:

@@ -83,12 +83,20 @@ __device__ inline void wgrad_reg_body(float* lds, int bid, const GemmArgs& ga, E
     lwrite(lds, rg[0]);
     gload(D < nk ? D : nk - 1, rg[0], 0);
     // epilogue operands: queued behind the first D tiles, they arrive while the loop runs
+#ifdef PVAE_WGRAD_EPI_DIRECT
     typename Epi::Pre pre[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
         pre[a][0] = epi.load(q0 + wq + 2 * li + a, p0 + wp + 8 * lh);
         pre[a][1] = epi.load(q0 + wq + 2 * li + a, p0 + wp + 8 * lh + 4);
     }
+#else
+    // (the epilogue's mapping: thread t owns columns 4 (t & 15) .. + 3 of rows (t >> 4) + 16 i -- whole 256-byte rows)
+    const int eq = tid >> 4, ep = (tid & 15) << 2;
+    typename Epi::Pre pre[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pre[i] = epi.load(q0 + eq + 16 * i, p0 + ep);
+#endif
     __syncthreads();
 
     // one k-tile: 8 steps of (2 fragment reads, 4 MFMAs); after step 3 the next tile moves from its
@@ -168,7 +176,7 @@ __device__ inline void wgrad_reg_body(float* lds, int bid, const GemmArgs& ga, E
         if (!(ABL & 8)) __syncthreads();
     };
     auto tile_step = [&](int t, int d, bool guarded) {
-        if constexpr (ABL == 0) tile_step_piped(t, d, guarded);
+        if constexpr ((ABL & 15) == 0) tile_step_piped(t, d, guarded);
         else tile_step_plain(t, d, guarded);
     };
     int t0 = 0;
@@ -181,12 +189,43 @@ __device__ inline void wgrad_reg_body(float* lds, int bid, const GemmArgs& ga, E
         if (t0 + d < nk) tile_step(t0 + d, d, true);
 
     PVAE_MARK(0, 2);                                             // contraction done, epilogue (Adam) starts
+    auto emit = [&](int q, int p, v4f v, const typename Epi::Pre& pr) {
+        if (ABL & 16) asm volatile("" ::"v"(v));       // (probes) the finished values stay live, nothing is stored
+        else epi.apply(q, p, v, pr);
+    };
+#ifdef PVAE_WGRAD_EPI_DIRECT
+    // straight out of the MFMA layout: a wave-instruction writes 16 rows x four 16-byte pieces 32 bytes apart, and a
+    // second one fills the holes (kept for the A/B)
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
         const int q = q0 + wq + 2 * li + a, p = p0 + wp + 8 * lh;
-        epi.apply(q, p, v4f{acc[a][0][0], acc[a][1][0], acc[a][0][1], acc[a][1][1]}, pre[a][0]);
-        epi.apply(q, p + 4, v4f{acc[a][0][2], acc[a][1][2], acc[a][0][3], acc[a][1][3]}, pre[a][1]);
+        emit(q, p, v4f{acc[a][0][0], acc[a][1][0], acc[a][0][1], acc[a][1][1]}, pre[a][0]);
+        emit(q, p + 4, v4f{acc[a][0][2], acc[a][1][2], acc[a][0][3], acc[a][1][3]}, pre[a][1]);
     }
+#else
+    // Through LDS into whole rows.  Lane (li, lh) holds, for a = 0, 1, columns 8 lh .. 8 lh + 7 of row 2 li + a of its
+    // wave's 32x32 sub-tile; stored as it stands, each line of G is written by two instructions with a checkerboard
+    // byte mask.  The ring is free (every thread has passed the last tile's barrier), so the tile goes to LDS and comes
+    // back as 4 rows x 256 contiguous bytes per wave-instruction.  Row 2 li + a of a sub-tile is kept at LDS row
+    // 16 a + li of its 32-row half, rows RS = 68 dwords apart: the eight lanes of a ds_write_b128 group (li = 0..7) are
+    // 68 = 4 (mod 32) dwords apart, every bank once; a ds_read_b128 group is 8 + 8 lanes of two LDS rows 16 apart
+    // (16 x 68 = 0 mod 64) covering dwords 0-15, 48-63 of one and 16-47 of the other, every bank once.
+    constexpr int RS = 68;
+    static_assert(64 * RS <= kRegRingFloats, "ring must hold the output tile");
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        float* row = lds + (wq + 16 * a + li) * RS + wp + 8 * lh;
+        *reinterpret_cast<v4f*>(row) = v4f{acc[a][0][0], acc[a][1][0], acc[a][0][1], acc[a][1][1]};
+        *reinterpret_cast<v4f*>(row + 4) = v4f{acc[a][0][2], acc[a][1][2], acc[a][0][3], acc[a][1][3]};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = eq + 16 * i;                                      // output row of the tile
+        const int lr = (r & 32) + 16 * (r & 1) + ((r & 31) >> 1);       // where it is kept
+        emit(q0 + r, p0 + ep, *reinterpret_cast<const v4f*>(lds + lr * RS + ep), pre[i]);
+    }
+#endif
     if (epi.loss.out && bid == 0 && wave == 3) finalize_loss_wave(epi.loss, lane);
 }
 

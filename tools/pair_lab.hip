@@ -3,6 +3,7 @@
 // at the BASELINE sizes (256 x 1024 x 1024), on RANDOM operands (zero-filled buffers clock ~19 % higher,
 // MI355X_MICROARCH.md DVFS note), timed as the period of back-to-back launches on one stream.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/pair_lab.hip -o ab_libs/pair_lab
+//   (-DPVAE_WGRAD_EPI_DIRECT: the weight-gradient epilogue of rounds 1-9, for the A/B of round 10)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -112,13 +113,19 @@ int main() {
                    pass ? "ZERO" : "random", us, ghz, per, 256 * 4 * 2048.0 / 32.0 * ghz * 1e9 / 1e12);
         }
     }
+#ifdef PVAE_WGRAD_EPI_DIRECT
+    printf("variant: -DPVAE_WGRAD_EPI_DIRECT (weight gradient stored straight out of the MFMA layout)\n");
+#else
     printf("variant: production stores (sc1 write-through)\n");
+#endif
 #define T(ABL, parts, name) printf("  %-64s %6.2f us\n", name, time_pair<ABL>(st, dZ, W, X, act, dX, G, M, N, K, parts, ad, a, b))
     T(0, 15, "complete: dgrad || wgrad || bias || 256 Adam workgroups");
     T(0, 7, "no Adam workgroups");
     T(0, 3, "dgrad || wgrad only");
+    T(16, 3, "dgrad || wgrad, no gradient store");
     T(0, 1, "dgrad workgroups only (256)");
     T(0, 2, "wgrad workgroups only (256)");
+    T(16, 2, "wgrad workgroups only, no gradient store");
     T(0, 8, "Adam workgroups only (256)");
     {
         T(4, 3, "dgrad || wgrad, no MFMA");
