@@ -140,7 +140,8 @@ typedef struct pvae_layer_info {
 typedef struct pvae_step_params {
     float a_rec_coeff;     /* motor_decoder_a_rec_coeff (1.0)  */
     float kl_coeff;        /* vae_kl_coeff (beta)              */
-    float s_rec_coeff;     /* world_model_s_rec_coeff          */
+    float s_rec_coeff;     /* world_model_s_rec_coeff: weight of MSE(s2, WM(s1, a_gt)) (tpv:411-414) in BOTH phases
+                              (1.0 in the world phase, tpv:331-335; the trainer's joint default is 0.0, tpv:284) */
     float cycle_coeff;     /* vae_cycle_coeff (1e-3)           */
     double lr;             /* learning rate of this epoch (double: torch keeps these as   */
     double beta1, beta2, adam_eps; /* Python floats; 1 - beta and the bias corrections are   */
@@ -221,7 +222,11 @@ int pvae_set_direct(pvae_ctx* ctx, int on);
  *       "p2p_timeout_ms" (> 0: the bounded waits of the stack sets' PPO gradient exchange, pvae_fc_ppo_peer_*)
  *   ctx, that context's schedule:  "pair" "defer_adam" "same_layer" "fold_sampler" (0 / 1), "direct" (= pvae_set_direct),
  *       "p2p_timeout_ms" (> 0), "p2p_selftest_flags_only" (0 / 1), "server_mailbox" (0 auto, 1 pinned host memory, 2 device)
- * Every variant gives the same bits as the default (held by tests/test_gpu_shapes.py, test_gpu_fuzz.py).  -1: unknown name. */
+ * Every variant gives the same bits as the default (held by tests/test_gpu_shapes.py, test_gpu_fuzz.py).  -1: unknown name.
+ *   ctx, not a schedule switch:  "joint_s_rec" (0 / 1, default 0): the joint phase accepts pvae_step_params.s_rec_coeff != 0
+ *       (see pvae_forward_backward).  A context that has not opted in keeps refusing that combination with -4, as every
+ *       context did before the term was built; the supervised trainer opts in when its config holds a non-zero
+ *       world_model_s_rec_coeff. */
 int pvae_set_option(pvae_ctx* ctx, const char* name, int64_t value);
 int pvae_direct_active(pvae_ctx* ctx, int phase, int32_t rows, const pvae_step_params* sp, int fused);
 
@@ -254,7 +259,15 @@ int pvae_set_batch(pvae_ctx* ctx, const float* x, const float* y, int32_t rows, 
  * lookahead L > 1 (tpv:367-428): step t+1 starts from the world model's own prediction of step
  * t, so encoder, sampler, decoder and world model run for every step in BOTH phases, the
  * backward pass walks the steps last to first through all three stacks, and each layer's weight
- * gradient is one contraction over the L stacked steps.  Terms are means over the L steps. */
+ * gradient is one contraction over the L stacked steps.  Terms are means over the L steps.
+ * Joint phase with s_rec_coeff > 0 (tpv:411-414 while the world model is frozen, tpv:347-350; the context has opted in
+ * with pvae_set_option(ctx, "joint_s_rec", 1), else -4): the world model also runs
+ * on the DEMONSTRATED action.  At lookahead 1 its inputs are data: a forward-only pass before the decoder's action
+ * overwrites the input panel's action columns, loss_s in loss_out, no gradient -- encoder and decoder gradients are the
+ * bits of the same step with s_rec_coeff = 0.  At lookahead > 1 the state of step t >= 1 is a prediction: the pass of
+ * step t is followed by an input-gradient-only chain whose state columns join the other consumers of step t-1's
+ * prediction.  In neither case is a weight gradient, an Adam update or a gradient-arena write made for the world
+ * model, and the stages pvae_backward_plan reports as finishing a slice are those of s_rec_coeff = 0. */
 int pvae_forward_backward(pvae_ctx* ctx, int phase, int32_t rows, const pvae_step_params* sp,
                           const float* eps, float* loss_out, int flags, void* stream);
 /* Adam over the nets in net_mask (bit n = PVAE_NET_n) using the bound grads arena.

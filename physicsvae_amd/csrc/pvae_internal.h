@@ -237,6 +237,7 @@ struct pvae_ctx {
     bool same_layer_pairs = true;  // PVAE_SAME_LAYER=0: wgrad_i rides with dgrad_{i-1} as before (A/B)
     bool p2p_selftest_flags_only = false;   // option: the attach-time self-test skips the cached-arena part
     int server_mailbox = 0;                 // option: where the rollout server's request block lives (0 auto, 1 host, 2 device)
+    bool joint_s_rec = false;      // option "joint_s_rec": the joint phase runs with world_model_s_rec_coeff != 0 (default: refused, -4)
     bool fold_sampler = true;      // the sampler runs as the prologue of the decoder's first-layer launch (PVAE_FOLD_SAMPLER=0: its own launch)
                                    // (ProSampler).  Off by default: one launch less, but the step is not shorter -- the kernel
                                    // trace shows 6.4-7.0 us for the merged launch against 4.4 + 4.6, and the un-profiled

@@ -36,7 +36,7 @@ struct Unroll {
 static Unroll make_unroll(const pvae_ctx* c, int phase, int rows, const pvae_step_params* sp) {
     Unroll u;
     u.T = c->W.L; u.rows = rows; u.rows_pad = pad32(rows);
-    u.use_g = phase == PVAE_PHASE_WORLD && sp->s_rec_coeff > 0.0f;
+    u.use_g = sp->s_rec_coeff > 0.0f;      // (both phases: tpv:411-414 does not ask which one)
     return u;
 }
 
@@ -83,7 +83,8 @@ int run_forward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_param
         mse.partial = part + 4 * kLossParts + t * S.wm_tiles;
         if ((rc = forward_net(c, PVAE_NET_WM, u.rows_pad, st, wm_tail, bp))) return rc;
         if (u.use_g) {                         // demonstrated action: state reconstruction (tpv:411-414)
-            mse.dz = backward ? w + wwm.dz.back() + bt * ldo_wm : nullptr;
+            // (joint phase, step 0: s1 and a_gt are data and the world model is frozen -- a loss term, no gradient)
+            mse.dz = backward && (!joint || t > 0) ? w + wwm.dz.back() + bt * ldo_wm : nullptr;
             mse.grad_scale = sp->s_rec_coeff * S.gs / (S.Bg * Db);
             mse.partial = part + 3 * kLossParts + t * S.wm_tiles;
             if ((rc = forward_net(c, PVAE_NET_WM, u.rows_pad, st, wm_tail, bt))) return rc;
@@ -268,7 +269,10 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
         const bool upstream = joint || t > 0;
         const bool up_a = upstream || mh_train;   // the action's gradient of this step is wanted (by the helper, if by nobody else)
         const bool pair_wm = look_pair && t == 0 && !joint && krows_of[PVAE_NET_WM] > 0;
-        if (backward && u.use_g) {
+        // joint phase: the world model is frozen (tpv:347-350), so its demonstrated-action invocation is a dgrad-only chain
+        // whose one product is the state columns of d(wm_in) -- the gradient wrt s1_t, a prediction for t >= 1; step 0 has
+        // none to give (pair_wm is false there: no weight gradient, no Adam for the world model)
+        if (backward && u.use_g && (!joint || t > 0)) {
             if (pair_wm && !p_act[t]) paired_chain(PVAE_NET_WM, t, 1, true);    // (no predicted-action chain follows)
             else dgrad_chain(PVAE_NET_WM, t, t > 0);
         }

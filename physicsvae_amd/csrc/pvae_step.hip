@@ -265,6 +265,7 @@ static int step_shape(pvae_ctx* c, int phase, int rows, const pvae_step_params* 
         if (sp->a_rec_coeff > 0.0f)
             S.lf.nparts[0] = S.seed_action ? dgrad_tiles(S.rows_pad, seed_window(Db, Da).width) : S.nparts_a * T;
         if (S.kl_active) S.lf.nparts[1] = S.gridz * T;
+        if (sp->s_rec_coeff > 0.0f) S.lf.nparts[2] = S.wm_tiles * T;       // tpv:411-414 with the world model frozen
         if (sp->cycle_coeff > 0.0f) S.lf.nparts[3] = S.wm_tiles * T;
     }
     return 0;
@@ -280,9 +281,10 @@ static int check_step(pvae_ctx* c, int phase, int32_t rows, const pvae_step_para
     if (rows != c->staged_rows) return fail(-2, "rows %d != staged rows %d", rows, c->staged_rows);
     if (backward && fused && (!c->m || !c->v)) return fail(-2, "Adam moment arenas not bound");
     if (backward && !fused && !c->grads) return fail(-2, "gradient arena not bound");
-    if (phase == PVAE_PHASE_JOINT && sp->s_rec_coeff != 0.0f)
-        return fail(-4, "joint phase with world_model_s_rec_coeff != 0 is not supported "
-                        "(reference default is 0.0, tpv:284)");
+    // (the reference's joint default is 0.0, tpv:284: a context runs the term in the joint phase once its owner has said so)
+    if (phase == PVAE_PHASE_JOINT && sp->s_rec_coeff != 0.0f && !c->joint_s_rec)
+        return fail(-4, "joint phase with world_model_s_rec_coeff != 0 is not supported unless the context opts in "
+                        "(pvae_set_option \"joint_s_rec\"; reference default is 0.0, tpv:284)");
     return 0;
 }
 
@@ -310,20 +312,25 @@ static int run_forward(pvae_ctx* c, int phase, int rows, const pvae_step_params*
     wm_tail.mse = &mse;
     // direct step: every stack's first layer gathers its rows itself, s_{t+1} is read from `states` by the loss epilogue
     const bool dx = c->dx.on;
-    XSrc xs_te, xs_md, xs_wm;
-    ProCols wm_cols;
+    XSrc xs_te, xs_md, xs_wm, xs_wg;
+    ProCols wm_cols, wg_cols;
+    // the world model's gathered first layer: [s_t | a_t] (`src_phase` WORLD) or [s_t | a_hat] (JOINT)
+    auto wm_direct = [&](int src_phase, XSrc& xs, ProCols& cols, FwdTail& tail) {
+        memset(&cols, 0, sizeof(cols));
+        const bool wm64 = uses_64x32(S.rows_pad, WM.layers[0].n_out_pad);
+        xs = xsrc_of(c, PVAE_NET_WM, src_phase, wm64, rows);
+        tail.xs0 = &xs;
+        if (!wm64) {
+            const XSrc full = xsrc_of(c, PVAE_NET_WM, src_phase, true, rows);
+            cols.src = full.s1; cols.ind = full.ind1; cols.rm = full.rm; cols.ld = full.ld1; cols.c0 = Db; cols.n = Da;
+            cols.rows = rows;
+            tail.cols0 = &cols;
+        }
+    };
     memset(&wm_cols, 0, sizeof(wm_cols));
     if (dx) {
         mse.target = c->states + Db; mse.ldt = Db; mse.tind = 1; mse.trm = c->dx.rm;   // row + 1 of the window's s_t
-        const bool wm64 = uses_64x32(S.rows_pad, WM.layers[0].n_out_pad);
-        xs_wm = xsrc_of(c, PVAE_NET_WM, phase, wm64, rows);
-        wm_tail.xs0 = &xs_wm;
-        if (!wm64) {
-            const XSrc full = xsrc_of(c, PVAE_NET_WM, phase, true, rows);
-            wm_cols.src = full.s1; wm_cols.ind = full.ind1; wm_cols.rm = full.rm; wm_cols.ld = full.ld1; wm_cols.c0 = Db; wm_cols.n = Da;
-            wm_cols.rows = rows;
-            wm_tail.cols0 = &wm_cols;
-        }
+        wm_direct(phase, xs_wm, wm_cols, wm_tail);
     }
     if (phase == PVAE_PHASE_WORLD) {
         // tpv:411-414: L = s_rec * MSE(s2, WM(s1, a_gt)); only the world model learns (tpv:326-329)
@@ -342,6 +349,19 @@ static int run_forward(pvae_ctx* c, int phase, int rows, const pvae_step_params*
         if (learned_prior)
             HIP_TRY(hipMemsetAsync(w + wpr.dz.back(), 0, (size_t)c->W.Bp * PR.layers.back().n_out_pad * sizeof(float), st));
         c->seed_pads_clean = true;
+    }
+    if (sp->s_rec_coeff > 0.0f) {
+        // tpv:411-414 with the world model frozen (tpv:347-350): s1 and a_gt are data, so MSE(s2, WM(s1, a_gt)) adds
+        // s_rec * loss_s to the loss and nothing to any gradient -- forward only, no dz.  It runs FIRST: the input panel
+        // holds [s1 | a_gt] until the decoder's tail puts a_hat into the action columns, and the activations it leaves
+        // are overwritten by the predicted-action pass below.
+        EpiMse mse_g = mse;
+        mse_g.dz = nullptr; mse_g.grad_scale = 0.0f;
+        mse_g.partial = part + 3 * kLossParts;
+        FwdTail wg_tail;
+        wg_tail.mse = &mse_g;
+        if (dx) wm_direct(PVAE_PHASE_WORLD, xs_wg, wg_cols, wg_tail);
+        if ((rc = forward_net(c, PVAE_NET_WM, S.rows_pad, st, wg_tail))) return rc;
     }
     // joint forward: [prior mean ->] TE -> sampler -> MD -> WM (rmt:742-771, 801-809)
     if (learned_prior && (rc = forward_net(c, PVAE_NET_PR, S.rows_pad, st))) return rc;

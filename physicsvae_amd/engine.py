@@ -205,6 +205,12 @@ class HipEngine(PpoSurface, DataParallelExchange, RolloutClient):
         self._need_gpu()
         _lib.check(self.lib.pvae_set_direct(self.ctx, 1 if on else 0), "pvae_set_direct")
 
+    def set_joint_s_rec(self, on=True):
+        """The joint phase runs with `world_model_s_rec_coeff` != 0 (tpv:411-414 with the world model frozen; include/pvae.h
+        pvae_set_option "joint_s_rec").  Opt-in: a context that was not told keeps refusing that combination."""
+        self._need_gpu()
+        _lib.check(self.lib.pvae_set_option(self.ctx, b"joint_s_rec", 1 if on else 0), "pvae_set_option(joint_s_rec)")
+
     def direct_active(self, phase, rows, sp, fused=True):
         """Would a training step with these arguments take the direct path?"""
         self._need_gpu()

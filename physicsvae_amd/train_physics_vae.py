@@ -382,6 +382,8 @@ class TrainModel(torch_models.TrainModel):
         self.latent_prior_type = config.get("latent_prior_type")
         self.lookahead = config.get("lookahead")
         super().setup(config)
+        if config.get("world_model_s_rec_coeff") and self.engine.ctx is not None:
+            self.engine.set_joint_s_rec(True)     # tpv:411-414 in the joint phase: the library runs it for a context that asks
         self.model.set_learnable_task_encoder(False)
         self.model.set_learnable_motor_decoder(False)
         self.model.set_learnable_world_model(True)
