@@ -185,6 +185,14 @@ void pvae_destroy(pvae_ctx* ctx);
  * Replaces the per-tensor storage of nn.Linear + torch.optim.Adam state (tm:119-122). */
 int pvae_bind_arenas(pvae_ctx* ctx, float* params, float* grads, float* exp_avg,
                      float* exp_avg_sq);
+/* workspace: device buffer of at least pvae_workspace_bytes() bytes, 256-byte aligned.  It must be ZERO-FILLED when it is
+ * bound, and the caller must not write it afterwards (reading panels through pvae_workspace_offset is fine).  Two things
+ * rely on that: the 64 floats at its end that no launch ever writes and that a gathered first-layer operand reads as its
+ * "no source" columns (pvae_set_direct), and the pad columns of the gradient-seed panels outside the range the library
+ * clears itself on the first backward pass after a bind -- the seed epilogues write the real columns only, and whole
+ * padded tiles are contracted over both.  Everything else the library keeps out of its sums on its own, whatever earlier
+ * calls (of any row count, any phase, pvae_infer included) left behind: held by tests/test_gpu_step_history.py; that no
+ * launch reads into a result or writes outside the bytes counted here, by tests/test_gpu_step_guards.py. */
 int pvae_bind_workspace(pvae_ctx* ctx, void* workspace, size_t bytes);
 /* Demonstration set resident in HBM, de-duplicated: states[n_rows][Db], actions[n_rows][Da]
  * (fp32, dense), window_row[n_windows] = row of s_t (s_{t+1} is row+1, a_t is the same row;
@@ -207,7 +215,10 @@ int pvae_bind_dataset_next(pvae_ctx* ctx, const float* next_states);
  * sampler / the decoder left them, and the two targets s_{t+1}, a_t are read from the set by the loss epilogues.  A step
  * qualifies at lookahead 1 with the default prior, more than 4 rows, first layers wide enough for the 32x32 / 64-row
  * tile kernels, no `next_states` array, and dataset allocations that are readable 16 bytes past their last row (checked
- * at pvae_bind_dataset with hipMemGetAddressRange: a chunk may reach 12 bytes past a row).  Everything else -- and
+ * at pvae_bind_dataset with hipMemGetAddressRange: a chunk may reach 12 bytes past a row).  What those bytes hold reaches
+ * no result: the one joint-phase minibatch whose last window ends on the very last row of `states` stages its panels when
+ * 2 * dim_body is no multiple of 4 (the encoder's operand would otherwise end in a chunk whose tail lies behind the array,
+ * and a NaN pattern there survives the multiplication by the weight block's zero pad columns).  Everything else -- and
  * pvae_gather / pvae_set_batch + pvae_forward_backward always -- goes through the staging launch as before; both paths
  * give the same bits.  OPT-IN: pvae_set_direct(ctx, 1) (default off -- at BASELINE's 256 rows per GPU the staged step is
  * the faster one: its gather rides in the previous step's last launch); pvae_direct_active tells

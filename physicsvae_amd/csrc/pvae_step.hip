@@ -633,6 +633,16 @@ bool DirectStep::enter(pvae_ctx* c, int phase, int64_t first_window, int rows, c
     if (!direct_ok(c, phase, rows, sp, fused)) return false;
     const RowMap rm = row_map(c, first_window, rows);
     if (!rm.seg) return false;             // (more than one episode jump inside the minibatch, or no host copy of window_row)
+    // The encoder's gathered operand [s_t | s_{t+1}] ends inside a 16-byte chunk when 2 Db is no multiple of 4; the chunk's
+    // tail is what follows the row in memory -- the next row, data -- and meets W's zero pad columns (QGather).  Behind the
+    // LAST row of `states` lies no data: the bytes are readable (data_slack), but a NaN or Inf pattern there times zero is
+    // NaN, and the hidden ReLU then drops that window's whole first layer.  The one minibatch of an epoch that holds this
+    // window stages its panels instead (same bits).
+    if (phase == PVAE_PHASE_JOINT && ((2 * c->L.cfg.dim_body) & 3)) {
+        const int64_t last0 = (int64_t)rm.b0 + (rm.q1 < rows ? rm.q1 : rows) - 1;
+        const int64_t last1 = rm.q1 < rows ? (int64_t)rm.b1 + (rows - rm.q1) - 1 : -1;
+        if ((last0 > last1 ? last0 : last1) + 2 >= c->n_rows) return false;
+    }
     c->dx.on = true;
     c->dx.rm = rm;
     memset(&c->next_touch, 0, sizeof(c->next_touch));
