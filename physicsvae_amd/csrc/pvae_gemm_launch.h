@@ -128,7 +128,7 @@ inline hipError_t gemm_forward_epi(const float* X, int ldx, const float* W, int 
     else PVAE_LAUNCH((gemm_splitk_ws_kernel<true, Epi>), dim3(t.grid), dim3(kWsThreads), st, PVAE_GA_PASS(t.ga), e);
     return hipGetLastError();
 }
-// forward layer on 32x32 tiles whose launch forms some of its own input columns (Pro, see splitk_ws_body)
+// forward layer on 32x32 tiles whose launch forms some of its own input columns (Pro, see splitk_ws_pertile_body)
 inline bool forward_pro_ok(int M, int N) { return !forward_uses_16x16(M, N) && !uses_64x32(M, N) && !g_krot && !g_rowxcd; }
 template <class Epi, class Pro>
 inline hipError_t gemm_forward_pro(const float* X, int ldx, const float* W, int ldw, int M, int N, int K, const Epi& e,

@@ -339,7 +339,7 @@ __device__ inline float block_sum_256(float v) {
     return block_sum_256(v, red);
 }
 
-// The same sampler as the PROLOGUE of the decoder's first-layer launch (pvae_gemm.h, splitk_ws_body / NoPro): every
+// The same sampler as the PROLOGUE of the decoder's first-layer launch (pvae_gemm_ws.h, splitk_ws_pertile_body): every
 // workgroup of that launch forms z for its own 32 batch rows while its first k-tile is in flight and patches it over
 // the z columns of its input tile in LDS; the workgroups of column tile 0 also store z (the decoder's first-layer
 // weight gradient reads it from the input panel), the draws actually used, and the KL partial of their row block.

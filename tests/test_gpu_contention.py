@@ -1,6 +1,6 @@
 """The step under CONTENTION: four processes share the GPU, each repeating the same three optimizer steps from the same
 state; every arena must equal the first repetition's bit for bit.  Round 5's one real kernel bug -- a write-after-read race
-in the six-slot LDS-DMA ring of the wave-specialised forward kernel (pvae_gemm_ws.h, `splitk_ws_body`) -- was invisible to
+in the six-slot LDS-DMA ring of the wave-specialised forward kernel (pvae_gemm_ws.h, `splitk_ws_superstep_body`) -- was invisible to
 every single-process test and showed within tens of repetitions as soon as other processes' workgroups shared the CUs
 (the same pressure an RCCL or peer-exchange kernel beside the step exerts on a real node).  This is that hunt
 (tools/p2p_race_hunt.py) as a driver-run test, over EVERY LDS-DMA ring the step can run on:

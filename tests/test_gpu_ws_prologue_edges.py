@@ -1,4 +1,4 @@
-"""The prologue of the plain dense 32x32 forward / input-gradient body (pvae_gemm_ws.h, splitk_ws_body): k-tiles 0, 1 and 2
+"""The prologue of the plain dense 32x32 forward / input-gradient body (pvae_gemm_ws.h, splitk_ws_superstep_body): k-tiles 0, 1 and 2
 are fetched by all eight waves (six LDS-DMAs each, counted waits), the loaders add tile 3 in front of barrier #0 and tile 4
 behind it, and the compute waves certify their shares of tiles 1 and 2 in front of their loop.  Contraction lengths of nk = 1, 2, 3, 4, 5,
 6, 8, 9 and 16 k-tiles take every guard of that prologue (tiles 1 ... 4 present or absent), the first loop iteration with

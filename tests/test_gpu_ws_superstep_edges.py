@@ -1,4 +1,4 @@
-"""Every edge of the plain 32x32 forward / input-gradient k-loop (splitk_ws_body: six-slot ring, super-steps of two k-tiles
+"""Every edge of the plain 32x32 forward / input-gradient k-loop (splitk_ws_superstep_body: six-slot ring, super-steps of two k-tiles
 per workgroup barrier, a loader wave's four DMAs of a tile behind one M0 write, the compute waves' fragment reads between
 the MFMAs): contraction lengths of nk = 1 ... 7 and 13 k-tiles -- every branch of the loaders' prologue (issue(2..4)
 present or absent), odd and even tails of the super-step, and the first wrap of the ring (nk >= 7) -- through gemm_probe,

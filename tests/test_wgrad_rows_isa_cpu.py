@@ -3,35 +3,23 @@ gemm_wgrad_reg_kernel<EpiGradStore>: the tile's four global stores come behind t
 four ds_read_b128 (the tile returns from LDS as whole rows) with no MFMA between them, the kernel has exactly one barrier
 more than the build with the old epilogue (-DPVAE_WGRAD_EPI_DIRECT), and no more registers.  pvae_probe.hip is compiled
 with the flags of physicsvae_amd/build.py.  No GPU needed; skipped where there is no hipcc."""
-import os
 import re
-import subprocess
 
 import pytest
 
-from physicsvae_amd import build as B
-from test_loader_isa_cpu import function_lines
+from isa import assembly, function_lines
 
 KERNEL = r"_ZN4pvae\d+gemm_wgrad_reg_kernelINS_12EpiGradStoreELi0EEE"
 
 
 @pytest.fixture(scope="module")
-def builds(tmp_path_factory):
+def builds():
     """{"rows" / "direct": (instruction mnemonics of the kernel, its .vgpr_count)}"""
-    try:
-        cc = B._hipcc()
-    except RuntimeError:
-        pytest.skip("no hipcc")
-    tmp = tmp_path_factory.mktemp("isa")
     out = {}
-    for name, flags in (("rows", []), ("direct", ["-DPVAE_WGRAD_EPI_DIRECT"])):
-        path = str(tmp / (name + ".s"))
-        res = subprocess.run([cc] + B.FLAGS + flags + ["-S", "--cuda-device-only", os.path.join(B.CSRC, "pvae_probe.hip"), "-o", path],
-                             capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr
-        with open(path) as f:
-            text = f.read()
-        fn = function_lines(text.split("\n"), KERNEL)
+    for name, flags in (("rows", ()), ("direct", ("-DPVAE_WGRAD_EPI_DIRECT",))):
+        lines = assembly("pvae_probe.hip", flags)
+        text = "\n".join(lines)
+        fn = function_lines(lines, KERNEL)
         ops = [l.split()[0] for l in fn if l.startswith("\t") and not l.strip().startswith(";")]
         m = re.search(r"\.name:\s+%s\w*\n(?:.*\n){0,40}?\s+\.vgpr_count:\s+(\d+)" % KERNEL, text)
         assert m, "no metadata for the kernel"

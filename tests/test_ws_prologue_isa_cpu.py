@@ -1,4 +1,4 @@
-"""The prologue of the plain dense 32x32 forward / input-gradient kernels (pvae_gemm_ws.h, splitk_ws_body) in the emitted
+"""The prologue of the plain dense 32x32 forward / input-gradient kernels (pvae_gemm_ws.h, splitk_ws_superstep_body) in the emitted
 gfx950 assembly, beside test_loader_isa_cpu.py and test_ws_superstep_isa_cpu.py: k-tiles 0, 1 and 2 are fetched by all eight
 waves, so the path every wave runs issues six LDS-DMA instructions through the two lane offsets of tile 0 (the only ones a
 compute wave ever issues), the compute waves' loop holds none, the loaders add tiles 3 and 4 (four instructions each) outside
@@ -9,8 +9,8 @@ import re
 
 import pytest
 
-from test_loader_isa_cpu import DMA, KERNELS, asm, function_lines, loader_loop_blocks  # noqa: F401  (asm: the fixture)
-from test_ws_superstep_isa_cpu import PLAIN, inner_loops
+from isa import DMA, KERNELS, asm, function_lines, inner_loops, loader_loop_blocks  # noqa: F401  (asm: the fixture)
+from test_ws_superstep_isa_cpu import PLAIN
 
 
 @pytest.mark.parametrize("kernel", sorted(PLAIN))

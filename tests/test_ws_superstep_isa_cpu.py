@@ -1,36 +1,14 @@
-"""The compute waves' k-loop of the plain 32x32 forward / input-gradient kernels (pvae_gemm_ws.h, splitk_ws_body) in the
+"""The compute waves' k-loop of the plain 32x32 forward / input-gradient kernels (pvae_gemm_ws.h, splitk_ws_superstep_body) in the
 emitted gfx950 assembly, beside test_loader_isa_cpu.py: a compute wave opens every super-step with MFMAs -- at least two
 v_mfma stand between each s_barrier of its loop and the first ds_read behind it (the next tile's fragment reads go between
 the MFMAs, not in front of them), every barrier is preceded by the `s_waitcnt lgkmcnt(0)` that retires the fragment reads
 (round 5's race fix), and a super-step holds both tiles' reads (no branch inside it for hipcc to sink reads behind).
 pvae_net.hip is compiled with the flags of physicsvae_amd/build.py.  No GPU needed; skipped where there is no hipcc."""
-import re
-
 import pytest
 
-from test_loader_isa_cpu import KERNELS, asm, function_lines  # noqa: F401  (asm: the fixture)
+from isa import KERNELS, asm, function_lines, inner_loops  # noqa: F401  (asm: the fixture)
 
 PLAIN = {"ws<P_ROW, EpiBiasAct>": 4, "ws<P_COL, EpiMask>": 6}      # ds_read instructions per fragment set
-
-
-def inner_loops(fn):
-    """{header label: flat list of instruction lines} of every innermost loop of the function (hipcc's block comments, as in
-    test_loader_isa_cpu.loader_loop_blocks)."""
-    loops, cur = {}, None
-    for l in fn:
-        m = re.match(r"^(\.LBB\d+_\d+):(.*)$", l) or re.match(r"^; %bb\.\d+:(.*)$", l)
-        if m:
-            note = m.group(m.lastindex)
-            head = re.search(r"in Loop: Header=(BB\d+_\d+)", note)
-            if "This Inner Loop Header" in note:
-                cur = loops.setdefault(m.group(1)[2:], [])
-            elif head and head.group(1) in loops:
-                cur = loops[head.group(1)]
-            else:
-                cur = None
-        elif cur is not None and l.startswith("\t") and not l.strip().startswith(";"):
-            cur.append(l)
-    return loops
 
 
 @pytest.mark.parametrize("kernel", sorted(PLAIN))

@@ -4,18 +4,13 @@
 // period of back-to-back dependent launches (HIP events) and the per-workgroup timeline relative to
 // the first workgroup's entry.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/timeline_probe.hip -o tools/timeline_probe.out
-// Arms of an A/B are builds of this file with the library's compile-time switches (pvae_gemm_ws.h), run alternating in one
-// session.  Round 8's four (profiles/r08_timeline_probe_superstep_arms.txt), with docs/patches/r08_ws_loader_tile_m0.patch
-// applied for the loader arm:
-//   A  -DPVAE_WS_DMA_M0_EACH -DPVAE_WS_READS_AHEAD   the k-loop as it was
-//   B  -DPVAE_WS_READS_AHEAD                         loaders only: a tile's four DMAs behind one M0 write
-//   C  -DPVAE_WS_DMA_M0_EACH                         compute waves only: fragment reads between the MFMAs (= the tree)
-//   D                                                both
-// (the tree without the patch has no loader switch: A is -DPVAE_WS_READS_AHEAD alone, C no define)
-// Round 9's four (profiles/r09_timeline_probe_prologue.txt), built with the library's -mllvm -amdgpu-kernarg-preload-count=16:
-//   S  -DPVAE_WS_PROLOGUE_SERIAL      the prologue as it was: tile 0 by all eight waves, tiles 1-4 by the loaders
-//   M / L / N  -DPVAE_WS_PROLOGUE_AHEAD=0 / 1 / 2   tiles 0-2 by all eight waves, none / tile 3 / tiles 3 and 4 of the
-//      loaders' in front of barrier #0 (L = the tree)
+// Arms of an A/B are builds of this file with a patch of docs/patches/ applied to the library's header, run alternating in one
+// session.  Round 8's four (profiles/r08_timeline_probe_superstep_arms.txt): loaders with / without
+// r08_ws_loader_tile_m0.patch x compute waves with / without r08_ws_reads_ahead.patch (the tree: neither).  Round 9's four
+// (profiles/r09_timeline_probe_prologue.txt), built with the library's -mllvm -amdgpu-kernarg-preload-count=16:
+// r09_ws_prologue_serial.patch (S, the prologue as it was) and r09_ws_prologue_ahead.patch with 0 / 1 / 2 (M / L / N: none /
+// tile 3 / tiles 3 and 4 of the loaders' in front of barrier #0; L = the tree).  The patches apply to the header of the commit
+// before round 11, which still held these arms as compile-time switches (docs/patches/README.md).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
