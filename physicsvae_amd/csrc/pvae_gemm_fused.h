@@ -122,7 +122,7 @@ bwd_pair_kernel(PVAE_GA2_PARAMS, EpiD ed, EpiW ew, AdamPair ad) {
     if (b < nd) {
         if (gd.tile16) splitk_reg16_body<false, EpiD>(lds, b, gd, ed);
         else splitk_reg_body<false, EpiD, ABL>(lds, b, gd, ed);
-    } else if (b < nd + nw) wgrad_body<EpiW, ABL>(lds, b - nd, gw, ew);
+    } else if (b < nd + nw) wgrad_body<EpiW, (ABL & 32) ? 0 : ABL>(lds, b - nd, gw, ew);   // (bit 32: the input-gradient body alone)
     else if (b < nd + nw + bias_tiles(gw)) bias_grad_body(lds, b - nd - nw, gw, ew);
     else adam_pair_body(ad, b - nd - nw - bias_tiles(gw));
     PVAE_MARK(0, 3);

@@ -32,7 +32,34 @@ namespace pvae {
 // ---- forward / dgrad: C[32 q][32 p] per workgroup, BK = 64, the 4 waves split K -------------
 //   Q is always ROW (X or dZ, k-contiguous).  P_ROW: W[p][k] (forward);  !P_ROW: W[k][p] (dgrad).
 // ABL (tools/pair_lab.hip, tools/pair_probe.hip only; 0 in production): 1 = no tile staging in the loop, 2 = no LDS
-// fragment reads, 4 = no MFMA, 8 = no barrier, 16 = no gradient store (wgrad_reg_body only: epi.apply skipped).
+// fragment reads, 4 = no MFMA, 8 = no barrier (here: no ordering point in the k-loop), 16 = no gradient store
+// (wgrad_reg_body only: epi.apply skipped), 32 = the bits apply to the input-gradient body of a pair alone.
+// ---------------------------------------------------------------------------------------
+// Wave-private staging.  Wave w reads only its own k-quarter of a staged tile -- chunks 4w .. 4w+3 of every row of a ROW
+// operand, k-rows 16w .. 16w+15 of a COL operand -- so no byte of the image is read by a wave that did not write it if
+// every wave stages exactly the chunks it reads: LDS transposes lanes, it shares nothing.  One wave's LDS instructions
+// execute in order, so the k-loops of splitk_reg_body and splitk_reg16_body hold no workgroup barrier (splitk_reg64_body
+// keeps the thread-linear map and its barriers: see there); the first barrier of a body stands between the loop
+// and the split-K reduction buffer, which overlays the staging ring (a fast wave's partial tile would otherwise land on
+// chunks a slower wave has yet to read).  The 2-slot ring holds as before: a wave's write of slot (t+1)&1 follows its
+// own reads of that slot in its own LDS queue.
+//   ROW tile: lanes 4m .. 4m+3 stage chunks 4w .. 4w+3 (64 contiguous bytes) of row 16u + stage_row16(lane).  The eight
+//   lanes of a ds_write_b128 group hold two rows; a row's four chunks fill one 64-byte half of the 128-byte bank line,
+//   which half is bit 2 of (chunk ^ row), so the two rows of a group differ in bit 2 (rows r and r + 4): conflict-free
+//   (row = lane >> 2 would pair rows r and r + 1 on the same half: 2-way).
+//   COL tile: eight (PT = 32) or four (PT = 16) lanes stage one whole k-row; a write group covers 128 contiguous bytes.
+__device__ inline int stage_row16(int lane) {
+    const int m = lane >> 2;
+    return (m & 8) | ((m & 1) << 2) | ((m >> 1) & 3);
+}
+// What stands where the k-loop barrier stood: nothing for the hardware, an ordering point for the compiler -- a lane reads
+// what other lanes of its wave wrote, and hipcc may otherwise prove that a thread's own store and load do not alias and
+// hoist the read over the write.
+__device__ inline void wave_order_point() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // ---------------------------------------------------------------------------------------
 // Split-K partial tile of a wave -> its LDS reduction buffer red[32][RS], with 16-byte writes: the MFMA layout gives
 // each lane runs of consecutive p (P_ROW: acc[a][b] = 4 consecutive p of row 16a + li; output-contiguous operands:
@@ -74,23 +101,22 @@ __device__ inline void splitk_reg_body(float* lds, int bid, const GemmArgs& ga, 
     const int wave = tid >> 6;
     const int li = lane & 15, lh = lane >> 4;
 
+    // wave-private staging (see above): two chunks of each operand tile per thread
     const float* sq[2];
     const float* sp[2];
-    int slot_off[2];
+    int slot_off[2], slot_off_p[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int j = (wave + 4 * u) * 64 + lane;
-        slot_off[u] = j * 4;
-        {
-            const int row = j >> 4, c = (j & 15) ^ (row & 15);
-            sq[u] = Q + (size_t)(q0 + row) * ldq + c * 4;
-        }
+        const int row = 16 * u + stage_row16(lane), c = 4 * wave + (lane & 3);
+        slot_off[u] = (row * 16 + (c ^ (row & 15))) * 4;
+        sq[u] = Q + (size_t)(q0 + row) * ldq + c * 4;
         if (P_ROW) {
-            const int row = j >> 4, c = (j & 15) ^ (row & 15);
+            slot_off_p[u] = slot_off[u];
             sp[u] = P + (size_t)(p0 + row) * ldp + c * 4;
         } else {
-            const int r = j >> 3, k = r ^ ((r >> 2) & 1);
-            sp[u] = P + (size_t)k * ldp + p0 + (j & 7) * 4;
+            const int k = 16 * wave + 8 * u + (lane >> 3);
+            slot_off_p[u] = (k ^ ((k >> 2) & 1)) * 32 + (lane & 7) * 4;
+            sp[u] = P + (size_t)k * ldp + p0 + (lane & 7) * 4;
         }
     }
     const size_t kstep_p = P_ROW ? (size_t)BK : (size_t)BK * ldp;
@@ -104,9 +130,9 @@ __device__ inline void splitk_reg_body(float* lds, int bid, const GemmArgs& ga, 
     };
     auto lwrite = [&](float* slot, const v4f(&r)[4]) {
         *reinterpret_cast<v4f*>(slot + slot_off[0]) = r[0];
-        *reinterpret_cast<v4f*>(slot + kTile + slot_off[0]) = r[1];
+        *reinterpret_cast<v4f*>(slot + kTile + slot_off_p[0]) = r[1];
         *reinterpret_cast<v4f*>(slot + slot_off[1]) = r[2];
-        *reinterpret_cast<v4f*>(slot + kTile + slot_off[1]) = r[3];
+        *reinterpret_cast<v4f*>(slot + kTile + slot_off_p[1]) = r[3];
     };
 
     v4f acc[2][2];
@@ -129,7 +155,7 @@ __device__ inline void splitk_reg_body(float* lds, int bid, const GemmArgs& ga, 
     lwrite(lds, rg[0]);
     gload(D < nk ? D : nk - 1, rg[0]);
     const typename Epi::Pre epre = epi.preload(q0 + (tid >> 3), p0 + ((tid & 7) << 2));   // arrives under the loop
-    __syncthreads();
+    wave_order_point();
 
     v4f abl_q = v4f{1.f, 2.f, 3.f, 4.f} * (float)(lane + 1);
     asm volatile("" : "+v"(abl_q));
@@ -180,7 +206,7 @@ __device__ inline void splitk_reg_body(float* lds, int bid, const GemmArgs& ga, 
                 }
             }
         }
-        if (!(ABL & 8)) __syncthreads();
+        if (!(ABL & 8)) wave_order_point();
     };
     int t0 = 0;
     for (; t0 + D <= nk; t0 += D) {
@@ -191,6 +217,7 @@ __device__ inline void splitk_reg_body(float* lds, int bid, const GemmArgs& ga, 
     for (int d = 0; d < D; ++d)
         if (t0 + d < nk) tile_step(t0 + d, d, true);
 
+    __syncthreads();                       // the reduction buffer overlays the ring: every wave has read its last tile
     constexpr int RS = 36;
     store_partial_32x32<P_ROW>(lds + wave * (32 * RS), acc, li, lh);
     __syncthreads();
@@ -229,6 +256,9 @@ __device__ inline void splitk_reg64_body(float* lds, int bid, const GemmArgs& ga
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lh = lane >> 4;
 
+    // (slot j = 16-byte chunk j of the tile, staged by thread j & 255: whole 256-byte rows per 16 lanes, and a barrier behind
+    //  every k-tile.  The wave-private map of splitk_reg_body measured SLOWER here -- 1024 rows 585.9 -> 599.8 us, 512 rows
+    //  unchanged, profiles/r12_ab_reg_private.txt -- and was taken out again.)
     const float* sq[4];
     const float* sp[2];
 #pragma unroll
@@ -368,13 +398,14 @@ __device__ inline void splitk_reg16_body(float* lds, int bid, const GemmArgs& ga
     const int wave = tid >> 6;
     const int li = lane & 15, lh = lane >> 4;
 
-    // one 16-byte chunk of each operand tile per thread: slot j = tid, row j>>4, chunk (j&15)^row
-    const int srow = tid >> 4, schunk = (tid & 15) ^ srow;
+    // one 16-byte chunk of each operand tile per thread, wave-private (see splitk_reg_body): chunk 4 wave + (lane & 3) of
+    // row stage_row16(lane), kept at slot row * 16 + (chunk ^ row)
+    const int srow = stage_row16(lane), schunk = 4 * wave + (lane & 3);
     const float* sq = Q + (size_t)(q0 + srow) * ldq + schunk * 4;
     const float* sp = P_ROW ? P + (size_t)(p0 + srow) * ldp + schunk * 4
-                            : P + (size_t)(tid >> 2) * ldp + p0 + (tid & 3) * 4;      // k = tid/4, 4 chunks per row
+                            : P + (size_t)(tid >> 2) * ldp + p0 + (tid & 3) * 4;      // k = tid/4 = 16 wave + lane/4, 4 chunks per row
     const size_t kstep_p = P_ROW ? (size_t)BK : (size_t)BK * ldp;
-    const int slot_off = tid * 4;
+    const int slot_off = (srow * 16 + (schunk ^ srow)) * 4;
     // input-gradient form: P image rows k are kept at row k ^ ((k >> 2) & 1).  A fragment read touches rows
     // 4 lh + s2 (16 dwords each): rows 4 apart would otherwise fall on the same 16 banks for both halves of a
     // 32-lane read group (2-way conflict on every k-step: 15 % of the LDS cycles of the sampler-seed launch)
@@ -398,20 +429,22 @@ __device__ inline void splitk_reg16_body(float* lds, int bid, const GemmArgs& ga
     for (int d = 0; d < D; ++d) gload(d < nk ? d : nk - 1, rg[d]);     // (clamped, not guarded: exact vmcnt)
     lwrite(lds, rg[0]);
     gload(D < nk ? D : nk - 1, rg[0]);
-    __syncthreads();
+    wave_order_point();
 
     // (full groups of D tiles are branch-free so that the compiler counts the outstanding loads
     // exactly -- see wgrad_reg_body)
-    auto tile_step = [&](int t, int d, bool guarded) {
-        const float* st = lds + (t & 1) * kStage;
-        const v4f fq = *reinterpret_cast<const v4f*>(st + of);
-        v4f fp;
+    auto frag_read = [&](const float* st, v4f& fq, v4f& fp) {
+        fq = *reinterpret_cast<const v4f*>(st + of);
         if (P_ROW) {
             fp = *reinterpret_cast<const v4f*>(st + kTile + of);
         } else {
 #pragma unroll
             for (int s2 = 0; s2 < 4; ++s2) fp[s2] = st[kTile + ((16 * wave + 4 * lh + s2) ^ (lh & 1)) * 16 + li];
         }
+    };
+    auto tile_step = [&](int t, int d, bool guarded) {
+        v4f fq, fp;
+        frag_read(lds + (t & 1) * kStage, fq, fp);
 #pragma unroll
         for (int s2 = 0; s2 < 4; ++s2) {
             acc[s2 & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fp[s2], fq[s2], acc[s2 & 1], 0, 0, 0);
@@ -426,7 +459,7 @@ __device__ inline void splitk_reg16_body(float* lds, int bid, const GemmArgs& ga
                 }
             }
         }
-        __syncthreads();
+        wave_order_point();
     };
     int t0 = 0;
     for (; t0 + D <= nk; t0 += D) {
@@ -438,6 +471,7 @@ __device__ inline void splitk_reg16_body(float* lds, int bid, const GemmArgs& ga
         if (t0 + d < nk) tile_step(t0 + d, d, true);
 
     // split-K reduction (fixed order) + epilogue: 64 threads x float4 cover the 16x16 tile
+    __syncthreads();                       // the reduction buffer overlays the ring: every wave has read its last tile
     constexpr int RS = 20;
     float* red = lds + wave * (16 * RS);
     const v4f mine = acc[0] + acc[1];

@@ -132,6 +132,8 @@ int main() {
         T(1, 3, "dgrad || wgrad, no global loads / LDS writes");
         T(2, 3, "dgrad || wgrad, no LDS fragment reads");
         T(8, 3, "dgrad || wgrad, no barriers");
+        T(40, 3, "dgrad || wgrad, no barriers in the dgrad k-loop only");
+        T(8, 1, "dgrad only, no barriers");
         T(11, 3, "dgrad || wgrad, MFMA only");
         T(3, 3, "dgrad || wgrad, MFMA + barriers");
         T(4, 1, "dgrad only, no MFMA");
