@@ -948,6 +948,43 @@ int pvae_ppo_peer_open(pvae_ctx* ctx, int rank, int world, const void* blobs);
 int pvae_ppo_peer_close(pvae_ctx* ctx);
 int pvae_ppo_peer_status(pvae_ctx* ctx, int* rank, int* world, uint32_t* timeouts, void* stream);
 
+/* ---- Learner diagnostics from inside the fused PPO steps ----------------------------------------------------------------
+ * Both specs train with `kl_coeff: 0.0` and `vf_clip_param: 1000` (data/spec/loco/loco_imitation.yaml:15-16;
+ * data/spec/loco/loco_runtime_physics_vae.yaml:15-16): the kl stat and half of the vf stat say nothing in those runs, and
+ * the value outputs, the ratios and the gradient live only inside the call.  The reference leaves its learner stats to
+ * RLlib (vf_explained_var among them); there is no reference counterpart of what follows.  A diagnostics row is
+ * PVAE_PPO_DIAG floats per step (the specification: physicsvae_amd/ppo.py `learner_diag_torch`, `grad_gnorm_torch`), with
+ * y = value_targets, v = the step's value output and ratio as the loss forms it, over the minibatch's B rows:
+ *   [0] vf_explained_var  max(-1, 1 - Var(y - v) / Var(y)); exactly -1 for B == 1 or Var(y) == 0.  The variances come from
+ *                         float32 sums taken around the first row's y and y - v and are finished in double.
+ *   [1] clip_frac         share of rows with ratio < 1 - clip_param or ratio > 1 + clip_param
+ *   [2] vf_clip_frac      share of rows with |v - vf_preds| > vf_clip_param
+ *   [3] ratio_max_dev     max over the rows of |ratio - 1|, this ratio re-formed from a log-density summed in double (the
+ *                         loss's float32 logp, a sum of ~k terms, would show its ulp here at k >= 130)
+ *   [4] grad_gnorm        sqrt(sum g^2) over every element the step's Adam consumes: all trained segments and a trained
+ *                         log-std vector, after the workers' exchange and after grad_scale, before weight decay; frozen
+ *                         stacks (train_mask) do not enter.  Squares and sums in double; every workgroup of the Adam launch
+ *                         leaves ONE partial in a slot of its own (no atomics) and ONE SMALL LAUNCH PER STEP adds the slots in
+ *                         slot order -- the same inputs and grid give the same bits.
+ *   [5..7]                reserved, written as 0
+ *   *_diag_bytes    the scratch *_ppo_diag wants (gradient-norm slots + the loss head's diagnostics partial rows); `steps`
+ *                   >= 1 is accepted for a later per-call finish and does not enter today.
+ *   *_ppo_diag      binds `diag` (device, capacity_steps x PVAE_PPO_DIAG floats) and the scratch (device, 16-byte aligned);
+ *                   diag == NULL unbinds.  While bound: *_ppo_step writes row 0; *_ppo_grad entries 0..3 (and the reserved
+ *                   ones) of row 0; *_ppo_apply entry 4 of row 0; *_ppo_sgd rows 0 .. steps-1, and answers a negative code,
+ *                   launching nothing, when steps > capacity_steps.  A step has one launch more (*_ppo_grad: none; *_ppo_apply:
+ *                   one); every other output keeps its bits, nothing synchronises.  Not bound: every entry point is what
+ *                   it was, bit for bit and launch for launch.
+ *   pvae_ppo_loss_diag   pvae_ppo_loss with diag_out[PVAE_PPO_DIAG]: entries 0..3, and 0 in the rest. */
+#define PVAE_PPO_DIAG 8
+size_t pvae_fc_ppo_diag_bytes(const pvae_fc_config* cfg, int32_t steps);
+int pvae_fc_ppo_diag(pvae_fc* fc, float* diag, int32_t capacity_steps, void* scratch, size_t scratch_bytes);
+size_t pvae_ppo_diag_bytes(pvae_ctx* ctx, int32_t steps);
+int pvae_ppo_diag(pvae_ctx* ctx, float* diag, int32_t capacity_steps, void* scratch, size_t scratch_bytes);
+int pvae_ppo_loss_diag(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
+                       const pvae_fc_ppo_batch* batch, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* params,
+                       float* d_mean, float* d_log_std, float* d_value, float* stats_out, float* diag_out, void* stream);
+
 /* ---- Train-batch preparation for PhysicsVAE: evaluate, bootstrap, GAE, standardisation -------------------------------
  * "Train-batch preparation for the PPO learner" above, with PhysicsVAE as the policy: from a device-resident rollout to the
  * seven columns pvae_ppo_sgd reads, on one stream.  The rollout, the parameters and the outputs are the structs of that

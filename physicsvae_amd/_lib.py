@@ -40,6 +40,7 @@ ABI_VERSION = 12
 LOSS_MSE, LOSS_L1 = 0, 1
 EXCHANGE_ALLREDUCE, EXCHANGE_SHARDED, EXCHANGE_P2P, EXCHANGE_LOCAL, EXCHANGE_P2P_PUSH = 0, 1, 2, 3, 4
 P2P_BLOB_BYTES, P2P_MAX_RANKS = 512, 8
+PPO_DIAG = 8                     # PVAE_PPO_DIAG: floats of one learner-diagnostics row
 
 
 class Config(C.Structure):
@@ -222,6 +223,12 @@ _SIGS = {
     "pvae_fc_ppo_step": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int64, C.c_int32, C.POINTER(FcPpoParams), _P, _P]),
     "pvae_fc_ppo_sgd": (C.c_int, [_P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.c_int32, C.POINTER(FcPpoParams), _P, _P]),
     "pvae_fc_ppo_launches": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "pvae_fc_ppo_diag_bytes": (C.c_size_t, [C.POINTER(FcConfig), C.c_int32]),
+    "pvae_fc_ppo_diag": (C.c_int, [_P, _P, C.c_int32, _P, C.c_size_t]),
+    "pvae_ppo_diag_bytes": (C.c_size_t, [_P, C.c_int32]),
+    "pvae_ppo_diag": (C.c_int, [_P, _P, C.c_int32, _P, C.c_size_t]),
+    "pvae_ppo_loss_diag": (C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.POINTER(FcPpoParams),
+                                     _P, _P, _P, _P, _P, _P]),
     "pvae_fc_ppo_sizeof": (C.c_int, [C.c_int]),
     "pvae_fc_gae_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "pvae_gae": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(GaeParams), _P, _P, _P,

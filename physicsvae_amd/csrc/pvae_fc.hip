@@ -34,6 +34,7 @@ struct pvae_fc {
     int ppo_launches = 0;
     int eval_launches = 0, gae_launches = 0;      // pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate (pvae_fc_gae_launches)
     PpoPeers peers;                               // the learner's gradient exchange between workers (pvae_fc_ppo_peer_*)
+    PpoDiag diag;                                 // learner diagnostics (pvae_fc_ppo_diag)
 };
 
 namespace {
@@ -515,9 +516,9 @@ int check_ppo(pvae_fc* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* 
 }
 
 // The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
-// gradient arena (arguments checked by the caller); `launches` counts what went out
+// gradient arena (arguments checked by the caller); `launches` counts what went out; `dpart`: the head's diagnostics partial rows
 int ppo_grad_half(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-                  const pvae_fc_ppo_params* p, hipStream_t st, int* launches) {
+                  const pvae_fc_ppo_params* p, float* dpart, hipStream_t st, int* launches) {
     const FcLayout& L = c->L;
     const int mask = p->train_mask ? p->train_mask : (1 << L.S) - 1;
     Run r{c, st, rows, pad32(rows)};
@@ -546,6 +547,7 @@ int ppo_grad_half(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, 
         if (mask & 1) { h.d_mean = dz_ptr(c, 0, lp); h.ld_dm = panel_ld(c, 0, lp); h.width_dm = L.stack[0][lp].n_out_pad; }
         if (mask & 2) { h.d_value = dz_ptr(c, 1, lv); h.ld_dv = panel_ld(c, 1, lv); h.width_dv = L.stack[1][lv].n_out_pad; }
         h.part = c->scratch; h.part_stride = part_stride(b->k, colsum); h.colsum = colsum;
+        h.dpart = dpart;
         if ((rc = ppo_head_launch(h, st))) return rc;
         ++r.launches;
     }
@@ -583,21 +585,22 @@ int ppo_segments(pvae_fc* c, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
 }
 
 // one minibatch (arguments checked by the caller): the first half, then the Adam launch -- its exchanged form while a
-// gradient exchange between workers is open (pvae_fc_ppo_peer_open)
+// gradient exchange between workers is open (pvae_fc_ppo_peer_open); `diag_step`: the row of a bound diagnostics buffer
 int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-             const pvae_fc_ppo_params* p, int adam_t, float* stats_out, hipStream_t st) {
+             const pvae_fc_ppo_params* p, int adam_t, float* stats_out, int diag_step, hipStream_t st) {
     int launches = 0;
-    int rc = ppo_grad_half(c, b, index, first, rows, p, st, &launches);
+    const PpoDiagRow dg = diag_row(c->diag, diag_step);
+    int rc = ppo_grad_half(c, b, index, first, rows, p, dg.dpart, st, &launches);
     if (rc) return rc;
     PpoAdamSegs sg;
     if ((rc = ppo_segments(c, p, sg))) return rc;
     const bool colsum = p->log_std_kind == 1;
     rc = c->peers.open ? ppo_adam_exchange_launch(c->peers, g_ppo_peer_timeout_ticks, sg, p, adam_t, rows, b->k, c->scratch, colsum,
-                                                  c->log_std, c->log_std_m, c->log_std_v, stats_out, st)
+                                                  c->log_std, c->log_std_m, c->log_std_v, stats_out, dg, st, &launches)
                        : ppo_adam_launch(sg, p, adam_t, rows, b->k, c->scratch, colsum, c->log_std, c->log_std_m, c->log_std_v,
-                                         stats_out, st);
+                                         stats_out, dg, st, &launches);
     if (rc) return rc;
-    c->ppo_launches = launches + 1;
+    c->ppo_launches = launches;
     return 0;
 }
 
@@ -910,7 +913,7 @@ int pvae_fc_ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* inde
                      const pvae_fc_ppo_params* p, float* stats_out, void* stream) {
     int rc = check_ppo(c, b, p, first, rows, stats_out);
     if (rc) return rc;
-    return ppo_step(c, b, index, first, rows, p, p->adam_t, stats_out, (hipStream_t)stream);
+    return ppo_step(c, b, index, first, rows, p, p->adam_t, stats_out, 0, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_sgd(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* perm, int32_t minibatch, int32_t num_sgd_iter,
@@ -919,15 +922,31 @@ int pvae_fc_ppo_sgd(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* perm,
     int rc = check_ppo(c, b, p, 0, 1, stats_out);
     if (rc) return rc;
     if (minibatch > c->L.cfg.max_batch) return fail(-1, "minibatch %d > max_batch %d", minibatch, c->L.cfg.max_batch);
+    const long long steps = num_sgd_iter * ((b->n_rows + minibatch - 1) / minibatch);
+    if (c->diag.out && steps > c->diag.capacity)
+        return fail(-1, "%lld steps, the bound diagnostics buffer holds %d rows", steps, c->diag.capacity);
     int step = 0;
     for (int pass = 0; pass < num_sgd_iter; ++pass)
         for (long long first = 0; first < b->n_rows; first += minibatch, ++step) {
             const int rows = (int)(b->n_rows - first < minibatch ? b->n_rows - first : minibatch);
             rc = ppo_step(c, b, perm ? perm + (size_t)pass * b->n_rows : nullptr, first, rows, p, p->adam_t + step,
-                          stats_out + 5 * (size_t)step, (hipStream_t)stream);
+                          stats_out + 5 * (size_t)step, step, (hipStream_t)stream);
             if (rc) return rc;
         }
     return 0;
+}
+
+size_t pvae_fc_ppo_diag_bytes(const pvae_fc_config* cfg, int32_t steps) {
+    if (!cfg) return 0;
+    if (steps < 1) { fail(-1, "steps must be >= 1, got %d", steps); return 0; }
+    const FcLayout L = make_fc_layout(*cfg);
+    if (!L.ok) { fail(-1, "bad stack-set config: %s", L.why); return 0; }
+    return ppo_diag_bytes(L.cfg.max_batch);              // (the norm is finished per step: no per-step slot rows)
+}
+
+int pvae_fc_ppo_diag(pvae_fc* c, float* diag, int32_t capacity_steps, void* scratch, size_t scratch_bytes) {
+    if (!c) return fail(-1, "null stack set");
+    return ppo_diag_bind(c->diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
 }
 
 int pvae_fc_ppo_grad(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
@@ -937,8 +956,9 @@ int pvae_fc_ppo_grad(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* inde
     const bool colsum = p->log_std_kind == 1;
     if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
     int launches = 0;
-    if ((rc = ppo_grad_half(c, b, index, first, rows, p, (hipStream_t)stream, &launches))) return rc;
-    if ((rc = ppo_grad_finish_launch(rows, b->k, c->scratch, colsum, ls_grad, stats_out, (hipStream_t)stream, &launches))) return rc;
+    const PpoDiagRow dg = diag_row(c->diag, 0);
+    if ((rc = ppo_grad_half(c, b, index, first, rows, p, dg.dpart, (hipStream_t)stream, &launches))) return rc;
+    if ((rc = ppo_grad_finish_launch(rows, b->k, c->scratch, colsum, ls_grad, stats_out, dg, (hipStream_t)stream, &launches))) return rc;
     c->ppo_launches = launches;
     return 0;
 }
@@ -959,10 +979,11 @@ int pvae_fc_ppo_apply(pvae_fc* c, const pvae_fc_ppo_params* p, float grad_scale,
     PpoAdamSegs sg;
     int rc = ppo_segments(c, p, sg);
     if (rc) return rc;
+    int launches = 0;
     if ((rc = ppo_apply_launch(sg, p, p->adam_t, L.cfg.n_out[0], grad_scale, ls_grad, colsum, c->log_std, c->log_std_m, c->log_std_v,
-                               (hipStream_t)stream)))
+                               diag_row(c->diag, 0), (hipStream_t)stream, &launches)))
         return rc;
-    c->ppo_launches = 1;
+    c->ppo_launches = launches;
     return 0;
 }
 

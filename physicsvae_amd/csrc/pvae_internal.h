@@ -180,6 +180,23 @@ struct PpoPeers {
     float* self_buf = nullptr;                               // the attach-time check's saved gradient line
 };
 
+// Learner diagnostics (include/pvae.h "Learner diagnostics"): what *_ppo_diag bound -- `out` [capacity][PVAE_PPO_DIAG] rows
+// of the caller's, and the scratch cut in two: `gslot`, one double per workgroup of an Adam launch (the sum of squares
+// of the gradient values it loaded; the launch's extra workgroup: the log-std vector's), and `dpart`, the loss head's
+// diagnostics partial rows.  `out` null: nothing bound, every launch below runs its instantiation without diagnostics.
+// A PpoDiagRow names the row one step writes.  The norm is finished by ONE SMALL LAUNCH PER STEP (ppo_gnorm_launch): the
+// Adam launch's extra workgroup runs beside the others and cannot wait for their slots.
+constexpr int kDiagPart = 8;                    // floats of a diagnostics partial row: 2 counts, 1 max, 4 pivoted sums, 1 spare
+constexpr int kDiagSlots = 2056;                // >= the largest Adam grid (2048 + 1), a multiple of 8
+struct PpoDiag {
+    float* out = nullptr; int capacity = 0;
+    double* gslot = nullptr; float* dpart = nullptr;
+};
+struct PpoDiagRow { float* row; double* gslot; float* dpart; };
+inline PpoDiagRow diag_row(const PpoDiag& d, long long step) {
+    return d.out ? PpoDiagRow{d.out + step * PVAE_PPO_DIAG, d.gslot, d.dpart} : PpoDiagRow{nullptr, nullptr, nullptr};
+}
+
 struct pvae_ctx {
     void* comm = nullptr;        // ncclComm_t of the data-parallel group (pvae_comm_init)
     int comm_rank = 0, comm_world = 1;
@@ -276,6 +293,7 @@ struct pvae_ctx {
         int launches = 0;
         int eval_launches = 0, gae_launches = 0;         // pvae_ppo_prepare / pvae_ppo_evaluate (pvae_ppo_gae_launches)
         PpoPeers peers;                                  // the learner's gradient exchange between workers (pvae_ppo_peer_*)
+        PpoDiag diag;                                    // learner diagnostics (pvae_ppo_diag)
     } ppo;
 };
 static inline void params_touched(pvae_ctx* c, hipStream_t st, bool queued = true) {
@@ -603,6 +621,7 @@ struct PpoHead {
     float* d_mean; float* d_ls; float* d_value;                  // [rows_pad][width_*] blocks, row stride ld_d* (null: none)
     int ld_dm, ld_dls, ld_dv, width_dm, width_dls, width_dv;
     float* part; int part_stride; int colsum;                    // partial rows [waves][part_stride]; colsum: + the log-std columns
+    float* dpart;                                                // diagnostics partial rows [waves][kDiagPart] (null: none; PpoDiag)
 };
 int head_waves(int rows_pad);                                    // partial rows a head launch over rows_pad rows leaves
 int part_stride(int k, bool colsum);
@@ -619,16 +638,23 @@ struct PpoAdamSegs {
     float* p[kAdamSegs]; const float* g[kAdamSegs]; float* m[kAdamSegs]; float* v[kAdamSegs];
     long long n4[kAdamSegs];                    // float4 elements of segment i
 };
+// learner diagnostics (PpoDiag, above pvae_ctx)
+size_t ppo_diag_bytes(int max_batch);
+int ppo_diag_bind(PpoDiag& d, float* diag, int capacity, void* scratch, size_t bytes, int max_batch);
 int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st);
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, hipStream_t st,
+                    int* launches);
 // The step in two halves (include/pvae.h "Gradient exchange between workers").  The first half ends with
 // ppo_grad_finish_launch in place of the Adam launch: stats_out[5] (ppo_finish_kernel) and, colsum, ls_grad[k] = the column
 // sums of the partial rows, the value the Adam launch's last workgroup forms; `launches` counts what went out.  The second
 // half is ppo_apply_launch: Adam over the segments on grad_scale * gradient, the log-std vector from grad_scale * ls_grad.
-int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out, hipStream_t st,
-                           int* launches);
+// With a diagnostics row: the finish launch also writes its entries 0..3 (and zeros the reserved ones), the apply launch
+// leaves the squares of what Adam consumed in the slots and one more launch writes entry 4.
+int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out,
+                           const PpoDiagRow& dg, hipStream_t st, int* launches);
 int ppo_apply_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int k, float grad_scale,
-                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, hipStream_t st);
+                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, const PpoDiagRow& dg, hipStream_t st,
+                     int* launches);
 
 // ---- the PPO learners' peer-mapped gradient exchange (set-up: pvae_exchange.hip; the launch: pvae_ppo_core.hip) ----
 // Flag words of the peer-mapped exchanges (unsigned, one block per rank in uncached device memory): epochs and tokens only
@@ -653,7 +679,7 @@ inline long long g_ppo_peer_timeout_ticks = 20ll * 100000000ll;     // stack set
 // The exchanged form of ppo_adam_launch: one launch, the N ranks' gradients summed in rank order and scaled by float(1 / N)
 int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
                              int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
-                             float* stats_out, hipStream_t st);
+                             float* stats_out, const PpoDiagRow& dg, hipStream_t st, int* launches);
 int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
                       const float* log_std_m, const float* log_std_v);      // the alignment and pairing rules of *_ppo_bind
 // Rows [r0, r1) of up to kZeroPanels panels (columns [0, width) of row stride ld) set to zero: a <= 4-row forward runs on

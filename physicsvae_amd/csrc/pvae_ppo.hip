@@ -128,8 +128,8 @@ int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params*
 // The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
 // gradient arenas (arguments checked by the caller); `launches_out` counts what went out
 int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t seed, uint64_t offset, hipStream_t st,
-                  int* launches_out) {
+                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t seed, uint64_t offset, float* dpart,
+                  hipStream_t st, int* launches_out) {
     const pvae_ctx::Ppo& q = c->ppo;
     const pvae_config& cfg = c->L.cfg;
     const int Db = cfg.dim_body, Z = cfg.latent;
@@ -172,6 +172,7 @@ int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* 
         if (md_back) { h.d_mean = w + wmd.dz.back(); h.ld_dm = md_last.n_out_pad; h.width_dm = md_last.n_out_pad; }
         if (train_v) { h.d_value = vs.d_value; h.ld_dv = vs.ld_dv; h.width_dv = vs.width_dv; }
         h.part = q.scratch; h.part_stride = part_stride(b->k, colsum != 0); h.colsum = colsum;
+        h.dpart = dpart;                                     // (the head's diagnostics partial rows, or null)
         if ((rc = ppo_head_launch(h, st))) return rc;
         ++launches;
     }
@@ -210,20 +211,21 @@ void ppo_segments(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_params*
 // gradient exchange between workers is open (pvae_ppo_peer_open)
 int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
              const pvae_fc_ppo_params* p, int adam_t, const float* eps, int noise, uint64_t seed, uint64_t offset,
-             float* stats_out, hipStream_t st) {
+             float* stats_out, int diag_step, hipStream_t st) {
     pvae_ctx::Ppo& q = c->ppo;
     int launches = 0;
-    int rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, seed, offset, st, &launches);
+    const PpoDiagRow dg = diag_row(q.diag, diag_step);       // the row of a bound diagnostics buffer
+    int rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, seed, offset, dg.dpart, st, &launches);
     if (rc) return rc;
     PpoAdamSegs sg;
     ppo_segments(c, vs, p, sg);
     const int colsum = p->log_std_kind == 1;
     rc = q.peers.open ? ppo_adam_exchange_launch(q.peers, c->p2p.timeout_ticks, sg, p, adam_t, rows, b->k, q.scratch, colsum,
-                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, st)
+                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, dg, st, &launches)
                       : ppo_adam_launch(sg, p, adam_t, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m, q.log_std_v,
-                                        stats_out, st);
+                                        stats_out, dg, st, &launches);
     if (rc) return rc;
-    q.launches = launches + 1;
+    q.launches = launches;
     return 0;
 }
 
@@ -345,7 +347,7 @@ int pvae_ppo_step(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index,
     FcValueStack vs;
     int rc = check_ppo(c, b, p, first, rows, stats_out, &vs);
     if (rc) return rc;
-    if ((rc = ppo_step(c, vs, b, index, first, rows, p, p->adam_t, eps, noise, rng_seed, rng_offset, stats_out, (hipStream_t)stream)))
+    if ((rc = ppo_step(c, vs, b, index, first, rows, p, p->adam_t, eps, noise, rng_seed, rng_offset, stats_out, 0, (hipStream_t)stream)))
         return rc;
     params_touched(c, (hipStream_t)stream);
     return 0;
@@ -360,6 +362,9 @@ int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, i
     if (rc) return rc;
     if (minibatch > c->L.cfg.max_batch || minibatch > vs.max_batch)
         return fail(-1, "minibatch %d > max_batch %d", minibatch, std::min(c->L.cfg.max_batch, vs.max_batch));
+    const long long steps = num_sgd_iter * ((b->n_rows + minibatch - 1) / minibatch);
+    if (c->ppo.diag.out && steps > c->ppo.diag.capacity)
+        return fail(-1, "%lld steps, the bound diagnostics buffer holds %d rows", steps, c->ppo.diag.capacity);
     const size_t eps_step = (size_t)minibatch * c->L.cfg.latent;
     int step = 0;
     for (int pass = 0; pass < num_sgd_iter; ++pass)
@@ -367,11 +372,22 @@ int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, i
             const int rows = (int)(b->n_rows - first < minibatch ? b->n_rows - first : minibatch);
             rc = ppo_step(c, vs, b, perm ? perm + (size_t)pass * b->n_rows : nullptr, first, rows, p, p->adam_t + step,
                           eps ? eps + eps_step * step : nullptr, noise, rng_seed, rng_offset + (uint64_t)step,
-                          stats_out + 5 * (size_t)step, (hipStream_t)stream);
+                          stats_out + 5 * (size_t)step, step, (hipStream_t)stream);
             if (rc) return rc;
         }
     params_touched(c, (hipStream_t)stream);
     return 0;
+}
+
+size_t pvae_ppo_diag_bytes(pvae_ctx* c, int32_t steps) {
+    if (!c) { fail(-1, "null ctx"); return 0; }
+    if (steps < 1) { fail(-1, "steps must be >= 1, got %d", steps); return 0; }
+    return ppo_diag_bytes(c->L.cfg.max_batch);           // (the norm is finished per step: no per-step slot rows)
+}
+
+int pvae_ppo_diag(pvae_ctx* c, float* diag, int32_t capacity_steps, void* scratch, size_t scratch_bytes) {
+    if (!c) return fail(-1, "null ctx");
+    return ppo_diag_bind(c->ppo.diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
 }
 
 int pvae_ppo_grad(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
@@ -383,9 +399,10 @@ int pvae_ppo_grad(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index,
     const int colsum = p->log_std_kind == 1;
     if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
     int launches = 0;
-    if ((rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, rng_seed, rng_offset, (hipStream_t)stream, &launches)))
+    const PpoDiagRow dg = diag_row(c->ppo.diag, 0);
+    if ((rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, rng_seed, rng_offset, dg.dpart, (hipStream_t)stream, &launches)))
         return rc;
-    if ((rc = ppo_grad_finish_launch(rows, b->k, c->ppo.scratch, colsum, ls_grad, stats_out, (hipStream_t)stream, &launches)))
+    if ((rc = ppo_grad_finish_launch(rows, b->k, c->ppo.scratch, colsum, ls_grad, stats_out, dg, (hipStream_t)stream, &launches)))
         return rc;
     c->ppo.launches = launches;
     return 0;
@@ -407,10 +424,11 @@ int pvae_ppo_apply(pvae_ctx* c, const pvae_fc_ppo_params* p, float grad_scale, c
     if ((rc = fc_value_stack(q.value, &vs))) return rc;
     PpoAdamSegs sg;
     ppo_segments(c, vs, p, sg);
+    int launches = 0;
     if ((rc = ppo_apply_launch(sg, p, p->adam_t, c->L.cfg.dim_action, grad_scale, ls_grad, colsum, q.log_std, q.log_std_m,
-                               q.log_std_v, (hipStream_t)stream)))
+                               q.log_std_v, diag_row(q.diag, 0), (hipStream_t)stream, &launches)))
         return rc;
-    c->ppo.launches = 1;
+    c->ppo.launches = launches;
     params_touched(c, (hipStream_t)stream);
     return 0;
 }

@@ -1,5 +1,6 @@
 // pvae_ppo_core.hip -- what the on-device PPO learner holds that no model owns (include/pvae.h "PPO learner step",
-// "Train-batch preparation", "Action sampling"): the loss head and its finishing reduction, the Adam + stats launch, the
+// "Train-batch preparation", "Action sampling", "Learner diagnostics"): the loss head and its finishing reduction (with the
+// per-step diagnostics and the gradient norm's partial sums as template instantiations), the Adam + stats launch, the
 // evaluate and the sampling epilogue, the pad copy, the zero-rows launch, GAE and standardisation, their argument checks,
 // and the entry points that need no model at all (pvae_ppo_loss, pvae_gae).  The stack set's learner (pvae_fc.hip) and
 // PhysicsVAE's (pvae_ppo.hip) fill the argument structs of pvae_internal.h from their own panels and call the launch
@@ -25,6 +26,19 @@ __device__ inline float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ inline double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// DIAG (include/pvae.h "Learner diagnostics"): the wave also leaves, in diagnostics partial row w (kDiagPart floats),
+// over its rows: [0] rows with the ratio outside [1 - clip, 1 + clip] (the negation of the comparison below), [1] rows with
+// |value - vf_preds| > vf_clip, [2] max |ratio - 1| (this one ratio re-formed in double, see below), and the four sums of the two variances, [3] sum (y - y0), [4] sum
+// (y - y0)^2, [5] sum (e - e0), [6] sum (e - e0)^2 with y = value_targets, e = y - value -- taken around the FIRST
+// minibatch row's y0 and e0, which every wave reads for itself: raw float32 sums of y and y^2 lose the variance of targets
+// far from zero (1000 +- 2: off by up to 5e-2; the pivoted sums are within 1e-7 of float64).  The stats partial row
+// keeps its layout and its bits; without DIAG the kernel is the one it was.
+template <bool DIAG>
 __global__ void __launch_bounds__(256)
 ppo_head_kernel(PpoHead h) {
     const int lane = threadIdx.x & 63;
@@ -34,6 +48,12 @@ ppo_head_kernel(PpoHead h) {
     if (h.colsum)
         for (int j = lane; j < k; j += 64) part[kPartStats + j] = 0.f;
     float st[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float dg[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float y0 = 0.f, e0 = 0.f;
+    if constexpr (DIAG) {
+        y0 = h.vtarg[batch_row(h.index, h.row0, h.n_rows, 0)];
+        e0 = y0 - h.value[0];
+    }
     for (int r = wave; r < h.rows_pad; r += waves) {
         const bool live = r < h.rows;
         float dlogp = 0.f, dval = 0.f;
@@ -43,11 +63,17 @@ ppo_head_kernel(PpoHead h) {
             mu = h.mean + r * h.ld_mean; ls = h.ls + r * h.ld_ls;
             act = h.actions + br * k; od = h.old_dist + br * 2 * k;
             float zz = 0.f, lss = 0.f, kl = 0.f;
+            [[maybe_unused]] double zz_d = 0.0, lss_d = 0.0;
             for (int j = lane; j < k; j += 64) {
                 const float l = h.ls_base + ls[j], inv_sig = expf(-l);
                 const float z = (act[j] - mu[j]) * inv_sig, d = od[j] - mu[j], lo = od[k + j];
                 zz = fmaf(z, z, zz);
                 lss += l;
+                if constexpr (DIAG) {
+                    const double zd = ((double)act[j] - (double)mu[j]) * exp(-(double)l);
+                    zz_d = fma(zd, zd, zz_d);
+                    lss_d += (double)l;
+                }
                 kl += l - lo + (expf(2.f * lo) + d * d) * (0.5f * inv_sig * inv_sig) - 0.5f;
             }
             zz = wave_sum(zz); lss = wave_sum(lss); kl = wave_sum(kl);
@@ -65,6 +91,18 @@ ppo_head_kernel(PpoHead h) {
             if (vf1 >= vf2 || fabsf(dv) <= h.vf_clip) dval = h.vf_coeff * h.inv_rows * 2.f * e1;
             st[0] += -surr + h.kl_coeff * kl + h.vf_coeff * vf - h.ent_coeff * ent;
             st[1] += -surr; st[2] += vf; st[3] += kl; st[4] += ent;
+            if constexpr (DIAG) {
+                if (ratio < lo_r || ratio > hi_r) dg[0] += 1.f;
+                if (fabsf(dv) > h.vf_clip) dg[1] += 1.f;
+                // ratio_max_dev from the log-density summed in double: the loss's own float32 logp is a sum of ~k terms
+                // of magnitude ~k, whose ulp at k >= 130 (1.5e-5) would show in exp(logp - old_logp) - 1
+                zz_d = wave_sum_d(zz_d); lss_d = wave_sum_d(lss_d);
+                const double logp_d = -0.5 * zz_d - lss_d - 0.5 * k * 1.8378770664093453;
+                dg[2] = fmaxf(dg[2], (float)fabs(exp(logp_d - (double)h.old_logp[br]) - 1.0));
+                const float dy = vt - y0, de = (vt - val) - e0;
+                dg[3] += dy; dg[4] = fmaf(dy, dy, dg[4]);
+                dg[5] += de; dg[6] = fmaf(de, de, dg[6]);
+            }
         }
         // the gradients, over the whole padded width of the row: zeros in pad rows and pad columns
         const int wmax = max(h.d_mean ? h.width_dm : k, h.d_ls ? h.width_dls : k);
@@ -87,9 +125,72 @@ ppo_head_kernel(PpoHead h) {
     if (lane == 0) {
 #pragma unroll
         for (int t = 0; t < 5; ++t) part[t] = st[t];
+        if constexpr (DIAG) {
+            float* __restrict__ dp = h.dpart + (size_t)wave * kDiagPart;
+#pragma unroll
+            for (int t = 0; t < 7; ++t) dp[t] = dg[t];
+            dp[7] = 0.f;
+        }
     }
 }
 
+// Diagnostics entries 0..3 from the diagnostics partial rows, by ONE wave: lane l adds rows l, l + 64, ... in double,
+// then a butterfly -- an order that depends on nothing but nparts.  The variances are finished in double from the pivoted
+// sums; vf_explained_var = max(-1, 1 - Var(y - v) / Var(y)), exactly -1 for one row or Var(y) == 0.  The reserved
+// entries 5..7 get 0, and `zero4` entry 4 too (the stand-alone head: no gradient norm).
+__device__ inline void ppo_diag_finish(const float* __restrict__ dpart, int nparts, int rows, float* __restrict__ out, int zero4,
+                                       int lane) {
+    double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = lane; i < nparts; i += 64) {
+        const float* __restrict__ dp = dpart + (size_t)i * kDiagPart;
+        s[0] += (double)dp[0]; s[1] += (double)dp[1];
+        s[2] = fmax(s[2], (double)dp[2]);
+        s[3] += (double)dp[3]; s[4] += (double)dp[4]; s[5] += (double)dp[5]; s[6] += (double)dp[6];
+    }
+#pragma unroll
+    for (int t = 0; t < 7; ++t) {
+        if (t == 2) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s[2] = fmax(s[2], __shfl_xor(s[2], o, 64));
+        } else {
+            s[t] = wave_sum_d(s[t]);
+        }
+    }
+    if (lane != 0) return;
+    const double n = (double)rows, my = s[3] / n, me = s[5] / n;
+    const double var_y = s[4] / n - my * my, var_e = s[6] / n - me * me;
+    double ev = -1.0;
+    if (rows > 1 && var_y > 0.0) ev = fmax(-1.0, 1.0 - fmax(var_e, 0.0) / var_y);
+    out[0] = (float)ev;
+    out[1] = (float)(s[0] / n);
+    out[2] = (float)(s[1] / n);
+    out[3] = (float)s[2];
+    if (zero4) out[4] = 0.f;
+    out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
+}
+
+// The gradient norm's two ends.  Every workgroup of an Adam launch ends with block_sum_sq: the squares of the gradient
+// values its threads loaded, added in double -- a butterfly per wave, then the four waves through LDS in wave order --
+// into the workgroup's OWN slot: no atomics, and the grid-stride map fixes which elements a workgroup holds, so the
+// sum depends on (segment sizes, grid) and never on timing.  ppo_gnorm_kernel, one wave of a later launch, adds the slots
+// in slot order (lane l: slots l, l + 64, ..., then a butterfly) and writes sqrt as float32 to diagnostics entry 4.
+__device__ inline double sq4(const v4f& g) {
+    return ((double)g[0] * (double)g[0] + (double)g[1] * (double)g[1]) + ((double)g[2] * (double)g[2] + (double)g[3] * (double)g[3]);
+}
+__device__ inline void block_sum_sq(double sq, double* __restrict__ slot) {
+    __shared__ double red[4];
+    sq = wave_sum_d(sq);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) *slot = ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ void __launch_bounds__(64)
+ppo_gnorm_kernel(const double* __restrict__ gslot, int nslots, float* __restrict__ out) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += 64) s += gslot[i];
+    s = wave_sum_d(s);
+    if (threadIdx.x == 0) *out = (float)sqrt(s);
+}
 // The partial rows summed in a fixed order by ONE wave: stats_out[5] (means over the rows)
 __device__ inline void ppo_finish(const float* __restrict__ part, int nparts, int stride, float inv_rows, float* __restrict__ out,
                                   int lane) {
@@ -104,6 +205,14 @@ __device__ inline void ppo_finish(const float* __restrict__ part, int nparts, in
 __global__ void __launch_bounds__(64)
 ppo_finish_kernel(const float* part, int nparts, int stride, float inv_rows, float* out) {
     ppo_finish(part, nparts, stride, inv_rows, out, threadIdx.x);
+}
+// the finishing launch of the stand-alone head and of the step's first half with diagnostics: wave 0 the stats, wave 1 the
+// diagnostics entries
+__global__ void __launch_bounds__(128)
+ppo_finish_diag_kernel(const float* part, int nparts, int stride, float inv_rows, float* out, const float* dpart, int rows,
+                       float* diag, int zero4) {
+    if (threadIdx.x < 64) ppo_finish(part, nparts, stride, inv_rows, out, threadIdx.x);
+    else ppo_diag_finish(dpart, nparts, rows, diag, zero4, threadIdx.x - 64);
 }
 
 // column j of a state-independent log-std's gradient: the partial rows added in partial-row order
@@ -124,18 +233,29 @@ struct PpoAdam {
     AdamScalars s;
     const float* part; int nparts, part_stride; float inv_rows; float* stats_out;
     int k; float* ls; float* ls_m; float* ls_v;
+    // DIAG instantiations only: the head's diagnostics partial rows and the row they finish into (entries 0..3), the
+    // minibatch's rows, and the gradient-norm slots, one per workgroup of the launch
+    const float* dpart; int rows; float* diag; double* gslot;
 };
+// DIAG: + the diagnostics entries 0..3 by the extra workgroup's second wave, and every workgroup's sum of squares of the
+// gradient values it consumed into its slot (block_sum_sq; the extra workgroup: the log-std vector's gradient)
+template <bool DIAG>
 __global__ void __launch_bounds__(256)
 ppo_adam_kernel(PpoAdam a) {
+    [[maybe_unused]] double sq = 0.0;
     if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
+        if constexpr (DIAG)
+            if (threadIdx.x >= 64 && threadIdx.x < 128) ppo_diag_finish(a.dpart, a.nparts, a.rows, a.diag, 0, threadIdx.x - 64);
         if (a.ls)
             for (int j = threadIdx.x; j < a.k; j += 256) {
                 const float g = ppo_ls_colsum(a.part, a.nparts, a.part_stride, j);
+                if constexpr (DIAG) sq += (double)g * (double)g;
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
                 adam_update(g, p, m, v, a.s);
                 a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
             }
+        if constexpr (DIAG) block_sum_sq(sq, a.gslot + blockIdx.x);
         return;
     }
     const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
@@ -145,6 +265,7 @@ ppo_adam_kernel(PpoAdam a) {
         const long long q = i - (k ? a.end4[k - 1] : 0);
         v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
         const v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
+        if constexpr (DIAG) sq += sq4(gg);
         v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
         v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
         adam_update4(gg, pp, mm, vv, a.s);
@@ -152,6 +273,7 @@ ppo_adam_kernel(PpoAdam a) {
         reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
         reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
     }
+    if constexpr (DIAG) block_sum_sq(sq, a.gslot + blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -178,15 +300,21 @@ __device__ inline v4f scale4(const v4f& g, float s) {       // (pinned: no contr
 }
 
 // second half: ppo_adam_kernel on scale * gradient, the log-std vector from scale * ls_grad; no stats (the first half wrote them)
+// (DIAG: the slots get the squares of scale * gradient, what Adam consumes)
+template <bool DIAG>
 __global__ void __launch_bounds__(256)
 ppo_apply_kernel(PpoAdam a, float scale, const float* __restrict__ ls_grad) {
+    [[maybe_unused]] double sq = 0.0;
     if (blockIdx.x == gridDim.x - 1) {
         if (a.ls)
             for (int j = threadIdx.x; j < a.k; j += 256) {
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
-                adam_update(__fmul_rn(ls_grad[j], scale), p, m, v, a.s);
+                const float g = __fmul_rn(ls_grad[j], scale);
+                if constexpr (DIAG) sq += (double)g * (double)g;
+                adam_update(g, p, m, v, a.s);
                 a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
             }
+        if constexpr (DIAG) block_sum_sq(sq, a.gslot + blockIdx.x);
         return;
     }
     const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
@@ -194,8 +322,11 @@ ppo_apply_kernel(PpoAdam a, float scale, const float* __restrict__ ls_grad) {
         int k = 0;
         while (i >= a.end4[k]) ++k;
         const long long q = i - (k ? a.end4[k - 1] : 0);
-        ppo_adam_elem(a, k, q, scale4(reinterpret_cast<const v4f*>(a.seg.g[k])[q], scale));
+        const v4f gg = scale4(reinterpret_cast<const v4f*>(a.seg.g[k])[q], scale);
+        if constexpr (DIAG) sq += sq4(gg);
+        ppo_adam_elem(a, k, q, gg);
     }
+    if constexpr (DIAG) block_sum_sq(sq, a.gslot + blockIdx.x);
 }
 
 // The exchanged form of ppo_adam_kernel: N workers' gradients, each in its own process' buffers and mapped into this one
@@ -220,9 +351,11 @@ struct PpoAdamPeers {
     int me; unsigned epoch; long long timeout_ticks;
     float inv_n;
 };
-template <int N>
+// DIAG: as ppo_adam_kernel's -- the slots get the squares of the AVERAGED gradient, so every rank reports the same norm
+template <int N, bool DIAG>
 __global__ void __launch_bounds__(256)
 ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
+    [[maybe_unused]] double sq = 0.0;
     unsigned* mine = x.f[x.me];
     const int tid = threadIdx.x, me = x.me;
     if (blockIdx.x == 0) {
@@ -249,6 +382,8 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
     const bool go = !abort_;
     if (blockIdx.x == gridDim.x - 1) {
         if (tid < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, tid);
+        if constexpr (DIAG)
+            if (tid >= 64 && tid < 128) ppo_diag_finish(a.dpart, a.nparts, a.rows, a.diag, 0, tid - 64);
         if (a.ls && go)
             for (int j = tid; j < a.k; j += 256) {
                 float g = 0.f;                 // (the own column is summed here again: no workgroup waits for another of its launch)
@@ -260,7 +395,9 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
                     g = q == 0 ? gq : g + gq;                         // rank order
                 }
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
-                adam_update(__fmul_rn(g, x.inv_n), p, m, v, a.s);
+                const float gs = __fmul_rn(g, x.inv_n);
+                if constexpr (DIAG) sq += (double)gs * (double)gs;
+                adam_update(gs, p, m, v, a.s);
                 a.ls[j] = p; a.ls_m[j] = m; a.ls_v[j] = v;
             }
     } else if (go) {
@@ -279,10 +416,13 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
                 v4f sum = g[0];
 #pragma unroll
                 for (int q = 1; q < N; ++q) sum += g[q];              // rank order
-                ppo_adam_elem(a, k, i, scale4(sum, x.inv_n));
+                const v4f gs = scale4(sum, x.inv_n);
+                if constexpr (DIAG) sq += sq4(gs);
+                ppo_adam_elem(a, k, i, gs);
             }
         }
     }
+    if constexpr (DIAG) block_sum_sq(sq, a.gslot + blockIdx.x);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __shared__ unsigned last;
@@ -452,11 +592,6 @@ struct GaeArgs {
     float* adv; float* vtarg;
     double* part;
 };
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ void __launch_bounds__(256)
 gae_kernel(GaeArgs g) {
     __shared__ double red[4][2];
@@ -547,7 +682,8 @@ int loss_scratch(hipStream_t st, float** out) {
     for (const LossScratch& e : g_loss_scratch)
         if (e.dev == dev && e.st == st) { *out = e.p; return 0; }
     float* p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, (size_t)4 * kHeadMaxBlocks * kPartStats * sizeof(float)));
+    // (the stats partial rows, then the diagnostics partial rows of pvae_ppo_loss_diag)
+    HIP_TRY(hipMalloc((void**)&p, (size_t)4 * kHeadMaxBlocks * (kPartStats + kDiagPart) * sizeof(float)));
     g_loss_scratch.push_back(LossScratch{dev, st, p});
     *out = p;
     return 0;
@@ -597,14 +733,39 @@ void fill_head(PpoHead& h, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params*
 }
 
 int ppo_head_launch(const PpoHead& h, hipStream_t st) {
-    hipLaunchKernelGGL(ppo_head_kernel, dim3(head_waves(pad32(h.rows)) / 4), dim3(256), 0, st, h);
+    const dim3 grid(head_waves(pad32(h.rows)) / 4);
+    if (h.dpart) hipLaunchKernelGGL(ppo_head_kernel<true>, grid, dim3(256), 0, st, h);
+    else hipLaunchKernelGGL(ppo_head_kernel<false>, grid, dim3(256), 0, st, h);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- learner diagnostics: the bound buffers ----
+size_t ppo_diag_bytes(int max_batch) {
+    return (size_t)kDiagSlots * sizeof(double) + (size_t)head_waves(pad32(max_batch)) * kDiagPart * sizeof(float);
+}
+int ppo_diag_bind(PpoDiag& d, float* diag, int capacity, void* scratch, size_t bytes, int max_batch) {
+    if (!diag) { d = PpoDiag(); return 0; }
+    if (capacity < 1) return fail(-1, "capacity_steps must be >= 1, got %d", capacity);
+    if (!scratch) return fail(-1, "diagnostics scratch is null");
+    if ((uintptr_t)scratch & 15) return fail(-1, "diagnostics scratch must be 16-byte aligned");
+    if (bytes < ppo_diag_bytes(max_batch)) return fail(-1, "diagnostics scratch too small: %zu < %zu bytes", bytes, ppo_diag_bytes(max_batch));
+    d.out = diag; d.capacity = capacity;
+    d.gslot = (double*)scratch; d.dpart = (float*)((double*)scratch + kDiagSlots);
+    return 0;
+}
+// the slots of an Adam launch of `nslots` workgroups added into entry 4 of the row
+static int ppo_gnorm_launch(const PpoDiagRow& dg, int nslots, hipStream_t st, int* launches) {
+    hipLaunchKernelGGL(ppo_gnorm_kernel, dim3(1), dim3(64), 0, st, (const double*)dg.gslot, nslots, dg.row + 4);
+    HIP_TRY(hipGetLastError());
+    if (launches) ++*launches;
     return 0;
 }
 
 // the arguments of the Adam launch in its three forms; returns the float4 elements of all segments
 static long long fill_adam(PpoAdam& a, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k,
-                           const float* part, int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out) {
+                           const float* part, int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out,
+                           const PpoDiagRow& dg) {
     memset((void*)&a, 0, sizeof(a));
     a.seg = segs;
     long long total4 = 0;
@@ -614,24 +775,33 @@ static long long fill_adam(PpoAdam& a, const PpoAdamSegs& segs, const pvae_fc_pp
     a.inv_rows = (float)(1.0 / rows); a.stats_out = stats_out;
     a.k = k;
     if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
+    a.dpart = dg.dpart; a.rows = rows; a.diag = dg.row; a.gslot = dg.gslot;
     return total4;
 }
 
 int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, hipStream_t st) {
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, hipStream_t st,
+                    int* launches) {
     PpoAdam a;
-    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out);
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg);
     long long grid = (total4 + 255) / 256;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3((int)grid + 1), dim3(256), 0, st, a);
+    static_assert(2048 + 1 <= kDiagSlots, "one gradient-norm slot per workgroup");
+    if (dg.row) hipLaunchKernelGGL(ppo_adam_kernel<true>, dim3((int)grid + 1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(ppo_adam_kernel<false>, dim3((int)grid + 1), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
-    return 0;
+    ++*launches;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
 }
 
-int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out, hipStream_t st,
-                           int* launches) {
+int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out,
+                           const PpoDiagRow& dg, hipStream_t st, int* launches) {
     const int nparts = head_waves(pad32(rows)), stride = part_stride(k, colsum != 0);
-    hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, nparts, stride, (float)(1.0 / rows), stats_out);
+    if (dg.row)
+        hipLaunchKernelGGL(ppo_finish_diag_kernel, dim3(1), dim3(128), 0, st, part, nparts, stride, (float)(1.0 / rows), stats_out,
+                           (const float*)dg.dpart, rows, dg.row, 0);
+    else
+        hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, nparts, stride, (float)(1.0 / rows), stats_out);
     HIP_TRY(hipGetLastError());
     ++*launches;
     if (colsum) {
@@ -643,23 +813,26 @@ int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float
 }
 
 int ppo_apply_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int k, float grad_scale,
-                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, hipStream_t st) {
+                     const float* ls_grad, int colsum, float* ls, float* ls_m, float* ls_v, const PpoDiagRow& dg, hipStream_t st,
+                     int* launches) {
     PpoAdam a;
-    const long long total4 = fill_adam(a, segs, p, adam_t, 1, k, nullptr, colsum, ls, ls_m, ls_v, nullptr);
+    const long long total4 = fill_adam(a, segs, p, adam_t, 1, k, nullptr, colsum, ls, ls_m, ls_v, nullptr, dg);
     long long grid = (total4 + 255) / 256;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(ppo_apply_kernel, dim3((int)grid + 1), dim3(256), 0, st, a, grad_scale, ls_grad);
+    if (dg.row) hipLaunchKernelGGL(ppo_apply_kernel<true>, dim3((int)grid + 1), dim3(256), 0, st, a, grad_scale, ls_grad);
+    else hipLaunchKernelGGL(ppo_apply_kernel<false>, dim3((int)grid + 1), dim3(256), 0, st, a, grad_scale, ls_grad);
     HIP_TRY(hipGetLastError());
-    return 0;
+    ++*launches;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
 }
 
 int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
                              int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
-                             float* stats_out, hipStream_t st) {
+                             float* stats_out, const PpoDiagRow& dg, hipStream_t st, int* launches) {
     if (!P.open) return fail(-2, "the PPO gradient exchange is not open");
     if (colsum && k != P.k) return fail(-2, "log-std vector of %d values, the exchange was exported for %d", k, P.k);
     PpoAdam a;
-    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out);
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg);
     PpoAdamPeers x;
     memset((void*)&x, 0, sizeof(x));
     for (int q = 0; q < P.world; ++q) {
@@ -683,14 +856,19 @@ int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdam
     if (grid > kExchangeMaxBlocks) grid = kExchangeMaxBlocks;
     if (grid < 1) grid = 1;
     switch (P.world) {
-#define PVAE_PPO_PEER_CASE(N) case N: hipLaunchKernelGGL((ppo_adam_exchange_kernel<N>), dim3((int)grid + 1), dim3(256), 0, st, a, x); break;
+#define PVAE_PPO_PEER_CASE(N)                                                                                              \
+    case N:                                                                                                                \
+        if (dg.row) hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, true>), dim3((int)grid + 1), dim3(256), 0, st, a, x);  \
+        else hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, false>), dim3((int)grid + 1), dim3(256), 0, st, a, x);        \
+        break;
         PVAE_PPO_PEER_CASE(1) PVAE_PPO_PEER_CASE(2) PVAE_PPO_PEER_CASE(3) PVAE_PPO_PEER_CASE(4)
         PVAE_PPO_PEER_CASE(5) PVAE_PPO_PEER_CASE(6) PVAE_PPO_PEER_CASE(7) PVAE_PPO_PEER_CASE(8)
 #undef PVAE_PPO_PEER_CASE
         default: return fail(-1, "world %d", P.world);
     }
     HIP_TRY(hipGetLastError());
-    return 0;
+    ++*launches;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
 }
 
 int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
@@ -823,11 +1001,11 @@ int check_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out) {
     return 0;
 }
 
-extern "C" {
 
-int pvae_ppo_loss(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
-                  const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
-                  float* d_mean, float* d_log_std, float* d_value, float* stats_out, void* stream) {
+// pvae_ppo_loss and pvae_ppo_loss_diag (diag_out != NULL: the head's DIAG instantiation and the two-wave finish)
+static int ppo_loss_run(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
+                        const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
+                        float* d_mean, float* d_log_std, float* d_value, float* stats_out, float* diag_out, void* stream) {
     int rc = check_loss_args(b, p, rows);
     if (rc) return rc;
     if (!mean || !log_std || !value) return fail(-1, "mean, log_std or value is null");
@@ -845,10 +1023,32 @@ int pvae_ppo_loss(const float* mean, const float* log_std, int64_t log_std_row_s
     h.d_ls = d_log_std; h.ld_dls = k; h.width_dls = k;
     h.d_value = d_value; h.ld_dv = 1; h.width_dv = 1;
     h.part = part; h.part_stride = kPartStats; h.colsum = 0;
+    if (diag_out) h.dpart = part + (size_t)4 * kHeadMaxBlocks * kPartStats;
     if ((rc = ppo_head_launch(h, st))) return rc;
-    hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, waves, kPartStats, h.inv_rows, stats_out);
+    if (diag_out)
+        hipLaunchKernelGGL(ppo_finish_diag_kernel, dim3(1), dim3(128), 0, st, (const float*)part, waves, (int)kPartStats, h.inv_rows,
+                           stats_out, (const float*)h.dpart, (int)rows, diag_out, 1);
+    else
+        hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, st, part, waves, kPartStats, h.inv_rows, stats_out);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int pvae_ppo_loss(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
+                  const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
+                  float* d_mean, float* d_log_std, float* d_value, float* stats_out, void* stream) {
+    return ppo_loss_run(mean, log_std, log_std_row_stride, value, b, index, rows, p, d_mean, d_log_std, d_value, stats_out, nullptr,
+                        stream);
+}
+
+int pvae_ppo_loss_diag(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
+                       const pvae_fc_ppo_batch* b, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* p,
+                       float* d_mean, float* d_log_std, float* d_value, float* stats_out, float* diag_out, void* stream) {
+    if (!diag_out) return fail(-1, "diag_out is null");
+    return ppo_loss_run(mean, log_std, log_std_row_stride, value, b, index, rows, p, d_mean, d_log_std, d_value, stats_out, diag_out,
+                        stream);
 }
 
 size_t pvae_fc_gae_workspace_bytes(int32_t n_segs) {

@@ -22,7 +22,7 @@ from ._lib import FLAG_FUSED_ADAM, FLAG_NO_BACKWARD, NET_MD, NET_MH, NET_NAMES, 
 from .arch import TENSOR_IDS, Arch, Stack                                                                  # noqa: F401
 from .engine_dp import DataParallelExchange
 from .engine_ppo import (PPO_COLUMNS, PpoSurface, evaluate_plan, gae, gae_scratch_for, make_act, make_ppo_batch,   # noqa: F401
-                         make_prepared, make_rollout, ppo_loss, prepare_plan)
+                         make_prepared, make_rollout, ppo_loss, ppo_loss_diag, prepare_plan)
 from .engine_rollout import RolloutClient
 from .stack_set import StackSetEngine, set_fc_per_stack                                                    # noqa: F401
 

@@ -129,6 +129,32 @@ class PpoSurface:
                                            int(num_sgd_iter), C.byref(params), *draws, stats.data_ptr(), self._stream()), what)
         return stats
 
+    def ppo_diag(self, buffer=None, row=0):
+        """`*_ppo_diag`: bind the learner-diagnostics rows (`ppo.diag_buffer`: float32 [steps, PPO_DIAG] on this device)
+        from row `row` on, or unbind (None).  While bound `ppo_step` writes the first bound row, `ppo_grad_step` its entries
+        0..3, `ppo_apply` its entry 4 and `ppo_sgd` one row per step (it refuses a buffer with fewer rows); see `ppo.DIAG`.
+        The partial-sum scratch is allocated once and kept with the engine."""
+        self._need_gpu()
+        what = self._PPO + "diag"
+        if buffer is None:
+            self._ppo_diag_keep = None
+            return _lib.check(getattr(self.lib, what)(self.ctx, None, 0, None, 0), what)
+        check_diag(buffer, None, self.device)
+        rows = int(buffer.shape[0]) - int(row)
+        assert rows >= 1, "row %d outside the %d diagnostics rows" % (row, buffer.shape[0])
+        if getattr(self, "ppo_diag_scratch", None) is None:
+            cfg = C.byref(self.cfg) if self._PPO == "pvae_fc_ppo_" else self.ctx
+            self.ppo_diag_bytes = int(getattr(self.lib, self._PPO + "diag_bytes")(cfg, 1))
+            self.ppo_diag_scratch = torch.zeros(self.ppo_diag_bytes // 8 + 2, dtype=torch.float64, device=self.device)
+        self._ppo_diag_keep = (buffer, int(row))              # (kept alive while bound)
+        _lib.check(getattr(self.lib, what)(self.ctx, buffer.data_ptr() + 4 * _lib.PPO_DIAG * int(row), rows,
+                                           self.ppo_diag_scratch.data_ptr(), self.ppo_diag_bytes), what)
+
+    def ppo_diag_bound(self):
+        """(buffer, row) as `ppo_diag` bound them last, or None: what a caller that binds rows of its own for one call
+        puts back afterwards (`ppo_diag(*bound)`)."""
+        return getattr(self, "_ppo_diag_keep", None)
+
     def ppo_launches(self):
         """Kernel launches of the last PPO step."""
         n = C.c_int32()
@@ -413,6 +439,17 @@ def make_ppo_batch(batch, device, k, n_in=None):
     return b, keep
 
 
+def check_diag(diag, steps, device):
+    """A diagnostics buffer is contiguous float32 [rows >= steps, PPO_DIAG] on `device`: a ValueError names what was
+    given and what is wanted (`steps` None: any number of rows)."""
+    want = "contiguous float32 [%s, %d] on %s" % ("rows" if steps is None else ">= %d" % steps, _lib.PPO_DIAG, torch.device(device))
+    ok = torch.is_tensor(diag) and diag.dtype == torch.float32 and diag.dim() == 2 and diag.shape[1] == _lib.PPO_DIAG \
+        and diag.is_contiguous() and diag.device == torch.device(device) and (steps is None or diag.shape[0] >= steps)
+    if not ok:
+        got = "%s %s on %s" % (diag.dtype, list(diag.shape), diag.device) if torch.is_tensor(diag) else repr(type(diag))
+        raise ValueError("diag_out must be %s (ppo.diag_buffer), got %s" % (want, got))
+
+
 def _check_index(index, n_rows, device):
     if index is not None:
         assert index.dtype == torch.int32 and index.is_contiguous() and index.device == torch.device(device), \
@@ -423,6 +460,19 @@ def ppo_loss(mean, log_std, value, batch, params, index=None):
     """`pvae_ppo_loss`: the loss head alone on dense tensors.  mean [rows, k]; log_std [rows, k] (a row stride of 0 -- an
     expanded vector -- is passed as it is); value [rows]; `batch`: the columns (dict, or what `make_ppo_batch` returned),
     row r read at index[r].  Returns (stats [5], d_mean, d_log_std [rows, k], d_value): the gradients of stats[0]."""
+    return _ppo_loss(mean, log_std, value, batch, params, index, None)
+
+
+def ppo_loss_diag(mean, log_std, value, batch, params, index=None, diag_out=None):
+    """`pvae_ppo_loss_diag`: `ppo_loss` with the learner diagnostics of the same rows.  `diag_out`: float32 [PPO_DIAG] on
+    the device (None: allocated), filled with entries 0..3 of `ppo.DIAG` and 0 in the rest.  Returns `ppo_loss`'s four
+    tensors, bit for bit, and the diagnostics row.  (Its own name: `ppo_loss`'s signature is pinned.)"""
+    if diag_out is None:
+        diag_out = torch.zeros(_lib.PPO_DIAG, dtype=torch.float32, device=mean.device)
+    return _ppo_loss(mean, log_std, value, batch, params, index, diag_out) + (diag_out,)
+
+
+def _ppo_loss(mean, log_std, value, batch, params, index, diag_out):
     lib = _lib.load()
     dev = mean.device
     assert dev.type == "cuda", "pvae_ppo_loss needs a GPU (there is no CPU fallback)"
@@ -430,6 +480,7 @@ def ppo_loss(mean, log_std, value, batch, params, index=None):
     mean = mean.float().contiguous()
     value = value.float().reshape(rows).contiguous()
     assert tuple(log_std.shape) == (rows, k)
+    assert log_std.device == dev and value.device == dev, "mean, log_std and value must be on one device (%s)" % dev
     if not (log_std.dtype == torch.float32 and (k == 1 or log_std.stride(1) == 1) and log_std.stride(0) in (0, k)):
         log_std = log_std.float().contiguous()
     stride = 0 if (rows > 1 and log_std.stride(0) == 0) else k
@@ -439,11 +490,17 @@ def ppo_loss(mean, log_std, value, batch, params, index=None):
     assert index is None or index.numel() >= rows
     d_mean, d_ls, d_val = torch.empty_like(mean), torch.empty(rows, k, dtype=torch.float32, device=dev), torch.empty_like(value)
     stats = torch.empty(5, dtype=torch.float32, device=dev)
+    if diag_out is not None:
+        check_diag(diag_out.view(1, -1) if torch.is_tensor(diag_out) and diag_out.dim() == 1 else diag_out, 1, dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.pvae_ppo_loss(mean.data_ptr(), log_std.data_ptr(), stride, value.data_ptr(), C.byref(b),
-                                     index.data_ptr() if index is not None else None, rows, C.byref(params),
-                                     d_mean.data_ptr(), d_ls.data_ptr(), d_val.data_ptr(), stats.data_ptr(),
-                                     torch.cuda.current_stream(dev).cuda_stream), "pvae_ppo_loss")
+        args = (mean.data_ptr(), log_std.data_ptr(), stride, value.data_ptr(), C.byref(b),
+                index.data_ptr() if index is not None else None, rows, C.byref(params),
+                d_mean.data_ptr(), d_ls.data_ptr(), d_val.data_ptr(), stats.data_ptr())
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if diag_out is None:
+            _lib.check(lib.pvae_ppo_loss(*args, st), "pvae_ppo_loss")
+        else:
+            _lib.check(lib.pvae_ppo_loss_diag(*args, diag_out.data_ptr(), st), "pvae_ppo_loss_diag")
     return stats, d_mean, d_ls, d_val
 
 

@@ -237,7 +237,7 @@ class FullyConnectedPolicy(nn.Module):
         return [t for t in (eng.params, eng.ppo_m, eng.ppo_v, vector, eng.ppo_ls_m if train_ls else None,
                             eng.ppo_ls_v if train_ls else None) if t is not None]
 
-    def ppo_learn(self, batch, config, perm=None, dp=None):
+    def ppo_learn(self, batch, config, perm=None, dp=None, diag_out=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_fc_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step
         forward + PPO loss + backward + Adam in 9 launches, nothing synchronised.  `batch`: device tensors under RLlib's
@@ -249,8 +249,12 @@ class FullyConnectedPolicy(nn.Module):
         workers before Adam (the rule: `ppo.py`'s module docstring); the call is collective, the workers' row counts are
         gathered once and a ValueError names the ranks that would issue another number of steps.  The stats stay this
         worker's own.  With "p2p" the one library call is unchanged; with "torch" every minibatch is `pvae_fc_ppo_grad`,
-        an all-reduce, `pvae_fc_ppo_apply`."""
+        an all-reduce, `pvae_fc_ppo_apply`.  `diag_out`: a float32 device tensor [steps, PPO_DIAG] from `ppo.diag_buffer`,
+        filled in place with the per-step learner diagnostics (`ppo.DIAG`; one small launch more per step, nothing
+        synchronised; `ppo.learner_info(stats, diag_out, config)` reads both); a wrong shape or device is a ValueError.  Rows the
+        caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns."""
         from . import ppo as P
+        from . import engine_ppo as E
         eng = self.engine
         eng._need_gpu()
         if config.sgd_minibatch_size > eng.max_batch:
@@ -272,11 +276,19 @@ class FullyConnectedPolicy(nn.Module):
             perm = perm.to(eng.device, torch.int32).contiguous()
         if dp is not None:
             dp.check_steps(int(cols[0].n_rows), config, eng.device)
-        if dp is not None and dp.transport == "torch":
-            stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=params.train_mask),
-                           int(cols[0].n_rows), config, perm, train_ls)
-        else:
-            stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm)
+        if diag_out is not None:
+            E.check_diag(diag_out, P.dp_steps(int(cols[0].n_rows), config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
+            bound = eng.ppo_diag_bound()
+            eng.ppo_diag(diag_out)
+        try:
+            if dp is not None and dp.transport == "torch":
+                stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=params.train_mask),
+                               int(cols[0].n_rows), config, perm, train_ls, diag_out=diag_out)
+            else:
+                stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm)
+        finally:
+            if diag_out is not None:
+                eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
         self.__dict__["_ppo_t"] = t + stats.shape[0]
         self._cur_value = None
         return stats

@@ -899,7 +899,7 @@ class PhysicsVAE(nn.Module):
         return [t for t in (eng.params, ve.params, eng.ppo_m, eng.ppo_v, ve.ppo_m, ve.ppo_v, vector,
                             eng.ppo_ls_m if train_ls else None, eng.ppo_ls_v if train_ls else None) if t is not None]
 
-    def ppo_learn(self, batch, config, perm=None, eps=None, dp=None):
+    def ppo_learn(self, batch, config, perm=None, eps=None, dp=None, diag_out=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_ppo_sgd`):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step the
         forward of rmt:742-771 without the world model, the PPO loss, backward and Adam, nothing synchronised.  `batch`:
@@ -914,8 +914,12 @@ class PhysicsVAE(nn.Module):
         docstring; the rank does not enter the Philox stream: give every worker's module its own seed); the call is
         collective, the workers' row counts are gathered once and a ValueError names the ranks that would issue another
         number of steps.  The stats stay this worker's own.  With "p2p" the one library call is unchanged; with "torch" every
-        minibatch is `pvae_ppo_grad`, an all-reduce of both gradient arenas, `pvae_ppo_apply`."""
+        minibatch is `pvae_ppo_grad`, an all-reduce of both gradient arenas, `pvae_ppo_apply`.  `diag_out`: a float32 device
+        tensor [steps, PPO_DIAG] from `ppo.diag_buffer`, filled in place with the per-step learner diagnostics (`ppo.DIAG`;
+        one small launch more per step, nothing synchronised); a wrong shape or device is a ValueError.  Rows the
+        caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns."""
         from . import ppo as P
+        from . import engine_ppo as E
         eng = self.engine
         self._ppo_refusals()
         mask = self._ppo_train_mask()
@@ -939,15 +943,23 @@ class PhysicsVAE(nn.Module):
         draws = dict(eps=eps, noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
         if dp is not None:
             dp.check_steps(int(cols[0].n_rows), config, eng.device)
-        if dp is not None and dp.transport == "torch":
-            n = int(cols[0].n_rows)
-            steps = P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter)
-            draws["eps"] = eng._ppo_eps(eps, (steps, config.sgd_minibatch_size, eng.arch.Z))
-            kind = "state_independent" if train_ls else "constant"
-            stats = dp.sgd(eng, cols, lambda i: config.params(kind, 0.0, adam_t=t + 1 + i, train_mask=params.train_mask), n,
-                           config, perm, train_ls, **draws)
-        else:
-            stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm, **draws)
+        if diag_out is not None:
+            E.check_diag(diag_out, P.dp_steps(int(cols[0].n_rows), config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
+            bound = eng.ppo_diag_bound()
+            eng.ppo_diag(diag_out)
+        try:
+            if dp is not None and dp.transport == "torch":
+                n = int(cols[0].n_rows)
+                steps = P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter)
+                draws["eps"] = eng._ppo_eps(eps, (steps, config.sgd_minibatch_size, eng.arch.Z))
+                kind = "state_independent" if train_ls else "constant"
+                stats = dp.sgd(eng, cols, lambda i: config.params(kind, 0.0, adam_t=t + 1 + i, train_mask=params.train_mask), n,
+                               config, perm, train_ls, diag_out=diag_out, **draws)
+            else:
+                stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm, **draws)
+        finally:
+            if diag_out is not None:
+                eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
         st._rng_calls += stats.shape[0]
         self.__dict__["_ppo_t"] = t + stats.shape[0]
         st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone

@@ -398,10 +398,12 @@ class PPODataParallel:
             rows = [int(x.item()) for x in parts]
         return P.dp_check_steps(rows, config.sgd_minibatch_size, config.num_sgd_iter)
 
-    def sgd(self, engine, cols, params_at, n_rows, config, perm, train_ls, **draws):
+    def sgd(self, engine, cols, params_at, n_rows, config, perm, train_ls, diag_out=None, **draws):
         """The SGD loop of `*_ppo_sgd` on the "torch" transport: per minibatch `ppo_grad_step`, a SUM all-reduce of the
         gradient buffers and of a trained log-std vector's gradient, `ppo_apply` with grad_scale = 1 / N.  `params_at(i)`:
-        step i's pvae_fc_ppo_params; `draws` (PhysicsVAE): eps [steps, minibatch, Z] or None, noise, seed, offset."""
+        step i's pvae_fc_ppo_params; `draws` (PhysicsVAE): eps [steps, minibatch, Z] or None, noise, seed, offset.
+        `diag_out`: the diagnostics rows (`ppo.diag_buffer`) -- step i's two halves are bound to row i, so both transports
+        fill the same rows; the norm is that of the averaged gradient, what `ppo_apply` consumes.  The caller unbinds."""
         mb = int(config.sgd_minibatch_size)
         steps = config.num_sgd_iter * ((n_rows + mb - 1) // mb)
         stats = torch.empty(steps, 5, dtype=torch.float32, device=engine.device)
@@ -413,6 +415,8 @@ class PPODataParallel:
             for first in range(0, n_rows, mb):
                 rows = min(mb, n_rows - first)
                 prm = params_at(i)
+                if diag_out is not None:
+                    engine.ppo_diag(diag_out, row=i)
                 kw = dict(draws, eps=None if eps is None else eps[i, :rows], offset=offset + i) if draws else {}
                 _, ls_grad = engine.ppo_grad_step(cols, prm, first, rows, index, stats_out=stats[i], **kw)
                 if self.world > 1:

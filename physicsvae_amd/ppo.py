@@ -83,6 +83,9 @@ from . import engine_ppo as E
 SAMPLE_BATCH_KEYS = {"obs": "obs", "actions": "actions", "action_dist_inputs": "old_dist", "action_logp": "old_logp",
                      "advantages": "advantages", "value_targets": "value_targets", "vf_preds": "vf_preds"}
 STATS = ("total_loss", "policy_loss", "vf_loss", "kl", "entropy")
+# the per-step learner diagnostics (include/pvae.h "Learner diagnostics"): rows of PPO_DIAG floats, entries 5..7 reserved (0)
+DIAG = ("vf_explained_var", "clip_frac", "vf_clip_frac", "ratio_max_dev", "grad_gnorm")
+PPO_DIAG = _lib.PPO_DIAG
 
 
 class PPOConfig:
@@ -358,6 +361,85 @@ class HipPPOLoss(torch.autograd.Function):
         return (d_mean.mul(g_total).view(ctx.shapes[0]) if need[0] else None,
                 d_ls.mul(g_total).view(ctx.shapes[1]) if need[1] else None,
                 d_val.mul(g_total).view(ctx.shapes[2]) if need[2] else None, None, None, None)
+
+
+def learner_diag_torch(mean, log_std, value, actions, old_dist, old_logp, advantages, value_targets, vf_preds, cfg):
+    """The first four entries of `DIAG` for one minibatch in plain torch, any dtype and device: a tensor [4].  The
+    arguments are `ppo_loss_torch`'s; with y = value_targets, v = value and ratio as the loss forms it, over the B rows:
+
+        vf_explained_var = max(-1, 1 - Var(y - v) / Var(y))
+        clip_frac        = share of rows with ratio < 1 - clip_param or ratio > 1 + clip_param
+        vf_clip_frac     = share of rows with |v - vf_preds| > vf_clip_param
+        ratio_max_dev    = max over the rows of |ratio - 1|
+
+    vf_explained_var is RLlib 1.11's `explained_variance` AS RECALLED (it has not been checked against a ray installation,
+    none was at hand): upstream uses `torch.var`, whose n - 1 cancels in the quotient, so the population variances taken
+    here give the same number.  Our choice where upstream gives nan or -inf: B == 1 or Var(y) == 0 gives exactly -1.
+    The sums are taken around the first row's y and y - v, as the kernel takes them: in float32, raw sums of y and y^2
+    lose the variance of targets far from zero.
+    The kernel's entry 3 is NOT taken from the ratio the loss forms: the loss's float32 log-density, whose bits the stats pin,
+    carries its own ulp into ratio - 1, so the kernel sums a second log-density in double for this one entry, while clip_frac
+    in the same row counts the loss's float32 ratio.  A ratio within float32 rounding of a clip boundary can therefore show
+    ratio_max_dev < clip_param beside clip_frac > 0, or the reverse."""
+    _, ratio, _, _, _, _ = _terms(mean, log_std, value, actions, old_dist, old_logp, advantages, value_targets, vf_preds, cfg)
+    n = mean.shape[0]
+    y, e = value_targets, value_targets - value
+    dy, de = y - y[0], e - e[0]
+    var_y = (dy * dy).sum() / n - (dy.sum() / n) ** 2
+    var_e = (de * de).sum() / n - (de.sum() / n) ** 2
+    minus1 = -torch.ones((), dtype=mean.dtype, device=mean.device)
+    if n > 1 and float(var_y) > 0.0:
+        ev = torch.maximum(minus1, 1 - torch.clamp(var_e, min=0.0) / var_y)
+    else:
+        ev = minus1
+    clipped = (ratio < 1 - cfg.clip_param) | (ratio > 1 + cfg.clip_param)
+    vf_clipped = (value - vf_preds).abs() > cfg.vf_clip_param
+    return torch.stack([ev, clipped.to(mean.dtype).mean(), vf_clipped.to(mean.dtype).mean(), (ratio - 1).abs().max()])
+
+
+def grad_gnorm_torch(grads):
+    """`DIAG`'s fifth entry: sqrt(sum g^2) over every element of the tensors given -- the gradient Adam consumes: every
+    trained segment and a trained log-std vector's gradient, after the workers' exchange and `grad_scale`, before weight
+    decay (what `clip_grad_norm_` would see; RLlib's `grad_gnorm`).  Accumulated in float64 whatever the inputs' dtype."""
+    total = torch.zeros((), dtype=torch.float64)
+    for g in grads:
+        total = total + (g.detach().double() ** 2).sum().cpu()
+    return torch.sqrt(total)
+
+
+def diag_buffer(n_rows, config, device):
+    """A zeroed float32 [dp_steps(n_rows, ...), PPO_DIAG] device tensor: what `ppo_learn(..., diag_out=)` fills for a
+    train batch of `n_rows` rows under `config`."""
+    steps = dp_steps(n_rows, config.sgd_minibatch_size, config.num_sgd_iter)
+    return torch.zeros(steps, PPO_DIAG, dtype=torch.float32, device=device)
+
+
+def learner_info(stats, diag, config):
+    """One `ppo_learn` call's stats [steps, 5] and diagnostics [steps, PPO_DIAG] as a dict under RLlib's learner-stats
+    keys (total_loss, policy_loss, vf_loss, vf_explained_var, kl, entropy, cur_kl_coeff, cur_lr, entropy_coeff) and ours
+    (clip_frac, vf_clip_frac, grad_gnorm, ratio_max_dev).  The values are means over the steps, `ratio_max_dev` the max;
+    ONE host synchronisation (both tensors come over in one copy)."""
+    steps = stats.shape[0]
+    assert tuple(stats.shape) == (steps, len(STATS)) and tuple(diag.shape) == (steps, PPO_DIAG), \
+        "stats must be [steps, %d] and diag [steps, %d]" % (len(STATS), PPO_DIAG)
+    both = torch.cat([stats.float(), diag.float().to(stats.device)], dim=1).cpu().double()
+    mean, top = both.mean(0), both.max(0).values
+    info = {name: float(mean[i]) for i, name in enumerate(STATS)}
+    for i, name in enumerate(DIAG):
+        info[name] = float(top[len(STATS) + i] if name == "ratio_max_dev" else mean[len(STATS) + i])
+    info.update(cur_kl_coeff=float(config.kl_coeff), cur_lr=float(config.lr), entropy_coeff=float(config.entropy_coeff))
+    return info
+
+
+def update_kl_coeff(kl_coeff, sampled_kl, kl_target=0.01):
+    """RLlib's adaptive KL rule, once per training iteration on the host: a sampled KL above 2 * kl_target multiplies the
+    coefficient by 1.5, one below 0.5 * kl_target by 0.5, anything between (the bounds included) leaves it.  Returns the
+    next iteration's coefficient (`PPOConfig.kl_coeff` is the caller's to set)."""
+    if sampled_kl > 2.0 * kl_target:
+        return kl_coeff * 1.5
+    if sampled_kl < 0.5 * kl_target:
+        return kl_coeff * 0.5
+    return kl_coeff
 
 
 def batch_columns(batch):

@@ -11,7 +11,8 @@ The ways alternate block by block within the session (`--rounds` rounds of `--st
 drift hit all of them alike; reported per way: median, min and max of the per-round means, in microseconds, and for (c)
 and (d) the acceptance figure: (a.median - x.median) / (a.max - a.min), which must exceed 3.  Prints one JSON line.
 
-    python tools/ppo_bench.py [--rows 500] [--steps 200] [--rounds 7] [--warmup 30] [--one-step]
+    python tools/ppo_bench.py [--rows 500] [--steps 200] [--rounds 7] [--warmup 30] [--one-step] [--diag]
+`--diag`: ways c and d run with a learner-diagnostics buffer bound (`ppo_diag`; one small launch more per step).
 `--one-step`: run a single fused step per log-std type and exit (for a kernel trace of one step).
 """
 import argparse
@@ -59,9 +60,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--one-step", action="store_true")
+    ap.add_argument("--diag", action="store_true",
+                    help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
     a = ap.parse_args()
     cfg = P.PPOConfig(clip_param=0.2, kl_coeff=0.0, vf_clip_param=1000.0, lr=1e-6, sgd_minibatch_size=a.rows, num_sgd_iter=1)
-    out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": OBS}
+    out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": OBS, "diag": bool(a.diag)}
     for kind in ("constant", "state_dependent"):
         torch.manual_seed(0)
         g = torch.Generator(device="cuda").manual_seed(0)
@@ -77,6 +80,8 @@ def main():
         base = float(f._log_std_base) if kind == "state_dependent" else 0.0
         eng = f.engine
         eng.ppo_bind(None if kind == "state_dependent" else f._policy_fn._model[-1].on_device(eng.device), False)
+        if a.diag:
+            eng.ppo_diag(torch.zeros(a.steps, P.PPO_DIAG, dtype=torch.float32, device="cuda"))   # one row per step of way d
         fb, fbig = eng.ppo_batch(cols), eng.ppo_batch(P.batch_columns(big))
         loss_params = cfg.params(kind, base)
         loss_cols = {k: v for k, v in cols.items() if k != "obs"}

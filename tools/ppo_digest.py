@@ -12,6 +12,9 @@ scenario -> output tensor -> sha256 of its raw bytes.  The library is the in-tre
 
 Two builds that launch the same kernels in the same order with the same arithmetic print the same line.  The digests belong
 to one compiler and one pair of builds: they are compared, never pinned.
+
+`--diag` binds a learner-diagnostics buffer (`ppo_diag`) on every engine of the learner scenarios and adds its rows to
+their digests under "diag": every other digest must then be the one printed without the flag.
 """
 import hashlib
 import json
@@ -29,6 +32,15 @@ DEV = "cuda"
 K = 5
 CFG = P.PPOConfig(clip_param=0.2, kl_coeff=0.3, entropy_coeff=0.01, vf_clip_param=0.7, vf_loss_coeff=0.5, lr=1e-3,
                   gamma=0.98, lambda_=0.95)
+DIAG = False                                                     # set by main() from `--diag`
+
+
+def bind_diag(eng):
+    """`--diag`: eight zeroed diagnostics rows bound to the engine and kept on it (more than any scenario's steps)."""
+    eng.diag_rows = None
+    if DIAG:
+        eng.diag_rows = torch.zeros(8, P.PPO_DIAG, dtype=torch.float32, device=DEV)
+        eng.ppo_diag(eng.diag_rows)
 
 
 def digest(tensors):
@@ -89,6 +101,7 @@ def fc_engine(kind, max_batch, rng):
         fill(eng.views(s), rng)
     ls = None if kind == 2 else log_std_vector(rng)
     eng.ppo_bind(ls, kind == 1)
+    bind_diag(eng)
     return eng, ls
 
 
@@ -104,11 +117,12 @@ def fc_sgd(out):
                                     perms(rng, 2, 70) if with_perm else None)
                 out["fc_sgd kind%d perm%d value_frozen%d" % (kind, with_perm, frozen)] = digest(
                     {"stats": stats, "params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "log_std": ls,
-                     "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v})
+                     "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v, "diag": eng.diag_rows})
 
 
 def state(eng, ls, ve=None):
-    d = {"params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "log_std": ls, "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v}
+    d = {"params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "log_std": ls, "log_std_m": eng.ppo_ls_m, "log_std_v": eng.ppo_ls_v,
+         "diag": eng.diag_rows}
     if ve is not None:
         d.update({"value_params": ve.params, "value_m": ve.ppo_m, "value_v": ve.ppo_v})
     return d
@@ -214,6 +228,7 @@ def vae_engine(prior, kind, max_batch, rng):
     fill(ve.views(0), rng)
     ls = log_std_vector(rng)
     eng.ppo_bind(ve, ls, kind == 1)
+    bind_diag(eng)
     return eng, ve, ls
 
 
@@ -231,7 +246,7 @@ def vae_sgd(out):
                     out["vae_sgd prior_%s kind%d eps%d mask%d" % (prior, kind, with_eps, mask)] = digest(
                         {"stats": stats, "params": eng.params, "m": eng.ppo_m, "v": eng.ppo_v, "value_params": ve.params,
                          "value_m": ve.ppo_m, "value_v": ve.ppo_v, "log_std": ls, "log_std_m": eng.ppo_ls_m,
-                         "log_std_v": eng.ppo_ls_v})
+                         "log_std_v": eng.ppo_ls_v, "diag": eng.diag_rows})
 
 
 def vae_prepare(out):
@@ -267,6 +282,8 @@ def vae_act(out):
 
 
 def main():
+    global DIAG
+    DIAG = "--diag" in sys.argv[1:]
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
     out = {}
     for scenario in (fc_sgd, fc_steps, fc_act, loss, gae, fc_prepare, vae_sgd, vae_steps, vae_act, vae_prepare):

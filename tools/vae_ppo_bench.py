@@ -11,7 +11,8 @@ The ways alternate block by block within the session (`--rounds` rounds of `--st
 drift hit all of them alike; reported per way: median, min and max of the per-round means, in microseconds, and for (c)
 and (d) the acceptance figure: (b.median - x.median) / (b.max - b.min), which must exceed 3.  Prints one JSON line.
 
-    python tools/vae_ppo_bench.py [--rows 500] [--steps 200] [--rounds 7] [--warmup 30] [--one-step]
+    python tools/vae_ppo_bench.py [--rows 500] [--steps 200] [--rounds 7] [--warmup 30] [--one-step] [--diag]
+`--diag`: ways c and d run with a learner-diagnostics buffer bound (`ppo_diag`; one small launch more per step).
 `--one-step`: run a single fused step and exit (for a kernel trace of one step).
 """
 import argparse
@@ -61,6 +62,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--one-step", action="store_true")
+    ap.add_argument("--diag", action="store_true",
+                    help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
     a = ap.parse_args()
     cfg = P.PPOConfig(clip_param=0.2, kl_coeff=0.0, vf_clip_param=1000.0, lr=1e-6, sgd_minibatch_size=a.rows, num_sgd_iter=1)
     out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": 2 * DB}
@@ -78,6 +81,9 @@ def main():
     opt = torch.optim.Adam([p for p in m.parameters() if p.requires_grad], lr=cfg.lr)
     eng = f.engine
     eng.ppo_bind(f._ppo_value_engine(), f._als.on_device(eng.device), False)
+    out["diag"] = bool(a.diag)
+    if a.diag:
+        eng.ppo_diag(torch.zeros(a.steps, P.PPO_DIAG, dtype=torch.float32, device="cuda"))       # one row per step of way d
     fb, fbig = eng.ppo_batch(cols), eng.ppo_batch(P.batch_columns(big))
     loss_params = cfg.params("constant")
     loss_cols = {k: v for k, v in cols.items() if k != "obs"}
