@@ -787,7 +787,8 @@ int pvae_fc_ppo_sizeof(int which);
  *                          old_dist and old_logp (all three or none), those as they are and no evaluate launch over the
  *                          rows --, bootstrap, GAE, standardise.
  *   pvae_fc_gae_launches   launches of the last pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate on this context: the evaluate
- *                          pass over the rows, and the rest (bootstrap + GAE + standardise).
+ *                          pass over the rows, and the rest (bootstrap + GAE + standardise).  Both counters are zeroed on entry of
+ *                          either call, so after a refused call they read 0, 0 (after one that a HIP error cut short: 0, 0 too).
  * Bad arguments (ends of seg_start that are not 0 and n_rows, n_segs < 1, a stack set that is not [policy, value(,
  * log-std)], an unbound buffer, a short scratch) return a negative code and launch nothing. */
 typedef struct pvae_gae_params {

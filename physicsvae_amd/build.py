@@ -13,7 +13,7 @@ UNITS = ["pvae.hip", "pvae_net.hip", "pvae_step.hip", "pvae_lookahead.hip", "pva
          "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip", "pvae_ppo.hip"]
 GEMM_HEADERS = ["pvae_gemm_common.h", "pvae_stage.h", "pvae_gemm_src.h", "pvae_gemm_reg.h", "pvae_gemm_ws.h",
                 "pvae_gemm_wgrad.h", "pvae_adam.h", "pvae_gemm_fused.h", "pvae_gemm_epi.h", "pvae_gemm_launch.h"]   # what pvae_gemm.h includes
-HEADERS = ["pvae_internal.h", "pvae_gemm.h"] + GEMM_HEADERS + ["pvae_layout.h", "pvae_fc_layout.h"]
+HEADERS = ["pvae_internal.h", "pvae_ppo_learner.h", "pvae_gemm.h"] + GEMM_HEADERS + ["pvae_layout.h", "pvae_fc_layout.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(HERE), "include", "pvae.h")
 # -amdgpu-kernarg-preload-count: leading scalar / pointer kernel arguments arrive in SGPRs at wave launch (gfx950)

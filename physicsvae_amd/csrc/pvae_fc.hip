@@ -11,11 +11,12 @@
 // gradient bodies, the bias sums), on (pointer, ld) operands into the arena of pvae_fc_layout.h; a group launch only
 // decides which body a workgroup runs and on which operands.  A problem's tile geometry depends on the problem alone,
 // never on what shares its launch, so the per-stack schedule (option "fc_per_stack") gives the same bits.
-// Below the stack set itself: its PPO learner step and train-batch preparation (pvae_fc_ppo_*), which run the forward
-// and backward launches above with the loss head, Adam, epilogue and GAE launches of pvae_ppo_core.hip between them, and
-// the value stack alone as PhysicsVAE's learner (pvae_ppo.hip) runs it.
+// Below the stack set itself: its PPO learner (pvae_fc_ppo_*) -- FcLearner, the model adapter the host driver of
+// pvae_ppo_learner.h runs: the set's checks, and the forward and backward launches above around the loss head of
+// pvae_ppo_core.hip -- and the value stack alone as PhysicsVAE's learner (pvae_ppo.hip) runs it.
 #include "pvae_internal.h"
 #include "pvae_fc_layout.h"
+#include "pvae_ppo_learner.h"
 
 struct pvae_fc {
     FcLayout L;
@@ -23,18 +24,7 @@ struct pvae_fc {
     float* params = nullptr;
     float* ws = nullptr;
     int fwd_launches = 0, bwd_launches = 0;
-    // PPO learner step (pvae_fc_ppo_bind)
-    float* grad = nullptr;
-    float* m = nullptr;
-    float* v = nullptr;
-    float* scratch = nullptr;
-    float* log_std = nullptr;
-    float* log_std_m = nullptr;
-    float* log_std_v = nullptr;
-    int ppo_launches = 0;
-    int eval_launches = 0, gae_launches = 0;      // pvae_fc_ppo_prepare / pvae_fc_ppo_evaluate (pvae_fc_gae_launches)
-    PpoPeers peers;                               // the learner's gradient exchange between workers (pvae_fc_ppo_peer_*)
-    PpoDiag diag;                                 // learner diagnostics (pvae_fc_ppo_diag)
+    PpoLearner ppo;                               // PPO learner (pvae_fc_ppo_bind)
 };
 
 namespace {
@@ -490,35 +480,86 @@ void set_range(Run& r, int S) {
         if (r.want[s]) { if (r.s_lo < 0) r.s_lo = s; r.s_hi = s; }
 }
 
-// ---- PPO learner step, host side ----
-int check_ppo(pvae_fc* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows, const float* stats) {
-    if (!c) return fail(-1, "null stack set");
-    if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
-    if (!c->grad || !c->m || !c->v || !c->scratch) return fail(-2, "pvae_fc_ppo_bind has not been called");
-    int rc = check_loss_args(b, p, rows);
-    if (rc) return rc;
-    if (!b->obs) return fail(-1, "batch obs is null");
-    if (!stats) return fail(-1, "stats_out is null");
-    const FcLayout& L = c->L;
-    if (L.S < 2 || L.S > 3) return fail(-1, "a PPO step needs [policy, value] or [policy, value, log-std] stacks, got %d", L.S);
-    if (L.cfg.n_out[1] != 1) return fail(-1, "stacks in the wrong order: stack 1 must be the value function (n_out 1, got %d)", L.cfg.n_out[1]);
-    if (L.S == 3 && L.cfg.n_out[2] != L.cfg.n_out[0])
-        return fail(-1, "stacks in the wrong order: the log-std stack (2) must be as wide as the policy stack (0)");
-    if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
-    if (b->k != L.cfg.n_out[0]) return fail(-1, "batch k %d != policy outputs %d", b->k, L.cfg.n_out[0]);
-    if (p->log_std_kind != 2 && !c->log_std) return fail(-2, "log_std vector not bound (pvae_fc_ppo_bind)");
-    if (p->log_std_kind == 1 && (!c->log_std_m || !c->log_std_v)) return fail(-2, "log_std moments not bound (pvae_fc_ppo_bind)");
-    if (rows > L.cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, L.cfg.max_batch);
-    if (first < 0 || first + rows > b->n_rows) return fail(-1, "rows [%lld, +%d) outside the batch of %lld", first, rows, (long long)b->n_rows);
-    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
-    if (p->train_mask < 0 || p->train_mask >= (1 << L.S)) return fail(-1, "train_mask names a stack that does not exist");
-    return 0;
-}
+// ---- the PPO learner and its train-batch preparation: the stack set as the driver (pvae_ppo_learner.h) sees it ----
+struct FcLearner {
+    pvae_fc* c;
+    PpoLearner* learner() const { return c ? &c->ppo : nullptr; }
+    int k() const { return c->L.cfg.n_out[0]; }
+    int n_in() const { return c->L.cfg.n_in; }
+    int max_minibatch() const { return c->L.cfg.max_batch; }
+    long long peer_timeout() const { return g_ppo_peer_timeout_ticks; }
+    void params_written(hipStream_t) const {}
+    float* eps_out() const { return nullptr; }
+
+    // the checks of a step in their order; check_bound and check_update are the parts the second half shares
+    int check_bound() const {
+        if (!c) return fail(-1, "null stack set");
+        if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
+        const PpoLearner& q = c->ppo;
+        if (!q.grad || !q.m || !q.v || !q.scratch) return fail(-2, "pvae_fc_ppo_bind has not been called");
+        return 0;
+    }
+    int check_update(const pvae_fc_ppo_params* p) const {
+        if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
+        if (p->train_mask < 0 || p->train_mask >= (1 << c->L.S)) return fail(-1, "train_mask names a stack that does not exist");
+        return 0;
+    }
+    int check_step(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows, const float* stats) const {
+        int rc = check_bound();
+        if (rc) return rc;
+        if ((rc = check_loss_args(b, p, rows))) return rc;
+        if (!b->obs) return fail(-1, "batch obs is null");
+        if (!stats) return fail(-1, "stats_out is null");
+        const FcLayout& L = c->L;
+        const PpoLearner& q = c->ppo;
+        if (L.S < 2 || L.S > 3) return fail(-1, "a PPO step needs [policy, value] or [policy, value, log-std] stacks, got %d", L.S);
+        if (L.cfg.n_out[1] != 1) return fail(-1, "stacks in the wrong order: stack 1 must be the value function (n_out 1, got %d)", L.cfg.n_out[1]);
+        if (L.S == 3 && L.cfg.n_out[2] != L.cfg.n_out[0])
+            return fail(-1, "stacks in the wrong order: the log-std stack (2) must be as wide as the policy stack (0)");
+        if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
+        if (b->k != L.cfg.n_out[0]) return fail(-1, "batch k %d != policy outputs %d", b->k, L.cfg.n_out[0]);
+        if (p->log_std_kind != 2 && !q.log_std) return fail(-2, "log_std vector not bound (pvae_fc_ppo_bind)");
+        if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_fc_ppo_bind)");
+        if (rows > L.cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, L.cfg.max_batch);
+        if (first < 0 || first + rows > b->n_rows) return fail(-1, "rows [%lld, +%d) outside the batch of %lld", first, rows, (long long)b->n_rows);
+        return check_update(p);
+    }
+    int check_apply(const pvae_fc_ppo_params* p, const float* ls_grad) const {
+        if (!c) return fail(-1, "null stack set");
+        if (!p) return fail(-1, "null params");
+        int rc = check_bound();
+        if (rc) return rc;
+        if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
+        if ((p->log_std_kind == 2) != (c->L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, c->L.S);
+        if ((rc = check_update(p))) return rc;
+        const PpoLearner& q = c->ppo;
+        if (p->log_std_kind == 1 && (!q.log_std || !q.log_std_m || !q.log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_fc_ppo_bind)");
+        if (p->log_std_kind == 1 && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+        return 0;
+    }
+
+    int check_eval(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) const;
+
+    int grad_half(const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows, const pvae_fc_ppo_params* p,
+                  int step, int minibatch, float* dpart, hipStream_t st, int* launches) const;
+    int segments(const pvae_fc_ppo_params* p, PpoAdamSegs& sg) const;
+    template <class Epi>
+    int eval_rows(const float* obs, long long n_rows, int k, const pvae_gae_params* p, hipStream_t st, int& launches, Epi&& epi) const;
+    int eval_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st, int& launches) const {
+        return fc_eval_boot(c, 1, c->L.cfg.max_batch, ro, out, st, launches);
+    }
+    int peer_arenas(const void* arg, float** arenas, long long* floats) const {
+        if (!c || !arg) return fail(-1, "null argument");
+        if (!c->ppo.grad) return fail(-2, "pvae_fc_ppo_bind has not been called");
+        arenas[0] = c->ppo.grad; floats[0] = c->L.arena_floats;
+        return 1;
+    }
+};
 
 // The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
 // gradient arena (arguments checked by the caller); `launches` counts what went out; `dpart`: the head's diagnostics partial rows
-int ppo_grad_half(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-                  const pvae_fc_ppo_params* p, float* dpart, hipStream_t st, int* launches) {
+int FcLearner::grad_half(const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows, const pvae_fc_ppo_params* p,
+                         int, int, float* dpart, hipStream_t st, int* launches) const {
     const FcLayout& L = c->L;
     const int mask = p->train_mask ? p->train_mask : (1 << L.S) - 1;
     Run r{c, st, rows, pad32(rows)};
@@ -542,24 +583,25 @@ int ppo_grad_half(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, 
             h.ls = act_ptr(c, 2, ll); h.ld_ls = panel_ld(c, 2, ll); h.ls_base = p->log_std_base;
             if ((mask >> 2) & 1) { h.d_ls = dz_ptr(c, 2, ll); h.ld_dls = panel_ld(c, 2, ll); h.width_dls = L.stack[2][ll].n_out_pad; }
         } else {
-            h.ls = c->log_std; h.ld_ls = 0;
+            h.ls = c->ppo.log_std; h.ld_ls = 0;
         }
         if (mask & 1) { h.d_mean = dz_ptr(c, 0, lp); h.ld_dm = panel_ld(c, 0, lp); h.width_dm = L.stack[0][lp].n_out_pad; }
         if (mask & 2) { h.d_value = dz_ptr(c, 1, lv); h.ld_dv = panel_ld(c, 1, lv); h.width_dv = L.stack[1][lv].n_out_pad; }
-        h.part = c->scratch; h.part_stride = part_stride(b->k, colsum); h.colsum = colsum;
+        h.part = c->ppo.scratch; h.part_stride = part_stride(b->k, colsum); h.colsum = colsum;
         h.dpart = dpart;
         if ((rc = ppo_head_launch(h, st))) return rc;
         ++r.launches;
     }
     for (int s = 0; s < L.S; ++s) r.want[s] = (mask >> s) & 1;
-    if ((rc = run_backward_layers<EpiGradStore>(r, false, c->grad, mask))) return rc;
+    if ((rc = run_backward_layers<EpiGradStore>(r, false, c->ppo.grad, mask))) return rc;
     *launches = r.launches;
     return 0;
 }
 
 // the trained stacks' parts of the arena, in arena order, adjacent ones merged: what the Adam launch runs over
-int ppo_segments(pvae_fc* c, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
+int FcLearner::segments(const pvae_fc_ppo_params* p, PpoAdamSegs& sg) const {
     const FcLayout& L = c->L;
+    const PpoLearner& q = c->ppo;
     const int mask = p->train_mask ? p->train_mask : (1 << L.S) - 1;
     std::vector<std::pair<long long, long long>> seg;
     auto add = [&](long long off, long long n) {
@@ -578,35 +620,14 @@ int ppo_segments(pvae_fc* c, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
     memset((void*)&sg, 0, sizeof(sg));
     for (const auto& e : seg) {
         if (sg.n == kAdamSegs) return fail(-3, "the trained parts of the arena form more than %d segments", kAdamSegs);
-        sg.p[sg.n] = c->params + e.first; sg.g[sg.n] = c->grad + e.first; sg.m[sg.n] = c->m + e.first; sg.v[sg.n] = c->v + e.first;
+        sg.p[sg.n] = c->params + e.first; sg.g[sg.n] = q.grad + e.first; sg.m[sg.n] = q.m + e.first; sg.v[sg.n] = q.v + e.first;
         sg.n4[sg.n++] = e.second / 4;
     }
     return 0;
 }
 
-// one minibatch (arguments checked by the caller): the first half, then the Adam launch -- its exchanged form while a
-// gradient exchange between workers is open (pvae_fc_ppo_peer_open); `diag_step`: the row of a bound diagnostics buffer
-int ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-             const pvae_fc_ppo_params* p, int adam_t, float* stats_out, int diag_step, hipStream_t st) {
-    int launches = 0;
-    const PpoDiagRow dg = diag_row(c->diag, diag_step);
-    int rc = ppo_grad_half(c, b, index, first, rows, p, dg.dpart, st, &launches);
-    if (rc) return rc;
-    PpoAdamSegs sg;
-    if ((rc = ppo_segments(c, p, sg))) return rc;
-    const bool colsum = p->log_std_kind == 1;
-    rc = c->peers.open ? ppo_adam_exchange_launch(c->peers, g_ppo_peer_timeout_ticks, sg, p, adam_t, rows, b->k, c->scratch, colsum,
-                                                  c->log_std, c->log_std_m, c->log_std_v, stats_out, dg, st, &launches)
-                       : ppo_adam_launch(sg, p, adam_t, rows, b->k, c->scratch, colsum, c->log_std, c->log_std_m, c->log_std_v,
-                                         stats_out, dg, st, &launches);
-    if (rc) return rc;
-    c->ppo_launches = launches;
-    return 0;
-}
-
-// ---- train-batch preparation, host side ----
 // what evaluate and prepare ask of the stack set; `rows_pass`: the policy's distribution is evaluated (its log-std is needed)
-int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) {
+int FcLearner::check_eval(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) const {
     if (!c) return fail(-1, "null stack set");
     if (!ro || !p || !out) return fail(-1, "null rollout, params or outputs");
     if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
@@ -620,7 +641,7 @@ int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, 
         if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
         if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
         if (ro->k != L.cfg.n_out[0]) return fail(-1, "rollout k %d != policy outputs %d", ro->k, L.cfg.n_out[0]);
-        if (p->log_std_kind != 2 && !c->log_std) return fail(-2, "log_std vector not bound (pvae_fc_ppo_bind)");
+        if (p->log_std_kind != 2 && !c->ppo.log_std) return fail(-2, "log_std vector not bound (pvae_fc_ppo_bind)");
         if (!ro->obs || !ro->actions) return fail(-1, "rollout obs or actions is null");
         if (!out->vf_preds || !out->old_dist || !out->old_logp) return fail(-1, "an evaluate output (vf_preds, old_dist, old_logp) is null");
     }
@@ -630,8 +651,8 @@ int check_eval(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, 
 // rows [n_rows][n_in] of `obs` through all stacks in chunks of max_batch: copy-in, one launch per depth, then the chunk's
 // epilogue -- epi(panels, first row, chunk index) launches it (the evaluate one, or the sampling one of pvae_fc_ppo_act)
 template <class Epi>
-int eval_rows(pvae_fc* c, const float* obs, long long n_rows, int k, const pvae_gae_params* p, hipStream_t st, int& launches,
-              Epi&& epi) {
+int FcLearner::eval_rows(const float* obs, long long n_rows, int k, const pvae_gae_params* p, hipStream_t st, int& launches,
+                         Epi&& epi) const {
     const FcLayout& L = c->L;
     uint64_t i = 0;
     for (long long first = 0; first < n_rows; first += L.cfg.max_batch, ++i) {
@@ -651,7 +672,7 @@ int eval_rows(pvae_fc* c, const float* obs, long long n_rows, int k, const pvae_
             const int ll = (int)L.stack[2].size() - 1;
             e.ls = act_ptr(c, 2, ll); e.ld_ls = panel_ld(c, 2, ll); e.ls_base = p->log_std_base;
         } else {
-            e.ls = c->log_std; e.ld_ls = 0;
+            e.ls = c->ppo.log_std; e.ld_ls = 0;
         }
         e.rows = rows; e.k = k;
         if ((rc = epi(e, first, i))) return rc;
@@ -659,19 +680,6 @@ int eval_rows(pvae_fc* c, const float* obs, long long n_rows, int k, const pvae_
     }
     return 0;
 }
-int eval_rows(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, hipStream_t st,
-              int& launches) {
-    const int k = ro->k;
-    return eval_rows(c, ro->obs, ro->n_rows, k, p, st, launches, [&](const PpoPanels& pan, long long first, uint64_t) {
-        PpoEval e;
-        memset(&e, 0, sizeof(e));
-        static_cast<PpoPanels&>(e) = pan;
-        e.actions = ro->actions + (size_t)first * k;
-        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
-        return ppo_eval_launch(e, st);
-    });
-}
-
 // one stack alone, as PhysicsVAE's learner and the bootstrap pass run the value function
 Run value_run(pvae_fc* c, int s, int rows, hipStream_t st) {
     Run r{c, st, rows, pad32(rows)};
@@ -688,7 +696,7 @@ Run value_run(pvae_fc* c, int s, int rows, hipStream_t st) {
 int fc_value_stack(pvae_fc* c, FcValueStack* out) {
     if (!c) return fail(-1, "null value stack set");
     if (!c->params || !c->ws) return fail(-2, "value stack set: pvae_fc_bind has not been called");
-    if (!c->grad || !c->m || !c->v) return fail(-2, "value stack set: pvae_fc_ppo_bind has not been called");
+    if (!c->ppo.grad || !c->ppo.m || !c->ppo.v) return fail(-2, "value stack set: pvae_fc_ppo_bind has not been called");
     const FcLayout& L = c->L;
     if (L.S != 1 || L.cfg.n_out[0] != 1) return fail(-1, "the value stack set must be one stack with one output, got %d stacks", L.S);
     const int lv = (int)L.stack[0].size() - 1;
@@ -696,7 +704,7 @@ int fc_value_stack(pvae_fc* c, FcValueStack* out) {
     out->in = c->ws + c->W.in; out->ld_in = L.ld0; out->n_in = L.cfg.n_in;
     out->value = act_ptr(c, 0, lv); out->ld_value = panel_ld(c, 0, lv);
     out->d_value = dz_ptr(c, 0, lv); out->ld_dv = panel_ld(c, 0, lv); out->width_dv = L.stack[0][lv].n_out_pad;
-    out->params = c->params; out->grad = c->grad; out->m = c->m; out->v = c->v;
+    out->params = c->params; out->grad = c->ppo.grad; out->m = c->ppo.m; out->v = c->ppo.v;
     out->arena_floats = L.arena_floats;
     out->max_batch = L.cfg.max_batch;
     for (int i = 0; i <= lv; ++i) {
@@ -716,7 +724,7 @@ int fc_value_forward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches)
 
 int fc_value_backward(pvae_fc* c, int s, int rows, hipStream_t st, int* launches) {
     Run r = value_run(c, s, rows, st);
-    const int rc = run_backward_layers<EpiGradStore>(r, false, c->grad, 1 << s);
+    const int rc = run_backward_layers<EpiGradStore>(r, false, c->ppo.grad, 1 << s);
     *launches += r.launches;
     return rc;
 }
@@ -798,7 +806,7 @@ int pvae_fc_create(const pvae_fc_config* cfg, pvae_fc** out) {
 }
 
 void pvae_fc_destroy(pvae_fc* fc) {
-    if (fc) ppo_peer_free(fc->peers);
+    if (fc) ppo_peer_free(fc->ppo.peers);
     delete fc;
 }
 
@@ -903,37 +911,21 @@ int pvae_fc_ppo_bind(pvae_fc* c, float* grad, float* m, float* v, void* scratch,
     if (scratch_bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
     const int rc = check_ppo_buffers(grad, m, v, scratch, log_std, log_std_m, log_std_v);
     if (rc) return rc;
-    c->grad = grad; c->m = m; c->v = v; c->scratch = (float*)scratch;
-    c->log_std = log_std; c->log_std_m = log_std_m; c->log_std_v = log_std_v;
+    PpoLearner& q = c->ppo;
+    q.grad = grad; q.m = m; q.v = v; q.scratch = (float*)scratch;
+    q.log_std = log_std; q.log_std_m = log_std_m; q.log_std_v = log_std_v;
     return 0;
 }
 
 
 int pvae_fc_ppo_step(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                      const pvae_fc_ppo_params* p, float* stats_out, void* stream) {
-    int rc = check_ppo(c, b, p, first, rows, stats_out);
-    if (rc) return rc;
-    return ppo_step(c, b, index, first, rows, p, p->adam_t, stats_out, 0, (hipStream_t)stream);
+    return learner_step(FcLearner{c}, b, index, first, rows, p, stats_out, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_sgd(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* perm, int32_t minibatch, int32_t num_sgd_iter,
                     const pvae_fc_ppo_params* p, float* stats_out, void* stream) {
-    if (minibatch < 1 || num_sgd_iter < 1) return fail(-1, "minibatch and num_sgd_iter must be positive");
-    int rc = check_ppo(c, b, p, 0, 1, stats_out);
-    if (rc) return rc;
-    if (minibatch > c->L.cfg.max_batch) return fail(-1, "minibatch %d > max_batch %d", minibatch, c->L.cfg.max_batch);
-    const long long steps = num_sgd_iter * ((b->n_rows + minibatch - 1) / minibatch);
-    if (c->diag.out && steps > c->diag.capacity)
-        return fail(-1, "%lld steps, the bound diagnostics buffer holds %d rows", steps, c->diag.capacity);
-    int step = 0;
-    for (int pass = 0; pass < num_sgd_iter; ++pass)
-        for (long long first = 0; first < b->n_rows; first += minibatch, ++step) {
-            const int rows = (int)(b->n_rows - first < minibatch ? b->n_rows - first : minibatch);
-            rc = ppo_step(c, b, perm ? perm + (size_t)pass * b->n_rows : nullptr, first, rows, p, p->adam_t + step,
-                          stats_out + 5 * (size_t)step, step, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-    return 0;
+    return learner_sgd(FcLearner{c}, b, perm, minibatch, num_sgd_iter, p, stats_out, (hipStream_t)stream);
 }
 
 size_t pvae_fc_ppo_diag_bytes(const pvae_fc_config* cfg, int32_t steps) {
@@ -946,131 +938,53 @@ size_t pvae_fc_ppo_diag_bytes(const pvae_fc_config* cfg, int32_t steps) {
 
 int pvae_fc_ppo_diag(pvae_fc* c, float* diag, int32_t capacity_steps, void* scratch, size_t scratch_bytes) {
     if (!c) return fail(-1, "null stack set");
-    return ppo_diag_bind(c->diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
+    return ppo_diag_bind(c->ppo.diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
 }
 
 int pvae_fc_ppo_grad(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                      const pvae_fc_ppo_params* p, float* stats_out, float* ls_grad, void* stream) {
-    int rc = check_ppo(c, b, p, first, rows, stats_out);
-    if (rc) return rc;
-    const bool colsum = p->log_std_kind == 1;
-    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
-    int launches = 0;
-    const PpoDiagRow dg = diag_row(c->diag, 0);
-    if ((rc = ppo_grad_half(c, b, index, first, rows, p, dg.dpart, (hipStream_t)stream, &launches))) return rc;
-    if ((rc = ppo_grad_finish_launch(rows, b->k, c->scratch, colsum, ls_grad, stats_out, dg, (hipStream_t)stream, &launches))) return rc;
-    c->ppo_launches = launches;
-    return 0;
+    return learner_grad(FcLearner{c}, b, index, first, rows, p, stats_out, ls_grad, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_apply(pvae_fc* c, const pvae_fc_ppo_params* p, float grad_scale, const float* ls_grad, void* stream) {
-    if (!c) return fail(-1, "null stack set");
-    if (!p) return fail(-1, "null params");
-    if (!c->params || !c->ws) return fail(-2, "pvae_fc_bind has not been called");
-    if (!c->grad || !c->m || !c->v || !c->scratch) return fail(-2, "pvae_fc_ppo_bind has not been called");
-    const FcLayout& L = c->L;
-    if (p->log_std_kind < 0 || p->log_std_kind > 2) return fail(-1, "log_std_kind %d outside [0, 2]", p->log_std_kind);
-    if ((p->log_std_kind == 2) != (L.S == 3)) return fail(-1, "log_std_kind %d does not fit %d stacks", p->log_std_kind, L.S);
-    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
-    if (p->train_mask < 0 || p->train_mask >= (1 << L.S)) return fail(-1, "train_mask names a stack that does not exist");
-    const bool colsum = p->log_std_kind == 1;
-    if (colsum && (!c->log_std || !c->log_std_m || !c->log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_fc_ppo_bind)");
-    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
-    PpoAdamSegs sg;
-    int rc = ppo_segments(c, p, sg);
-    if (rc) return rc;
-    int launches = 0;
-    if ((rc = ppo_apply_launch(sg, p, p->adam_t, L.cfg.n_out[0], grad_scale, ls_grad, colsum, c->log_std, c->log_std_m, c->log_std_v,
-                               diag_row(c->diag, 0), (hipStream_t)stream, &launches)))
-        return rc;
-    c->ppo_launches = launches;
-    return 0;
+    return learner_apply(FcLearner{c}, p, grad_scale, ls_grad, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_peer_export(pvae_fc* c, void* blob) {
-    if (!c || !blob) return fail(-1, "null argument");
-    if (!c->grad) return fail(-2, "pvae_fc_ppo_bind has not been called");
-    float* arenas[1] = {c->grad};
-    const long long floats[1] = {c->L.arena_floats};
-    return ppo_peer_export(c->peers, arenas, floats, 1, c->L.cfg.n_out[0], blob);
+    return learner_peer_export(FcLearner{c}, blob);
 }
 
 int pvae_fc_ppo_peer_open(pvae_fc* c, int rank, int world, const void* blobs) {
-    if (!c || !blobs) return fail(-1, "null argument");
-    if (!c->grad) return fail(-2, "pvae_fc_ppo_bind has not been called");
-    float* arenas[1] = {c->grad};
-    return ppo_peer_open(c->peers, arenas, rank, world, blobs, g_ppo_peer_timeout_ticks);
+    return learner_peer_open(FcLearner{c}, rank, world, blobs);
 }
 
 int pvae_fc_ppo_peer_close(pvae_fc* c) {
     if (!c) return fail(-1, "null stack set");
-    return ppo_peer_close(c->peers);
+    return ppo_peer_close(c->ppo.peers);
 }
 
 int pvae_fc_ppo_peer_status(pvae_fc* c, int* rank, int* world, uint32_t* timeouts, void* stream) {
     if (!c) return fail(-1, "null stack set");
-    return ppo_peer_status(c->peers, rank, world, timeouts, (hipStream_t)stream);
+    return ppo_peer_status(c->ppo.peers, rank, world, timeouts, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_launches(pvae_fc* c, int32_t* per_step) {
-    if (!c || !per_step) return fail(-1, "null argument");
-    *per_step = c->ppo_launches;
-    return 0;
+    return learner_launches(c ? &c->ppo : nullptr, per_step);
 }
-
 
 int pvae_fc_ppo_evaluate(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
                          void* stream) {
-    const bool rows_pass = out && out->vf_preds, boot = out && out->last_value;
-    int rc = check_eval(c, ro, p, out, rows_pass);
-    if (rc) return rc;
-    if (!rows_pass && !boot) return fail(-1, "neither vf_preds nor last_value: nothing to compute");
-    if (boot && (rc = check_boot(ro, out))) return rc;
-    int ev = 0, rest = 0;
-    if (rows_pass && (rc = eval_rows(c, ro, p, out, (hipStream_t)stream, ev))) return rc;
-    if (boot && (rc = fc_eval_boot(c, 1, c->L.cfg.max_batch, ro, out, (hipStream_t)stream, rest))) return rc;
-    c->eval_launches = ev; c->gae_launches = rest;
-    return 0;
+    return learner_evaluate(FcLearner{c}, ro, p, out, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_prepare(pvae_fc* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out,
                         void* scratch, size_t scratch_bytes, void* stream) {
-    int given = 0;
-    int rc = check_prepare(ro, p, out, scratch, scratch_bytes, &given,
-                           [&](bool rows_pass) { return check_eval(c, ro, p, out, rows_pass); });
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int ev = 0, rest = 0;
-    if (given == 0 && (rc = eval_rows(c, ro, p, out, st, ev))) return rc;
-    if ((rc = fc_eval_boot(c, 1, c->L.cfg.max_batch, ro, out, st, rest))) return rc;
-    // (last_value already holds the zeros of the done segments)
-    if ((rc = run_gae(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, nullptr, ro->seg_start, ro->n_rows,
-                      ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))
-        return rc;
-    c->eval_launches = ev; c->gae_launches = rest;
-    return 0;
+    return learner_prepare(FcLearner{c}, ro, p, out, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 int pvae_fc_ppo_act(pvae_fc* c, const pvae_ppo_act_in* in, const pvae_gae_params* p, const pvae_ppo_act_out* out, void* stream) {
     if (!c) return fail(-1, "null stack set");
-    if (!in || !p || !out) return fail(-1, "null in, params or out");
-    // the model's side of the checks is evaluate's: the same rows, the action column the one written here
-    pvae_fc_rollout ro;
-    pvae_fc_prepared ev;
-    act_as_evaluate(in, out, ro, ev);
-    int rc = check_eval(c, &ro, p, &ev, true);
-    if (rc) return rc;
-    if ((rc = check_act(in, out))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int launches = 0;
-    rc = eval_rows(c, in->obs, in->n_rows, in->k, p, st, launches, [&](const PpoPanels& pan, long long first, uint64_t i) {
-        PpoAct a;
-        fill_act(a, pan, in, out, first, i, c->L.cfg.n_in);
-        return ppo_act_launch(a, st);
-    });
-    if (rc) return rc;
-    c->eval_launches = launches; c->gae_launches = 0;
-    return 0;
+    return learner_act(FcLearner{c}, in, p, out, (hipStream_t)stream);
 }
 
 int pvae_ppo_act_sizeof(int which) {
@@ -1080,9 +994,7 @@ int pvae_ppo_act_sizeof(int which) {
 
 int pvae_fc_gae_launches(pvae_fc* c, int32_t* evaluate, int32_t* rest) {
     if (!c) return fail(-1, "null stack set");
-    if (evaluate) *evaluate = c->eval_launches;
-    if (rest) *rest = c->gae_launches;
-    return 0;
+    return learner_gae_launches(c->ppo, evaluate, rest);
 }
 
 }  // extern "C"

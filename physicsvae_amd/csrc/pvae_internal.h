@@ -9,11 +9,12 @@
 //                            the set-up of the PPO learners' gradient exchange between workers
 //   pvae_rollout_server.hip  the call-persistent rollout server
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
-//   pvae_fc.hip              the stack set, and its PPO learner step and train-batch preparation on the launches of pvae_ppo_core.hip
+//   pvae_fc.hip              the stack set, and what its PPO learner runs of it: the model adapter of pvae_ppo_learner.h
 //   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats and its
 //                            two-halves and exchanged forms, evaluate epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
-//   pvae_ppo.hip             the PPO learner step of PhysicsVAE and its train-batch preparation: join the launches of pvae_infer.hip,
-//                            pvae_fc.hip and pvae_ppo_core.hip
+//   pvae_ppo.hip             what PhysicsVAE's PPO learner runs of pvae_infer.hip and pvae_fc.hip: its model adapter
+//   pvae_ppo_learner.h       the PPO learner's host driver, once for both models: step, sgd loop, the two halves, exchange set-up,
+//                            evaluate, prepare and act, as function templates over a unit's model adapter
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -197,6 +198,18 @@ inline PpoDiagRow diag_row(const PpoDiag& d, long long step) {
     return d.out ? PpoDiagRow{d.out + step * PVAE_PPO_DIAG, d.gslot, d.dpart} : PpoDiagRow{nullptr, nullptr, nullptr};
 }
 
+// What a PPO learner keeps, whichever model it trains (the stack set: in pvae_fc; PhysicsVAE: pvae_ctx::ppo): what *_ppo_bind
+// bound, the launch counts of the last calls, the exchange and the diagnostics binding.  Its host driver: pvae_ppo_learner.h.
+struct PpoLearner {
+    float* grad = nullptr; float* m = nullptr; float* v = nullptr;
+    float* scratch = nullptr;
+    float* log_std = nullptr; float* log_std_m = nullptr; float* log_std_v = nullptr;
+    int launches = 0;                                    // *_ppo_launches
+    int eval_launches = 0, gae_launches = 0;             // *_gae_launches
+    PpoPeers peers;                                      // gradient exchange between workers (*_ppo_peer_*)
+    PpoDiag diag;                                        // learner diagnostics (*_ppo_diag)
+};
+
 struct pvae_ctx {
     void* comm = nullptr;        // ncclComm_t of the data-parallel group (pvae_comm_init)
     int comm_rank = 0, comm_world = 1;
@@ -283,18 +296,9 @@ struct pvae_ctx {
     hipStream_t param_stream = nullptr;                  // (NULL is a stream too: the default one.  The caller's stream must
                                                          //  outlive the writes it queued, as for any other call here.)
     bool param_pending = false;                          // work that writes the parameters may still be queued on it
-    // PPO learner step (pvae_ppo_bind): gradient and moment arenas of the parameter arena's layout -- not the supervised
-    // trainer's grads / m / v above --, the head's scratch, the log-std vector and the stack set of the value branch
-    struct Ppo {
-        float* grad = nullptr; float* m = nullptr; float* v = nullptr;
-        float* scratch = nullptr;
-        float* log_std = nullptr; float* log_std_m = nullptr; float* log_std_v = nullptr;
-        pvae_fc* value = nullptr;
-        int launches = 0;
-        int eval_launches = 0, gae_launches = 0;         // pvae_ppo_prepare / pvae_ppo_evaluate (pvae_ppo_gae_launches)
-        PpoPeers peers;                                  // the learner's gradient exchange between workers (pvae_ppo_peer_*)
-        PpoDiag diag;                                    // learner diagnostics (pvae_ppo_diag)
-    } ppo;
+    // PPO learner (pvae_ppo_bind): its gradient and moment arenas have the parameter arena's layout -- they are not the
+    // supervised trainer's grads / m / v above --, and the value branch is a stack set of its own
+    struct Ppo : PpoLearner { pvae_fc* value = nullptr; } ppo;
 };
 static inline void params_touched(pvae_ctx* c, hipStream_t st, bool queued = true) {
     // one stream is remembered: writes still queued on ANOTHER one are drained here (a caller that switches streams with

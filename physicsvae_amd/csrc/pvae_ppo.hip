@@ -12,7 +12,10 @@
 // max_batch rows with the evaluate epilogue in place of the loss head, then the value stack's bootstrap pass and the GAE and
 // standardise launches.  Launch order of a chunk:
 //   copy-in | TE layers | sampler | MD layers | value layers | epilogue
+// The sequence of a call -- sgd loop, Adam launch, evaluate / prepare / act -- is the host driver's (pvae_ppo_learner.h);
+// this unit gives it VaeLearner, the model adapter: PhysicsVAE's checks, first half, Adam segments and chunked rows pass.
 #include "pvae_internal.h"
+#include "pvae_ppo_learner.h"
 
 namespace {
 
@@ -100,36 +103,103 @@ int check_ppo_config(const pvae_config& cfg) {
     return 0;
 }
 
-int check_ppo(pvae_ctx* c, const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows,
-              const float* stats, FcValueStack* vs) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    const pvae_ctx::Ppo& q = c->ppo;
-    if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
-    if ((rc = check_loss_args(b, p, rows))) return rc;
-    if (!b->obs) return fail(-1, "batch obs is null");
-    if (!stats) return fail(-1, "stats_out is null");
-    const pvae_config& cfg = c->L.cfg;
-    if ((rc = check_ppo_config(cfg))) return rc;
-    if (p->log_std_kind != 0 && p->log_std_kind != 1) return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
-    if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
-    if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_ppo_bind)");
-    if (b->k != cfg.dim_action) return fail(-1, "batch k %d != dim_action %d", b->k, cfg.dim_action);
-    if (rows > cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, cfg.max_batch);
-    if (first < 0 || first + rows > b->n_rows) return fail(-1, "rows [%lld, +%d) outside the batch of %lld", first, rows, (long long)b->n_rows);
-    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
-    if (p->train_mask < 0 || p->train_mask > 7) return fail(-1, "train_mask names a net that does not exist (bits: 1 TE, 2 MD, 4 value)");
-    if ((rc = fc_value_stack(q.value, vs))) return rc;
-    if (vs->n_in != 2 * cfg.dim_body) return fail(-1, "the value stack reads %d inputs, the observation has %d", vs->n_in, 2 * cfg.dim_body);
-    if (rows > vs->max_batch) return fail(-1, "rows %d > max_batch %d of the value stack set", rows, vs->max_batch);
-    return 0;
-}
+// ---- the PPO learner and its train-batch preparation: PhysicsVAE as the driver (pvae_ppo_learner.h) sees it ----
+// The context, the value stack set as the checks resolved it, and the latent draws of the call: a step's (`eps`, `noise`,
+// `seed`, `offset`), or an evaluate pass's (`draws`).
+struct VaeLearner {
+    pvae_ctx* c;
+    const pvae_ppo_draws* draws = nullptr;
+    const float* eps = nullptr; int noise = 0; uint64_t seed = 0, offset = 0;
+    FcValueStack vs{};
+    PpoLearner* learner() const { return c ? &c->ppo : nullptr; }
+    int k() const { return c->L.cfg.dim_action; }
+    int n_in() const { return vs.n_in; }
+    int max_minibatch() const { return std::min(c->L.cfg.max_batch, vs.max_batch); }
+    long long peer_timeout() const { return c->p2p.timeout_ticks; }
+    void params_written(hipStream_t st) const { params_touched(c, st); }
+    float* eps_out() const { return draws ? draws->eps_out : nullptr; }
+
+    // the checks of a step in their order; check_bound, check_kind and check_update are the parts the second half shares
+    int check_bound() const {
+        const int rc = check_ready(c, true);
+        if (rc) return rc;
+        const pvae_ctx::Ppo& q = c->ppo;
+        if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
+        return 0;
+    }
+    int check_kind(int log_std_kind) const {
+        if (log_std_kind != 0 && log_std_kind != 1)
+            return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", log_std_kind);
+        return 0;
+    }
+    int check_update(const pvae_fc_ppo_params* p) const {
+        if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
+        if (p->train_mask < 0 || p->train_mask > 7) return fail(-1, "train_mask names a net that does not exist (bits: 1 TE, 2 MD, 4 value)");
+        return 0;
+    }
+    int check_value_stack(pvae_fc* value) {
+        const int rc = fc_value_stack(value, &vs);
+        if (rc) return rc;
+        const int n_obs = 2 * c->L.cfg.dim_body;
+        if (vs.n_in != n_obs) return fail(-1, "the value stack reads %d inputs, the observation has %d", vs.n_in, n_obs);
+        return 0;
+    }
+    int check_step(const pvae_fc_ppo_batch* b, const pvae_fc_ppo_params* p, long long first, int rows, const float* stats) {
+        int rc = check_bound();
+        if (rc) return rc;
+        const pvae_ctx::Ppo& q = c->ppo;
+        if ((rc = check_loss_args(b, p, rows))) return rc;
+        if (!b->obs) return fail(-1, "batch obs is null");
+        if (!stats) return fail(-1, "stats_out is null");
+        const pvae_config& cfg = c->L.cfg;
+        if ((rc = check_ppo_config(cfg)) || (rc = check_kind(p->log_std_kind))) return rc;
+        if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
+        if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_ppo_bind)");
+        if (b->k != cfg.dim_action) return fail(-1, "batch k %d != dim_action %d", b->k, cfg.dim_action);
+        if (rows > cfg.max_batch) return fail(-1, "rows %d outside [1, %d]", rows, cfg.max_batch);
+        if (first < 0 || first + rows > b->n_rows) return fail(-1, "rows [%lld, +%d) outside the batch of %lld", first, rows, (long long)b->n_rows);
+        if ((rc = check_update(p)) || (rc = check_value_stack(q.value))) return rc;
+        if (rows > vs.max_batch) return fail(-1, "rows %d > max_batch %d of the value stack set", rows, vs.max_batch);
+        return 0;
+    }
+    int check_apply(const pvae_fc_ppo_params* p, const float* ls_grad) {
+        int rc = check_ready(c, true);
+        if (rc) return rc;
+        if (!p) return fail(-1, "null params");
+        if ((rc = check_bound()) || (rc = check_kind(p->log_std_kind)) || (rc = check_update(p))) return rc;
+        const pvae_ctx::Ppo& q = c->ppo;
+        if (p->log_std_kind == 1 && (!q.log_std || !q.log_std_m || !q.log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_ppo_bind)");
+        if (p->log_std_kind == 1 && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
+        return fc_value_stack(q.value, &vs);
+    }
+    int check_eval(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass);
+
+    int grad_half(const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows, const pvae_fc_ppo_params* p,
+                  int step, int minibatch, float* dpart, hipStream_t st, int* launches_out) const;
+    int segments(const pvae_fc_ppo_params* p, PpoAdamSegs& sg) const;
+    template <class Epi>
+    int eval_rows(const float* obs, long long n_rows, int k, const pvae_gae_params*, hipStream_t st, int& launches, Epi&& epi) const;
+    int eval_boot(const pvae_fc_rollout* ro, const pvae_fc_prepared* out, hipStream_t st, int& launches) const {
+        return fc_eval_boot(c->ppo.value, 0, max_minibatch(), ro, out, st, launches);
+    }
+    // the learner's two gradient arenas as the exchange maps them: the one of pvae_ppo_bind, and the value stack set's
+    int peer_arenas(const void*, float** arenas, long long* floats) {
+        if (!c) return fail(-1, "null ctx");
+        const pvae_ctx::Ppo& q = c->ppo;
+        if (!q.grad || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
+        const int rc = fc_value_stack(q.value, &vs);
+        if (rc) return rc;
+        arenas[0] = q.grad; floats[0] = c->L.arena_floats;
+        arenas[1] = vs.grad; floats[1] = vs.arena_floats;
+        return 2;
+    }
+};
 
 // The first half of a minibatch's step, everything before the Adam launch: forward, loss head, backward into the bound
-// gradient arenas (arguments checked by the caller); `launches_out` counts what went out
-int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t seed, uint64_t offset, float* dpart,
-                  hipStream_t st, int* launches_out) {
+// gradient arenas (arguments checked by the caller); `launches_out` counts what went out.  Step `step` of a call draws
+// from eps + step * minibatch * Z, or from Philox at offset + step.
+int VaeLearner::grad_half(const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows, const pvae_fc_ppo_params* p,
+                          int step, int minibatch, float* dpart, hipStream_t st, int* launches_out) const {
     const pvae_ctx::Ppo& q = c->ppo;
     const pvae_config& cfg = c->L.cfg;
     const int Db = cfg.dim_body, Z = cfg.latent;
@@ -156,7 +226,8 @@ int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* 
         ++launches;
     }
     if ((rc = ppo_forward_net(c, PVAE_NET_TE, rows, st, &launches))) return rc;
-    if ((rc = ppo_sampler(c, eps, rows, noise, seed, offset, st, &launches))) return rc;
+    if ((rc = ppo_sampler(c, eps ? eps + (size_t)minibatch * Z * step : nullptr, rows, noise, seed, offset + (uint64_t)step, st, &launches)))
+        return rc;
     if ((rc = ppo_forward_net(c, PVAE_NET_MD, rows, st, &launches))) return rc;
     if ((rc = fc_value_forward(q.value, 0, rows, st, &launches))) return rc;
     const Layer& md_last = MD.layers.back();
@@ -193,7 +264,7 @@ int ppo_grad_half(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* 
 }
 
 // the trained nets' segments: what the Adam launch runs over (TE, MD: their parts of the arena; value: its own arena)
-void ppo_segments(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_params* p, PpoAdamSegs& sg) {
+int VaeLearner::segments(const pvae_fc_ppo_params* p, PpoAdamSegs& sg) const {
     const pvae_ctx::Ppo& q = c->ppo;
     const int mask = p->train_mask ? p->train_mask : 7;
     const NetLayout& TE = c->L.net[PVAE_NET_TE];
@@ -205,34 +276,13 @@ void ppo_segments(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_params*
     if (mask & kTrainTE) add(c->params + TE.off, q.grad + TE.off, q.m + TE.off, q.v + TE.off, TE.count);
     if (mask & kTrainMD) add(c->params + MD.off, q.grad + MD.off, q.m + MD.off, q.v + MD.off, MD.count);
     if (mask & kTrainValue) add(vs.params, vs.grad, vs.m, vs.v, vs.arena_floats);
-}
-
-// one minibatch (arguments checked by the caller): the first half, then the Adam launch -- its exchanged form while a
-// gradient exchange between workers is open (pvae_ppo_peer_open)
-int ppo_step(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_ppo_batch* b, const int32_t* index, long long first, int rows,
-             const pvae_fc_ppo_params* p, int adam_t, const float* eps, int noise, uint64_t seed, uint64_t offset,
-             float* stats_out, int diag_step, hipStream_t st) {
-    pvae_ctx::Ppo& q = c->ppo;
-    int launches = 0;
-    const PpoDiagRow dg = diag_row(q.diag, diag_step);       // the row of a bound diagnostics buffer
-    int rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, seed, offset, dg.dpart, st, &launches);
-    if (rc) return rc;
-    PpoAdamSegs sg;
-    ppo_segments(c, vs, p, sg);
-    const int colsum = p->log_std_kind == 1;
-    rc = q.peers.open ? ppo_adam_exchange_launch(q.peers, c->p2p.timeout_ticks, sg, p, adam_t, rows, b->k, q.scratch, colsum,
-                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, dg, st, &launches)
-                      : ppo_adam_launch(sg, p, adam_t, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m, q.log_std_v,
-                                        stats_out, dg, st, &launches);
-    if (rc) return rc;
-    q.launches = launches;
     return 0;
 }
 
 // ---- train-batch preparation (include/pvae.h "Train-batch preparation for PhysicsVAE") ----
 // what evaluate and prepare ask of the context; `rows_pass`: the policy's distribution is evaluated over the rows
-int check_eval(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
-               const pvae_fc_prepared* out, bool rows_pass, FcValueStack* vs) {
+int VaeLearner::check_eval(const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_fc_prepared* out, bool rows_pass) {
+    const pvae_ppo_draws* d = draws;
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (!ro || !p || !out) return fail(-1, "null rollout, params or outputs");
@@ -242,8 +292,7 @@ int check_eval(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p,
     if ((rc = check_ppo_config(cfg))) return rc;
     if (ro->n_rows < 1 || ro->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)ro->n_rows);
     if (rows_pass) {
-        if (p->log_std_kind != 0 && p->log_std_kind != 1)
-            return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
+        if ((rc = check_kind(p->log_std_kind))) return rc;
         if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
         if (ro->k != cfg.dim_action) return fail(-1, "rollout k %d != dim_action %d", ro->k, cfg.dim_action);
         if (!ro->obs || !ro->actions) return fail(-1, "rollout obs or actions is null");
@@ -251,21 +300,18 @@ int check_eval(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p,
         if (!d) return fail(-1, "draws is null");
         if (d->noise != 0 && d->noise != 1) return fail(-1, "draws noise must be 0 or 1, got %d", d->noise);
     }
-    if ((rc = fc_value_stack(q.value, vs))) return rc;
-    if (vs->n_in != 2 * cfg.dim_body) return fail(-1, "the value stack reads %d inputs, the observation has %d", vs->n_in, 2 * cfg.dim_body);
-    return 0;
+    return check_value_stack(q.value);
 }
-
-int eval_chunk(const pvae_ctx* c, const FcValueStack& vs) { return std::min(c->L.cfg.max_batch, vs.max_batch); }
 
 // rows [n_rows][2 Db] of `obs` through encoder, sampler, decoder and value stack in chunks of max_batch:
 // copy-in | TE layers | sampler | MD layers | value layers | the chunk's epilogue -- epi(panels, first row, chunk index)
 // launches it (the evaluate one, or the sampling one of pvae_ppo_act)
 template <class Epi>
-int eval_rows(pvae_ctx* c, const FcValueStack& vs, const float* obs, long long n_rows, int k, const pvae_ppo_draws* d,
-              hipStream_t st, int& launches, Epi&& epi) {
+int VaeLearner::eval_rows(const float* obs, long long n_rows, int k, const pvae_gae_params*, hipStream_t st, int& launches,
+                          Epi&& epi) const {
     const pvae_config& cfg = c->L.cfg;
-    const int Z = cfg.latent, chunk = eval_chunk(c, vs);
+    const pvae_ppo_draws* d = draws;
+    const int Z = cfg.latent, chunk = max_minibatch();
     const Layer& md_last = c->L.net[PVAE_NET_MD].layers.back();
     uint64_t i = 0;
     for (long long first = 0; first < n_rows; first += chunk, ++i) {
@@ -292,20 +338,6 @@ int eval_rows(pvae_ctx* c, const FcValueStack& vs, const float* obs, long long n
     }
     return 0;
 }
-int eval_rows(pvae_ctx* c, const FcValueStack& vs, const pvae_fc_rollout* ro, const pvae_ppo_draws* d,
-              const pvae_fc_prepared* out, hipStream_t st, int& launches) {
-    const int k = ro->k;
-    return eval_rows(c, vs, ro->obs, ro->n_rows, k, d, st, launches, [&](const PpoPanels& pan, long long first, uint64_t) {
-        PpoEval e;
-        memset(&e, 0, sizeof(e));
-        static_cast<PpoPanels&>(e) = pan;
-        e.actions = ro->actions + (size_t)first * k;
-        e.vf = out->vf_preds + first; e.dist = out->old_dist + (size_t)first * 2 * k; e.logp = out->old_logp + first;
-        if (d->eps_out) e.eps_dst = d->eps_out + (size_t)first * pan.Z;
-        return ppo_eval_launch(e, st);
-    });
-}
-
 }  // namespace
 
 extern "C" {
@@ -330,10 +362,7 @@ int pvae_ppo_bind(pvae_ctx* c, float* grad, float* m, float* v, void* scratch, s
     if (bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", bytes, need);
     int rc = check_ppo_buffers(grad, m, v, scratch, log_std, log_std_m, log_std_v);
     if (rc) return rc;
-    FcValueStack vs;
-    if ((rc = fc_value_stack(value, &vs))) return rc;
-    if (vs.n_in != 2 * c->L.cfg.dim_body)
-        return fail(-1, "the value stack reads %d inputs, the observation has %d", vs.n_in, 2 * c->L.cfg.dim_body);
+    if ((rc = VaeLearner{c}.check_value_stack(value))) return rc;
     pvae_ctx::Ppo& q = c->ppo;
     q.grad = grad; q.m = m; q.v = v; q.scratch = (float*)scratch;
     q.log_std = log_std; q.log_std_m = log_std_m; q.log_std_v = log_std_v;
@@ -344,39 +373,15 @@ int pvae_ppo_bind(pvae_ctx* c, float* grad, float* m, float* v, void* scratch, s
 int pvae_ppo_step(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                   const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
                   float* stats_out, void* stream) {
-    FcValueStack vs;
-    int rc = check_ppo(c, b, p, first, rows, stats_out, &vs);
-    if (rc) return rc;
-    if ((rc = ppo_step(c, vs, b, index, first, rows, p, p->adam_t, eps, noise, rng_seed, rng_offset, stats_out, 0, (hipStream_t)stream)))
-        return rc;
-    params_touched(c, (hipStream_t)stream);
-    return 0;
+    return learner_step(VaeLearner{c, nullptr, eps, noise, rng_seed, rng_offset}, b, index, first, rows, p, stats_out,
+                        (hipStream_t)stream);
 }
 
 int pvae_ppo_sgd(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* perm, int32_t minibatch, int32_t num_sgd_iter,
                  const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
                  float* stats_out, void* stream) {
-    if (minibatch < 1 || num_sgd_iter < 1) return fail(-1, "minibatch and num_sgd_iter must be positive");
-    FcValueStack vs;
-    int rc = check_ppo(c, b, p, 0, 1, stats_out, &vs);
-    if (rc) return rc;
-    if (minibatch > c->L.cfg.max_batch || minibatch > vs.max_batch)
-        return fail(-1, "minibatch %d > max_batch %d", minibatch, std::min(c->L.cfg.max_batch, vs.max_batch));
-    const long long steps = num_sgd_iter * ((b->n_rows + minibatch - 1) / minibatch);
-    if (c->ppo.diag.out && steps > c->ppo.diag.capacity)
-        return fail(-1, "%lld steps, the bound diagnostics buffer holds %d rows", steps, c->ppo.diag.capacity);
-    const size_t eps_step = (size_t)minibatch * c->L.cfg.latent;
-    int step = 0;
-    for (int pass = 0; pass < num_sgd_iter; ++pass)
-        for (long long first = 0; first < b->n_rows; first += minibatch, ++step) {
-            const int rows = (int)(b->n_rows - first < minibatch ? b->n_rows - first : minibatch);
-            rc = ppo_step(c, vs, b, perm ? perm + (size_t)pass * b->n_rows : nullptr, first, rows, p, p->adam_t + step,
-                          eps ? eps + eps_step * step : nullptr, noise, rng_seed, rng_offset + (uint64_t)step,
-                          stats_out + 5 * (size_t)step, step, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-    params_touched(c, (hipStream_t)stream);
-    return 0;
+    return learner_sgd(VaeLearner{c, nullptr, eps, noise, rng_seed, rng_offset}, b, perm, minibatch, num_sgd_iter, p, stats_out,
+                       (hipStream_t)stream);
 }
 
 size_t pvae_ppo_diag_bytes(pvae_ctx* c, int32_t steps) {
@@ -393,73 +398,20 @@ int pvae_ppo_diag(pvae_ctx* c, float* diag, int32_t capacity_steps, void* scratc
 int pvae_ppo_grad(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                   const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
                   float* stats_out, float* ls_grad, void* stream) {
-    FcValueStack vs;
-    int rc = check_ppo(c, b, p, first, rows, stats_out, &vs);
-    if (rc) return rc;
-    const int colsum = p->log_std_kind == 1;
-    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
-    int launches = 0;
-    const PpoDiagRow dg = diag_row(c->ppo.diag, 0);
-    if ((rc = ppo_grad_half(c, vs, b, index, first, rows, p, eps, noise, rng_seed, rng_offset, dg.dpart, (hipStream_t)stream, &launches)))
-        return rc;
-    if ((rc = ppo_grad_finish_launch(rows, b->k, c->ppo.scratch, colsum, ls_grad, stats_out, dg, (hipStream_t)stream, &launches)))
-        return rc;
-    c->ppo.launches = launches;
-    return 0;
+    return learner_grad(VaeLearner{c, nullptr, eps, noise, rng_seed, rng_offset}, b, index, first, rows, p, stats_out, ls_grad,
+                        (hipStream_t)stream);
 }
 
 int pvae_ppo_apply(pvae_ctx* c, const pvae_fc_ppo_params* p, float grad_scale, const float* ls_grad, void* stream) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (!p) return fail(-1, "null params");
-    const pvae_ctx::Ppo& q = c->ppo;
-    if (!q.grad || !q.m || !q.v || !q.scratch || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
-    if (p->log_std_kind != 0 && p->log_std_kind != 1) return fail(-1, "log_std_kind %d: PhysicsVAE has a constant (0) or state_independent (1) log-std", p->log_std_kind);
-    if (p->adam_t < 1) return fail(-1, "adam_t must be >= 1");
-    if (p->train_mask < 0 || p->train_mask > 7) return fail(-1, "train_mask names a net that does not exist (bits: 1 TE, 2 MD, 4 value)");
-    const int colsum = p->log_std_kind == 1;
-    if (colsum && (!q.log_std || !q.log_std_m || !q.log_std_v)) return fail(-2, "log_std vector or its moments not bound (pvae_ppo_bind)");
-    if (colsum && !ls_grad) return fail(-1, "ls_grad is null (log_std_kind 1)");
-    FcValueStack vs;
-    if ((rc = fc_value_stack(q.value, &vs))) return rc;
-    PpoAdamSegs sg;
-    ppo_segments(c, vs, p, sg);
-    int launches = 0;
-    if ((rc = ppo_apply_launch(sg, p, p->adam_t, c->L.cfg.dim_action, grad_scale, ls_grad, colsum, q.log_std, q.log_std_m,
-                               q.log_std_v, diag_row(q.diag, 0), (hipStream_t)stream, &launches)))
-        return rc;
-    c->ppo.launches = launches;
-    params_touched(c, (hipStream_t)stream);
-    return 0;
-}
-
-// the learner's two gradient arenas as the exchange maps them: the one of pvae_ppo_bind, and the value stack set's
-static int ppo_peer_arenas(pvae_ctx* c, float** arenas, long long* floats) {
-    if (!c) return fail(-1, "null ctx");
-    const pvae_ctx::Ppo& q = c->ppo;
-    if (!q.grad || !q.value) return fail(-2, "pvae_ppo_bind has not been called");
-    FcValueStack vs;
-    const int rc = fc_value_stack(q.value, &vs);
-    if (rc) return rc;
-    arenas[0] = q.grad; floats[0] = c->L.arena_floats;
-    arenas[1] = vs.grad; floats[1] = vs.arena_floats;
-    return 0;
+    return learner_apply(VaeLearner{c}, p, grad_scale, ls_grad, (hipStream_t)stream);
 }
 
 int pvae_ppo_peer_export(pvae_ctx* c, void* blob) {
-    float* arenas[2];
-    long long floats[2];
-    const int rc = ppo_peer_arenas(c, arenas, floats);
-    if (rc) return rc;
-    return ppo_peer_export(c->ppo.peers, arenas, floats, 2, c->L.cfg.dim_action, blob);
+    return learner_peer_export(VaeLearner{c}, blob);
 }
 
 int pvae_ppo_peer_open(pvae_ctx* c, int rank, int world, const void* blobs) {
-    float* arenas[2];
-    long long floats[2];
-    const int rc = ppo_peer_arenas(c, arenas, floats);
-    if (rc) return rc;
-    return ppo_peer_open(c->ppo.peers, arenas, rank, world, blobs, c->p2p.timeout_ticks);
+    return learner_peer_open(VaeLearner{c}, rank, world, blobs);
 }
 
 int pvae_ppo_peer_close(pvae_ctx* c) {
@@ -473,77 +425,27 @@ int pvae_ppo_peer_status(pvae_ctx* c, int* rank, int* world, uint32_t* timeouts,
 }
 
 int pvae_ppo_launches(pvae_ctx* c, int32_t* per_step) {
-    if (!c || !per_step) return fail(-1, "null argument");
-    *per_step = c->ppo.launches;
-    return 0;
+    return learner_launches(c ? &c->ppo : nullptr, per_step);
 }
 
 int pvae_ppo_evaluate(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
                       const pvae_fc_prepared* out, void* stream) {
-    const bool rows_pass = out && out->vf_preds, boot = out && out->last_value;
-    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
-    FcValueStack vs;
-    int rc = check_eval(c, ro, p, d, out, rows_pass, &vs);
-    if (rc) return rc;
-    if (!rows_pass && !boot) return fail(-1, "neither vf_preds nor last_value: nothing to compute");
-    if (boot && (rc = check_boot(ro, out))) return rc;
-    int ev = 0, rest = 0;
-    if (rows_pass && (rc = eval_rows(c, vs, ro, d, out, (hipStream_t)stream, ev))) return rc;
-    if (boot && (rc = fc_eval_boot(c->ppo.value, 0, eval_chunk(c, vs), ro, out, (hipStream_t)stream, rest))) return rc;
-    c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
-    return 0;
+    return learner_evaluate(VaeLearner{c, d}, ro, p, out, (hipStream_t)stream);
 }
 
 int pvae_ppo_prepare(pvae_ctx* c, const pvae_fc_rollout* ro, const pvae_gae_params* p, const pvae_ppo_draws* d,
                      const pvae_fc_prepared* out, void* scratch, size_t scratch_bytes, void* stream) {
-    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
-    FcValueStack vs;
-    int given = 0;
-    int rc = check_prepare(ro, p, out, scratch, scratch_bytes, &given,
-                           [&](bool rows_pass) { return check_eval(c, ro, p, d, out, rows_pass, &vs); });
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int ev = 0, rest = 0;
-    if (given == 0 && (rc = eval_rows(c, vs, ro, d, out, st, ev))) return rc;
-    if ((rc = fc_eval_boot(c->ppo.value, 0, eval_chunk(c, vs), ro, out, st, rest))) return rc;
-    // (last_value already holds the zeros of the done segments)
-    if ((rc = run_gae(ro->rewards, given ? ro->vf_preds : out->vf_preds, out->last_value, nullptr, ro->seg_start, ro->n_rows,
-                      ro->n_segs, p, out->advantages, out->value_targets, scratch, st, rest)))
-        return rc;
-    c->ppo.eval_launches = ev; c->ppo.gae_launches = rest;
-    return 0;
+    return learner_prepare(VaeLearner{c, d}, ro, p, out, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 int pvae_ppo_act(pvae_ctx* c, const pvae_ppo_act_in* in, const pvae_gae_params* p, const pvae_ppo_draws* d,
                  const pvae_ppo_act_out* out, void* stream) {
-    if (c) c->ppo.eval_launches = c->ppo.gae_launches = 0;          // a refused call reports that it launched nothing
-    if (!in || !p || !out) return fail(-1, "null in, params or out");
-    // the model's side of the checks is evaluate's: the same rows, the action column the one written here
-    pvae_fc_rollout ro;
-    pvae_fc_prepared ev;
-    act_as_evaluate(in, out, ro, ev);
-    FcValueStack vs;
-    int rc = check_eval(c, &ro, p, d, &ev, true, &vs);
-    if (rc) return rc;
-    if ((rc = check_act(in, out))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int launches = 0;
-    rc = eval_rows(c, vs, in->obs, in->n_rows, in->k, d, st, launches, [&](const PpoPanels& pan, long long first, uint64_t i) {
-        PpoAct a;
-        fill_act(a, pan, in, out, first, i, vs.n_in);
-        a.eps_dst = d->eps_out;
-        return ppo_act_launch(a, st);
-    });
-    if (rc) return rc;
-    c->ppo.eval_launches = launches;
-    return 0;
+    return learner_act(VaeLearner{c, d}, in, p, out, (hipStream_t)stream);
 }
 
 int pvae_ppo_gae_launches(pvae_ctx* c, int32_t* evaluate, int32_t* rest) {
     if (!c) return fail(-1, "null ctx");
-    if (evaluate) *evaluate = c->ppo.eval_launches;
-    if (rest) *rest = c->ppo.gae_launches;
-    return 0;
+    return learner_gae_launches(c->ppo, evaluate, rest);
 }
 
 }  // extern "C"

@@ -284,6 +284,128 @@ class PpoSurface:
         return e.value, r.value
 
 
+class PpoPolicy:
+    """The PPO learner surface of a model, written once: `FullyConnectedPolicy` and `PhysicsVAE` both mix it in and keep
+    the public methods (`ppo_learn`, `ppo_prepare`, `compute_actions`: their signatures and docstrings differ) as one-line
+    calls of the `_policy_*` bodies here.  What the model class supplies (`call`: "learn", "prepare" or "act"):
+
+        engine, _ppo_stacks()      a `PpoSurface`; the (name, FC stack) pairs a train mask has a bit for, in bit order
+        _ppo_refusals()            what prepare, act and the data-parallel state refuse first (default: nothing)
+        _ppo_learn_mask(config)    a learn call's refusals, in the class's own order -> `train_mask` of the step params
+        _ppo_bind_engine()         bind the learner's buffers -> (log-std kind, base, the vector is trained)
+        _ppo_draws(call, eps, dp_shape=None)    the draw keywords of the engine's call; `dp_shape` = (steps, minibatch):
+                                   the torch transport takes supplied draws as one tensor
+        _ppo_after(call, n)        n steps or chunks drew at the module's RNG counter; the last forward's results are gone
+        _ppo_dp_tensors(train_ls)  what `PPODataParallel.attach` copies from rank 0, after `_ppo_bind_engine`
+        _PPO_PARTIAL_SAMPLER       prepare hands the sampler's columns on when only some are there (the library refuses them)
+    """
+
+    _PPO_PARTIAL_SAMPLER = False
+
+    def _ppo_refusals(self):
+        pass
+
+    def _ppo_train_mask(self):
+        """Bit s: stack s of `_ppo_stacks()` is trained.  Each is trained or frozen as a whole."""
+        from . import autograd as AG
+        mask = 0
+        for s, (name, fn) in enumerate(self._ppo_stacks()):
+            flags = [p.requires_grad for p in AG.stack_params(fn)]
+            if any(flags) and not all(flags):
+                raise NotImplementedError("%s is partially frozen: the fused PPO step trains or freezes a stack as a whole"
+                                          % name)
+            mask |= (1 << s) if all(flags) else 0
+        return mask
+
+    def _policy_learn(self, batch, config, perm, eps, dp, diag_out):
+        from . import ppo as P
+        eng = self.engine
+        train_mask = self._ppo_learn_mask(config)
+        kind, base, train_ls = self._ppo_bind_engine()
+        if kind == "state_independent" and not train_ls:
+            kind = "constant"                    # a frozen vector is a constant one to the step
+        cols = eng.ppo_batch(P.batch_columns(batch))
+        n = int(cols[0].n_rows)
+        t = self.__dict__.get("_ppo_t", 0)
+        params = config.params(kind, base, adam_t=t + 1, train_mask=train_mask)
+        if perm is not None:
+            perm = perm.to(eng.device, torch.int32).contiguous()
+        if dp is not None:
+            dp.check_steps(n, config, eng.device)
+        if diag_out is not None:
+            check_diag(diag_out, P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
+            bound = eng.ppo_diag_bound()
+            eng.ppo_diag(diag_out)
+        try:
+            if dp is not None and dp.transport == "torch":
+                shape = (P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter), config.sgd_minibatch_size)
+                stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=train_mask), n,
+                               config, perm, train_ls, diag_out=diag_out,
+                               **self._ppo_draws("learn", eps, dp_shape=shape))
+            else:
+                stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm,
+                                    **self._ppo_draws("learn", eps))
+        finally:
+            if diag_out is not None:
+                eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
+        self.__dict__["_ppo_t"] = t + stats.shape[0]
+        self._ppo_after("learn", stats.shape[0])
+        return stats
+
+    def _policy_prepare(self, rollout, config, eps):
+        from . import ppo as P
+        eng = self.engine
+        self._ppo_refusals()
+        eng._need_gpu()
+        missing = [k for k in P.ROLLOUT_KEYS if rollout.get(k) is None]
+        if missing:
+            raise KeyError("rollout lacks %s" % ", ".join(missing))
+        kind, base, _ = self._ppo_bind_engine()
+        ro = {k: rollout[k] for k in ("obs", "actions", "rewards", "seg_start", "seg_done")}
+        ro["boot_obs"] = rollout["next_obs_last"]
+        given = [rollout.get(k) is not None for k in P.SAMPLER_KEYS]
+        if all(given) or (self._PPO_PARTIAL_SAMPLER and any(given)):
+            ro.update(vf_preds=rollout.get("vf_preds"), old_dist=rollout.get("action_dist_inputs"),
+                      old_logp=rollout.get("action_logp"))
+        res = eng.ppo_prepare(ro, config.gae_params(kind, base), **self._ppo_draws("prepare", eps))
+        chunks = (int(rollout["actions"].shape[0]) + eng.max_batch - 1) // eng.max_batch
+        self._ppo_after("prepare", 0 if all(given) else chunks)
+        out = {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
+               "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
+               "value_targets": res["value_targets"], "last_value": res["last_value"]}
+        if "latent_eps" in res:
+            out["latent_eps"] = res["latent_eps"]
+        return out
+
+    def _policy_act(self, obs, explore, noise, eps, clip, out, step):
+        from . import ppo as P
+        eng = self.engine
+        self._ppo_refusals()
+        eng._need_gpu()
+        assert (out is None) == (step is None), "out (a RolloutBuffer) and step go together"
+        kind, base, _ = self._ppo_bind_engine()
+        cols, out_row = out.step_out(step, clip) if out is not None else (None, None)
+        res = eng.ppo_act(obs.float(), P.make_gae_params(0.0, 0.0, False, kind, base), explore=explore, noise=noise, clip=clip,
+                          out=cols, out_row=out_row, **self._ppo_draws("act", eps))
+        self._ppo_after("act", (int(obs.shape[0]) + eng.max_batch - 1) // eng.max_batch)
+        res = P.act_result(res, out, step)
+        if not explore:
+            res.pop("action_noise", None)
+        return res
+
+    def _ppo_dp_state(self):
+        """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: the parameters, the log-std
+        vector and the PPO step's Adam moments (the step counter travels beside them)."""
+        self._ppo_refusals()
+        _, _, train_ls = self._ppo_bind_engine()
+        return [t for t in self._ppo_dp_tensors(train_ls) if t is not None]
+
+    def reset_ppo_optimizer(self):
+        """Forget the PPO step's Adam state: moments to zero, time step to zero."""
+        self.engine.ppo_reset()
+        self.__dict__["_ppo_t"] = 0
+
+
 def make_rollout(ro, need, device, n_in, k):
     """(pvae_fc_rollout, [tensors kept alive]) from a dict of device tensors: obs, actions, rewards, seg_start (int32
     [S + 1]), seg_done (bool / uint8 [S]), boot_obs ([S, n_in]) and, optionally, the sampler's vf_preds / old_dist /

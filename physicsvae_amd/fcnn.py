@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd as AG
+from .engine_ppo import PpoPolicy
 from .stack_set import StackSetEngine
 from .model import FC, _fc_stack, _portable, fc_spec
 
@@ -29,7 +30,7 @@ DEFAULT_FC_64X2 = fc_spec(64, 2)
 DEFAULT_FC_256X2 = fc_spec(256, 2)
 
 
-class FullyConnectedPolicy(nn.Module):
+class FullyConnectedPolicy(PpoPolicy, nn.Module):
     """A policy that generates action and value with FCNN (rmt:323-457)."""
 
     DEFAULT_CONFIG = {
@@ -146,19 +147,9 @@ class FullyConnectedPolicy(nn.Module):
         return self._cur_value
 
     # -- the fused PPO learner step (physicsvae_amd/ppo.py; include/pvae.h "PPO learner step") ------------
-    def _ppo_train_mask(self):
-        """Bit s: stack s is trained.  A stack is trained or frozen as a whole."""
-        mask = 0
-        for s, (name, fn) in enumerate((("_policy_fn", self._policy_fn), ("_value_fn", self._value_fn),
-                                        ("_log_std_fn", self._log_std_fn))):
-            if fn is None:
-                continue
-            flags = [p.requires_grad for p in AG.stack_params(fn)]
-            if any(flags) and not all(flags):
-                raise NotImplementedError("%s is partially frozen: the fused PPO step trains or freezes a stack as a whole"
-                                          % name)
-            mask |= (1 << s) if all(flags) else 0
-        return mask
+    def _ppo_stacks(self):
+        stacks = (("_policy_fn", self._policy_fn), ("_value_fn", self._value_fn), ("_log_std_fn", self._log_std_fn))
+        return [(name, fn) for name, fn in stacks if fn is not None]
 
     def _ppo_log_std(self):
         """(kind, base, vector, trained) of the log-std as the library's PPO calls take it."""
@@ -174,6 +165,43 @@ class FullyConnectedPolicy(nn.Module):
             base = float(self._log_std_base)
         return kind, base, log_std, train_ls
 
+    # what `PpoPolicy` asks of the class
+    def _ppo_learn_mask(self, config):
+        eng = self.engine
+        eng._need_gpu()
+        if config.sgd_minibatch_size > eng.max_batch:
+            raise ValueError("sgd_minibatch_size %d > max_batch %d (custom_model_config['max_batch'])"
+                             % (config.sgd_minibatch_size, eng.max_batch))
+        mask = self._ppo_train_mask()
+        train_ls = self._ppo_log_std()[3]
+        if mask == 0 and train_ls:
+            raise NotImplementedError("every stack is frozen: the fused PPO step does not train the state_independent "
+                                      "log_std vector alone")
+        if mask == 0:
+            raise ValueError("nothing to train: every stack is frozen")
+        return 0 if mask == (1 << len(eng.stacks)) - 1 else mask
+
+    def _ppo_bind_engine(self):
+        kind, base, log_std, train_ls = self._ppo_log_std()
+        self.engine.ppo_bind(log_std, train_ls)
+        return kind, base, train_ls
+
+    def _ppo_draws(self, call, eps, dp_shape=None):
+        return dict(seed=self._rng_seed, offset=self._rng_calls + 1) if call == "act" else {}
+
+    def _ppo_after(self, call, n):
+        if call == "act":                        # (the learner draws nothing: there is no latent)
+            self._rng_calls += n
+        if call != "prepare":
+            self._cur_value = None
+
+    def _ppo_dp_tensors(self, train_ls):
+        eng = self.engine
+        kind, _, log_std, _ = self._ppo_log_std()
+        vector = log_std if kind != "state_dependent" and self._policy_fn._model[-1].type != "constant" else None
+        return (eng.params, eng.ppo_m, eng.ppo_v, vector, eng.ppo_ls_m if train_ls else None,
+                eng.ppo_ls_v if train_ls else None)
+
     def ppo_prepare(self, rollout, config):
         """The first half of a learner iteration, on the device (`pvae_fc_ppo_prepare`): from a device-resident rollout to the
         train batch `ppo_learn` takes.  `rollout`: device tensors obs [N, n_in], actions [N, k], rewards [N], seg_start (int32
@@ -183,22 +211,7 @@ class FullyConnectedPolicy(nn.Module):
         every segment that did not end its episode, GAE with `config.gamma` / `config.lambda_`, the value targets, and
         (`config.standardize`) the advantages standardised over the batch.  Returns a dict under RLlib's sample-batch keys
         that `ppo_learn` accepts unchanged (plus `last_value` [S]); nothing synchronises."""
-        from . import ppo as P
-        eng = self.engine
-        eng._need_gpu()
-        missing = [k for k in P.ROLLOUT_KEYS if rollout.get(k) is None]
-        if missing:
-            raise KeyError("rollout lacks %s" % ", ".join(missing))
-        kind, base, log_std, train_ls = self._ppo_log_std()
-        eng.ppo_bind(log_std, train_ls)
-        ro = {k: rollout[k] for k in ("obs", "actions", "rewards", "seg_start", "seg_done")}
-        ro["boot_obs"] = rollout["next_obs_last"]
-        if all(rollout.get(k) is not None for k in P.SAMPLER_KEYS):
-            ro.update(vf_preds=rollout["vf_preds"], old_dist=rollout["action_dist_inputs"], old_logp=rollout["action_logp"])
-        res = eng.ppo_prepare(ro, config.gae_params(kind, base))
-        return {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
-                "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
-                "value_targets": res["value_targets"], "last_value": res["last_value"]}
+        return self._policy_prepare(rollout, config, None)
 
     def compute_actions(self, obs, explore=True, noise=None, clip=None, out=None, step=None):
         """The rollout worker's policy step, on the device (`pvae_fc_ppo_act`; the rule: `ppo.py`'s module docstring): from
@@ -211,31 +224,7 @@ class FullyConnectedPolicy(nn.Module):
         way, chunk i drawing at counter + 1 + i).  `out` / `step`: a `ppo.RolloutBuffer` and the step of its fragment
         this call is -- every column (the observations too) is then written in place into the buffer's rows and the
         returned tensors are views of them."""
-        from . import ppo as P
-        eng = self.engine
-        eng._need_gpu()
-        assert (out is None) == (step is None), "out (a RolloutBuffer) and step go together"
-        kind, base, log_std, train_ls = self._ppo_log_std()
-        eng.ppo_bind(log_std, train_ls)
-        cols, out_row = out.step_out(step, clip) if out is not None else (None, None)
-        res = eng.ppo_act(obs.float(), P.make_gae_params(0.0, 0.0, False, kind, base), explore=explore, noise=noise, clip=clip,
-                          seed=self._rng_seed, offset=self._rng_calls + 1, out=cols, out_row=out_row)
-        self._rng_calls += (int(obs.shape[0]) + eng.max_batch - 1) // eng.max_batch
-        self._cur_value = None
-        res = P.act_result(res, out, step)
-        if not explore:
-            res.pop("action_noise", None)
-        return res
-
-    def _ppo_dp_state(self):
-        """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: parameters, the log-std vector
-        and Adam's moments (the step counter travels beside them)."""
-        eng = self.engine
-        kind, base, log_std, train_ls = self._ppo_log_std()
-        eng.ppo_bind(log_std, train_ls)
-        vector = log_std if kind != "state_dependent" and self._policy_fn._model[-1].type != "constant" else None
-        return [t for t in (eng.params, eng.ppo_m, eng.ppo_v, vector, eng.ppo_ls_m if train_ls else None,
-                            eng.ppo_ls_v if train_ls else None) if t is not None]
+        return self._policy_act(obs, explore, noise, None, clip, out, step)
 
     def ppo_learn(self, batch, config, perm=None, dp=None, diag_out=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_fc_ppo_sgd`):
@@ -253,50 +242,7 @@ class FullyConnectedPolicy(nn.Module):
         filled in place with the per-step learner diagnostics (`ppo.DIAG`; one small launch more per step, nothing
         synchronised; `ppo.learner_info(stats, diag_out, config)` reads both); a wrong shape or device is a ValueError.  Rows the
         caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns."""
-        from . import ppo as P
-        from . import engine_ppo as E
-        eng = self.engine
-        eng._need_gpu()
-        if config.sgd_minibatch_size > eng.max_batch:
-            raise ValueError("sgd_minibatch_size %d > max_batch %d (custom_model_config['max_batch'])"
-                             % (config.sgd_minibatch_size, eng.max_batch))
-        mask = self._ppo_train_mask()
-        kind, base, log_std, train_ls = self._ppo_log_std()
-        if mask == 0 and train_ls:
-            raise NotImplementedError("every stack is frozen: the fused PPO step does not train the state_independent "
-                                      "log_std vector alone")
-        if mask == 0:
-            raise ValueError("nothing to train: every stack is frozen")
-        eng.ppo_bind(log_std, train_ls)
-        cols = eng.ppo_batch(P.batch_columns(batch))
-        t = self.__dict__.get("_ppo_t", 0)
-        full = (1 << len(eng.stacks)) - 1
-        params = config.params(kind, base, adam_t=t + 1, train_mask=0 if mask == full else mask)
-        if perm is not None:
-            perm = perm.to(eng.device, torch.int32).contiguous()
-        if dp is not None:
-            dp.check_steps(int(cols[0].n_rows), config, eng.device)
-        if diag_out is not None:
-            E.check_diag(diag_out, P.dp_steps(int(cols[0].n_rows), config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
-            bound = eng.ppo_diag_bound()
-            eng.ppo_diag(diag_out)
-        try:
-            if dp is not None and dp.transport == "torch":
-                stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=params.train_mask),
-                               int(cols[0].n_rows), config, perm, train_ls, diag_out=diag_out)
-            else:
-                stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm)
-        finally:
-            if diag_out is not None:
-                eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
-        self.__dict__["_ppo_t"] = t + stats.shape[0]
-        self._cur_value = None
-        return stats
-
-    def reset_ppo_optimizer(self):
-        """Forget Adam's state: moments to zero, time step to zero."""
-        self.engine.ppo_reset()
-        self.__dict__["_ppo_t"] = 0
+        return self._policy_learn(batch, config, perm, None, dp, diag_out)
 
     def set_exploration_std(self, std):
         self._policy_fn._model[-1].set_val(math.log(std))                         # rmt:448-450

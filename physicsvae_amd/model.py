@@ -28,6 +28,7 @@ from . import autograd as AG
 from ._lib import NET_MD, NET_MH, NET_NAMES, NET_PR, NET_TE, NET_WM, PRIOR_KINDS
 from .arch import Arch, Stack
 from .engine import HipEngine
+from .engine_ppo import PpoPolicy
 
 
 def fc_spec(width, depth, out_size="output", act_hidden="relu", act_out="linear"):
@@ -227,7 +228,7 @@ def _cur_property(name):
     return property(lambda self: getattr(self._st, name), lambda self, v: setattr(self._st, name, v))
 
 
-class PhysicsVAE(nn.Module):
+class PhysicsVAE(PpoPolicy, nn.Module):
     DEFAULT_CONFIG = {
         "project_dir": None,
         "log_std_type": "constant",
@@ -775,18 +776,11 @@ class PhysicsVAE(nn.Module):
         if self.engine.lookahead != 1:
             raise NotImplementedError("lookahead %d: the fused PPO step needs a lookahead 1 engine" % self.engine.lookahead)
 
-    def _ppo_train_mask(self):
-        """Bits 1 / 2 / 4: the task encoder / the motor decoder / the value branch is trained.  Each is trained or frozen
-        as a whole (the decoder's log_std vector is not part of its stack: rmt:936-941)."""
-        mask = 0
-        for bit, name, fn in ((1, "_task_encoder", self._task_encoder), (2, "_motor_decoder", self._motor_decoder),
-                              (4, "_value_branch", self._value_branch)):
-            flags = [p.requires_grad for p in AG.stack_params(fn)]
-            if any(flags) and not all(flags):
-                raise NotImplementedError("%s is partially frozen: the fused PPO step trains or freezes a stack as a whole"
-                                          % name)
-            mask |= bit if all(flags) else 0
-        return mask
+    def _ppo_stacks(self):
+        """Train-mask bits 1 / 2 / 4: the task encoder / the motor decoder / the value branch (the decoder's log_std
+        vector is not part of its stack: rmt:936-941)."""
+        return (("_task_encoder", self._task_encoder), ("_motor_decoder", self._motor_decoder),
+                ("_value_branch", self._value_branch))
 
     def _ppo_value_engine(self):
         """The value branch as a one-stack stack set (`StackSetEngine`, [value]), made on the first `ppo_learn`: the weights
@@ -808,6 +802,46 @@ class PhysicsVAE(nn.Module):
             self.__dict__.pop("_vb_layers", None)
         return ve
 
+    # what `PpoPolicy` asks of the class
+    _PPO_PARTIAL_SAMPLER = True
+
+    def _ppo_learn_mask(self, config):
+        eng = self.engine
+        self._ppo_refusals()
+        mask = self._ppo_train_mask()
+        if config.sgd_minibatch_size > eng.max_batch:
+            raise ValueError("sgd_minibatch_size %d > max_batch %d (custom_model_config['max_batch'])"
+                             % (config.sgd_minibatch_size, eng.max_batch))
+        if mask == 0:
+            raise ValueError("nothing to train: the task encoder, the motor decoder and the value branch are all frozen")
+        eng._need_gpu()
+        return 0 if mask == 7 else mask
+
+    def _ppo_bind_engine(self):
+        eng = self.engine
+        als = self.__dict__["_als"]
+        train_ls = als.type == "state_independent" and als.log_std.requires_grad
+        eng.ppo_bind(self._ppo_value_engine(), als.on_device(eng.device), train_ls)
+        return "state_independent" if als.type == "state_independent" else "constant", 0.0, train_ls
+
+    def _ppo_draws(self, call, eps, dp_shape=None):
+        if dp_shape is not None:
+            eps = self.engine._ppo_eps(eps, dp_shape + (self.engine.arch.Z,))
+        noise = "latent_noise" if call == "act" else "noise"
+        return {"eps": eps, noise: bool(self.latent_prior_noise), "seed": self._rng_seed, "offset": self._st._rng_calls + 1}
+
+    def _ppo_after(self, call, n):
+        st = self._st
+        st._rng_calls += n
+        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
+
+    def _ppo_dp_tensors(self, train_ls):
+        eng, ve = self.engine, self._ppo_value_engine()
+        als = self.__dict__["_als"]
+        vector = als.on_device(eng.device) if als.type != "constant" else None   # (a constant one is configuration, the same everywhere)
+        return (eng.params, ve.params, eng.ppo_m, eng.ppo_v, ve.ppo_m, ve.ppo_v, vector,
+                eng.ppo_ls_m if train_ls else None, eng.ppo_ls_v if train_ls else None)
+
     def ppo_prepare(self, rollout, config, eps=None):
         """The first half of a learner iteration, on the device (`pvae_ppo_prepare`): from a device-resident rollout to the
         train batch `ppo_learn` takes.  `rollout`: device tensors under `ppo.ROLLOUT_KEYS` -- obs [N, 2 Db], actions [N, Da],
@@ -824,32 +858,7 @@ class PhysicsVAE(nn.Module):
         unchanged, plus `last_value` [S] and `latent_eps` [N, Z], the draws used (None when the sampler's columns were
         given); nothing synchronises.  Frozen nets make no difference here, and a state_independent log-std is read, not
         trained.  The first call re-homes the value branch into a stack set (`_ppo_value_engine`)."""
-        from . import ppo as P
-        eng = self.engine
-        self._ppo_refusals()
-        eng._need_gpu()
-        missing = [k for k in P.ROLLOUT_KEYS if rollout.get(k) is None]
-        if missing:
-            raise KeyError("rollout lacks %s" % ", ".join(missing))
-        als = self.__dict__["_als"]
-        train_ls = als.type == "state_independent" and als.log_std.requires_grad
-        eng.ppo_bind(self._ppo_value_engine(), als.on_device(eng.device), train_ls)
-        ro = {k: rollout[k] for k in ("obs", "actions", "rewards", "seg_start", "seg_done")}
-        ro["boot_obs"] = rollout["next_obs_last"]
-        given = [rollout.get(k) is not None for k in P.SAMPLER_KEYS]
-        if any(given):
-            ro.update(vf_preds=rollout.get("vf_preds"), old_dist=rollout.get("action_dist_inputs"),
-                      old_logp=rollout.get("action_logp"))
-        st = self._st
-        res = eng.ppo_prepare(ro, config.gae_params("state_independent" if als.type == "state_independent" else "constant"),
-                              eps=eps, noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
-        if not all(given):
-            n = int(rollout["actions"].shape[0])
-            st._rng_calls += (n + eng.max_batch - 1) // eng.max_batch
-        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
-        return {"obs": rollout["obs"], "actions": rollout["actions"], "action_dist_inputs": res["old_dist"],
-                "action_logp": res["old_logp"], "vf_preds": res["vf_preds"], "advantages": res["advantages"],
-                "value_targets": res["value_targets"], "last_value": res["last_value"], "latent_eps": res["latent_eps"]}
+        return self._policy_prepare(rollout, config, eps)
 
     def compute_actions(self, obs, explore=True, noise=None, eps=None, clip=None, out=None, step=None):
         """The rollout worker's policy step, on the device (`pvae_ppo_act`; the rule: `ppo.py`'s module docstring): from the
@@ -864,40 +873,7 @@ class PhysicsVAE(nn.Module):
         `ppo_prepare` does.  `out` / `step`: a `ppo.RolloutBuffer` (made with `latent=Z`) and the step of its fragment this
         call is -- every column (the observations too) is then written in place into the buffer's rows and the returned
         tensors are views of them.  Refused by name where the fused PPO step is (`_ppo_refusals`)."""
-        from . import ppo as P
-        eng = self.engine
-        self._ppo_refusals()
-        eng._need_gpu()
-        assert (out is None) == (step is None), "out (a RolloutBuffer) and step go together"
-        als = self.__dict__["_als"]
-        train_ls = als.type == "state_independent" and als.log_std.requires_grad
-        eng.ppo_bind(self._ppo_value_engine(), als.on_device(eng.device), train_ls)
-        cols, out_row = out.step_out(step, clip) if out is not None else (None, None)
-        st = self._st
-        kind = "state_independent" if als.type == "state_independent" else "constant"
-        res = eng.ppo_act(obs.float(), P.make_gae_params(0.0, 0.0, False, kind), explore=explore, noise=noise, clip=clip,
-                          eps=eps, latent_noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1,
-                          out=cols, out_row=out_row)
-        st._rng_calls += (int(obs.shape[0]) + eng.max_batch - 1) // eng.max_batch
-        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
-        res = P.act_result(res, out, step)
-        if not explore:
-            res.pop("action_noise", None)
-        return res
-
-    def _ppo_dp_state(self):
-        """Bind the PPO buffers and return what `PPODataParallel.attach` copies from rank 0: the parameter arena and the
-        value branch's, the log-std vector and the PPO step's Adam moments (the step counter travels beside them)."""
-        eng = self.engine
-        self._ppo_refusals()
-        als = self.__dict__["_als"]
-        train_ls = als.type == "state_independent" and als.log_std.requires_grad
-        ve = self._ppo_value_engine()
-        log_std = als.on_device(eng.device)
-        eng.ppo_bind(ve, log_std, train_ls)
-        vector = log_std if als.type != "constant" else None        # (a constant one is configuration, the same everywhere)
-        return [t for t in (eng.params, ve.params, eng.ppo_m, eng.ppo_v, ve.ppo_m, ve.ppo_v, vector,
-                            eng.ppo_ls_m if train_ls else None, eng.ppo_ls_v if train_ls else None) if t is not None]
+        return self._policy_act(obs, explore, noise, eps, clip, out, step)
 
     def ppo_learn(self, batch, config, perm=None, eps=None, dp=None, diag_out=None):
         """One training iteration's SGD on a device-resident train batch, in one library call (`pvae_ppo_sgd`):
@@ -918,57 +894,7 @@ class PhysicsVAE(nn.Module):
         tensor [steps, PPO_DIAG] from `ppo.diag_buffer`, filled in place with the per-step learner diagnostics (`ppo.DIAG`;
         one small launch more per step, nothing synchronised); a wrong shape or device is a ValueError.  Rows the
         caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns."""
-        from . import ppo as P
-        from . import engine_ppo as E
-        eng = self.engine
-        self._ppo_refusals()
-        mask = self._ppo_train_mask()
-        if config.sgd_minibatch_size > eng.max_batch:
-            raise ValueError("sgd_minibatch_size %d > max_batch %d (custom_model_config['max_batch'])"
-                             % (config.sgd_minibatch_size, eng.max_batch))
-        if mask == 0:
-            raise ValueError("nothing to train: the task encoder, the motor decoder and the value branch are all frozen")
-        eng._need_gpu()
-        als = self.__dict__["_als"]
-        train_ls = als.type == "state_independent" and als.log_std.requires_grad
-        ve = self._ppo_value_engine()
-        eng.ppo_bind(ve, als.on_device(eng.device), train_ls)
-        cols = eng.ppo_batch(P.batch_columns(batch))
-        t = self.__dict__.get("_ppo_t", 0)
-        params = config.params("state_independent" if train_ls else "constant", 0.0, adam_t=t + 1,
-                               train_mask=0 if mask == 7 else mask)
-        if perm is not None:
-            perm = perm.to(eng.device, torch.int32).contiguous()
-        st = self._st
-        draws = dict(eps=eps, noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=st._rng_calls + 1)
-        if dp is not None:
-            dp.check_steps(int(cols[0].n_rows), config, eng.device)
-        if diag_out is not None:
-            E.check_diag(diag_out, P.dp_steps(int(cols[0].n_rows), config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
-            bound = eng.ppo_diag_bound()
-            eng.ppo_diag(diag_out)
-        try:
-            if dp is not None and dp.transport == "torch":
-                n = int(cols[0].n_rows)
-                steps = P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter)
-                draws["eps"] = eng._ppo_eps(eps, (steps, config.sgd_minibatch_size, eng.arch.Z))
-                kind = "state_independent" if train_ls else "constant"
-                stats = dp.sgd(eng, cols, lambda i: config.params(kind, 0.0, adam_t=t + 1 + i, train_mask=params.train_mask), n,
-                               config, perm, train_ls, diag_out=diag_out, **draws)
-            else:
-                stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm, **draws)
-        finally:
-            if diag_out is not None:
-                eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
-        st._rng_calls += stats.shape[0]
-        self.__dict__["_ppo_t"] = t + stats.shape[0]
-        st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
-        return stats
-
-    def reset_ppo_optimizer(self):
-        """Forget the PPO step's Adam state: moments to zero, time step to zero."""
-        self.engine.ppo_reset()
-        self.__dict__["_ppo_t"] = 0
+        return self._policy_learn(batch, config, perm, eps, dp, diag_out)
 
     def set_exploration_std(self, std):
         self._motor_decoder._model[-1].set_val(float(np.log(std)))
