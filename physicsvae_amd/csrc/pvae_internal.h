@@ -1,7 +1,8 @@
 // pvae_internal.h -- what the translation units of libpvae_gfx950.so share: error handling, the optional per-launch
 // profiler, the run-time RCCL binding, the context, Philox, and the few functions one unit calls in another.
 //   pvae.hip                 the context: layout queries, lifecycle, options, bindings, minibatch staging, pvae_read_tensor
-//   pvae_net.hip             one stack: forward launches, the sampler, the backward plan and its deferred-Adam hand-over
+//   pvae_net.hip             one stack: forward launches, the sampler, the backward plan (one function per schedule, on BwdNet
+//                            below) and its deferred-Adam hand-over
 //   pvae_step.hip            the training step at lookahead 1 and the step's C ABI (direct, prefetch and data-parallel steps)
 //   pvae_lookahead.hip       the training step at lookahead > 1 (the multi-step unroll)
 //   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
@@ -566,6 +567,118 @@ struct CarriedWgrad {
     std::function<int(const DgradArgs&)> run_with_dgrad;
     int64_t ready_off = 0, ready_cnt = 0;
     int net = -1;
+};
+inline Stage& push(Plan& plan, std::function<int()> fn) {
+    plan.emplace_back();
+    plan.back().run = std::move(fn);
+    return plan.back();
+}
+// a fused step may store a layer's gradient and leave its update to workgroups of a later launch (AdamSeg)
+inline bool can_defer_adam(const pvae_ctx* c, bool fused) { return fused && c->defer_adam && c->grads != nullptr; }
+
+// One stack's backward pass as both planners see it (plan_backward_net: lookahead 1; plan_backward_unrolled): the operands of
+// layer i on the row block that starts at row `blk` (lookahead 1: 0; the unroll: Unroll::blk(slot)), its input-gradient
+// launch, its three gradient epilogues and the choice between them, its deferred-Adam segment and its slice of the arena.
+// A plain value: the stages of a plan keep a copy.
+struct BwdNet {
+    pvae_ctx* c;
+    int n;
+    const NetLayout* N;
+    const NetWork* w;
+    AdamScalars as;
+    hipStream_t st;
+    double rowsf;                  // rows of the batch (the profiler's flop counts)
+    int dx0_cols = 0;              // > 0: the columns of layer 0's input gradient that anything reads (flop counts only)
+    BwdNet(pvae_ctx* c_, int n_, const pvae_step_params* sp, hipStream_t st_)
+        : c(c_), n(n_), N(&c_->L.net[n_]), w(&c_->W.net[n_]), as(adam_scalars(sp, n_)), st(st_), rowsf(c_->staged_rows_f) {}
+    int last() const { return (int)N->layers.size() - 1; }
+    const Layer& layer(int i) const { return N->layers[i]; }
+
+    // x: the input panel or act[i-1];  dz: the output gradient;  dx_out: where the input gradient goes, dz[i-1] or d_in
+    const float* x(int i, int64_t blk = 0) const { return c->ws + (i == 0 ? w->in : w->act[i - 1]) + blk * layer(i).ld; }
+    const float* dz(int i, int64_t blk = 0) const { return c->ws + w->dz[i] + blk * layer(i).n_out_pad; }
+    float* dx_out(int i, int64_t blk = 0) const { return c->ws + (i > 0 ? w->dz[i - 1] : w->d_in) + blk * layer(i).ld; }
+    // act_grad code of the layer whose output masks the input gradient of layer i (layer i - 1; none for i == 0)
+    int mask_act(int i) const { return i > 0 ? layer(i - 1).act : 1; }
+    int dgrad_cols(int i) const { return i > 0 || dx0_cols <= 0 ? layer(i).n_in : dx0_cols; }
+
+    // dgrad of layer i: dz[i] (.) W_i -> dz[i-1] (masked) or d_in (i == 0, unmasked)
+    DgradArgs dgrad_args(int i, int64_t blk, int rows_pad) const {
+        const Layer& l = layer(i);
+        return DgradArgs{dz(i, blk), l.n_out_pad, c->params + l.w_off, l.ld, i > 0 ? x(i, blk) : nullptr, l.ld, dx_out(i, blk), l.ld,
+                         rows_pad, l.ld, l.n_out_pad, 2.0 * rowsf * dgrad_cols(i) * l.n_out, mask_act(i)};
+    }
+    int dgrad(int i, int64_t blk, int rows_pad) const {
+        const DgradArgs d = dgrad_args(i, blk, rows_pad);
+        const int ps = g_prof.begin(1, d.flops, st);
+        HIP_TRY(gemm_dgrad(d.dZ, d.ldz, d.W, d.ldw, d.mask, d.ldm, d.dX, d.ldo, d.M, d.Kin, d.Nd, st, d.act));
+        g_prof.end(ps, st);
+        return 0;
+    }
+    // wgrad of layer i over rows [0, krows), alone or sharing its launch with the input gradient `d` (of any stack)
+    template <class E>
+    hipError_t wgrad(int i, int krows, const E& e, const AdamPair* ad) const {
+        const Layer& l = layer(i);
+        return gemm_wgrad(dz(i), l.n_out_pad, x(i), l.ld, l.n_out_pad, l.ld, krows, e, st, ad);
+    }
+    template <class E>
+    hipError_t wgrad_with_dgrad(int i, int krows, const DgradArgs& d, const E& e, const AdamPair& ad) const {
+        const Layer& l = layer(i);
+        return gemm_bwd_pair(d.dZ, d.ldz, d.W, d.ldw, d.mask, d.ldm, d.dX, d.ldo, d.M, d.Kin, d.Nd, dz(i), l.n_out_pad, x(i), l.ld,
+                             l.n_out_pad, l.ld, krows, e, st, &ad, d.act);
+    }
+
+    // what a weight-gradient launch does with layer i's gradient: Adam in place, store, or add into the arena
+    EpiGradAdam adam_epi(int i) const {
+        const Layer& l = layer(i);
+        EpiGradAdam e{c->params + l.w_off, c->m + l.w_off, c->v + l.w_off, l.ld, as};
+        e.b = c->params + l.b_off; e.bm = c->m + l.b_off; e.bv = c->v + l.b_off;
+        return e;
+    }
+    EpiGradStore store_epi(int i) const {
+        const Layer& l = layer(i);
+        EpiGradStore e{c->grads + l.w_off, l.ld};
+        e.gb = c->grads + l.b_off;
+        return e;
+    }
+    EpiGradAccum accum_epi(int i) const {
+        const Layer& l = layer(i);
+        EpiGradAccum e{c->grads + l.w_off, l.ld};
+        e.gb = c->grads + l.b_off;
+        return e;
+    }
+    // the epilogue of e's kind for layer i (the second problem of a two-layer launch)
+    EpiGradAdam like(const EpiGradAdam&, int i) const { return adam_epi(i); }
+    EpiGradStore like(const EpiGradStore&, int i) const { return store_epi(i); }
+    EpiGradAccum like(const EpiGradAccum&, int i) const { return accum_epi(i); }
+    // f(epilogue of layer i): Adam when `fused`, else the store -- or, kAccum, the add that pvae_net_backward(accumulate)
+    // asks for.  (kAccum = false: the unroll, which is never run accumulating and whose unit therefore holds no kernel
+    // with that epilogue; naming it there would instantiate them.)
+    // (the return type is f's declared one -- int or hipError_t --, not deduced from this body: a deduced one would
+    //  instantiate f, and with it the kernels it launches, where the call is parsed and not at the unit's end)
+    template <bool kAccum = true, class F>
+    std::invoke_result_t<F&, EpiGradAdam> with_grad_epi(int i, bool fused, F&& f) const {
+        if (fused) return f(adam_epi(i));
+        if constexpr (kAccum)
+            if (c->grad_accum) return f(accum_epi(i));
+        return f(store_epi(i));
+    }
+    // the update of layer i as a segment for workgroups of a later launch (its gradient stored by this one)
+    AdamSeg adam_seg(int i) const {
+        const Layer& l = layer(i);
+        AdamSeg a;
+        a.p = c->params + l.w_off; a.g = c->grads + l.w_off; a.m = c->m + l.w_off; a.v = c->v + l.w_off;
+        a.n4 = (l.b_off + l.n_out_pad - l.w_off) / 4;
+        a.s = as;
+        return a;
+    }
+    // the stage finishes layers lo..hi (lo <= hi) of this stack's slice of the gradient arena
+    template <class S>                         // (a Stage, or the CarriedWgrad that stands in for one)
+    void ready(S& s, int lo, int hi) const {
+        s.ready_off = layer(lo).w_off;
+        s.ready_cnt = layer(hi).b_off + layer(hi).n_out_pad - layer(lo).w_off;
+        s.net = n;
+    }
 };
 void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool input_grad, const pvae_step_params* sp, bool fused,
                        hipStream_t st, const LossFinal* fold, Plan& plan, const InputSeed* seed = nullptr,

@@ -117,12 +117,8 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
     const bool joint = phase == PVAE_PHASE_JOINT;
     const NetLayout* NL = c->L.net;
     const NetWork* NW = c->W.net;
-    const double rowsf = c->staged_rows_f;
-    auto push = [&](std::function<int()> f) -> Stage& {
-        plan.emplace_back();
-        plan.back().run = std::move(f);
-        return plan.back();
-    };
+    std::vector<BwdNet> nets;                  // every stack's backward view; a launch names its row block (u.blk(slot))
+    for (int n = 0; n < PVAE_NUM_NETS; ++n) nets.emplace_back(c, n, sp, st);
     // which invocations carry gradient (evaluated last step first)
     const bool a_grad = joint && sp->a_rec_coeff > 0.0f;
     std::vector<char> p_act(T, 0), md_act(T, 0), any(T + 1, 0);
@@ -133,22 +129,10 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
     }
     // full dgrad chain of net n over row block `slot`; layer 0 only when its input gradient is consumed
     auto dgrad_chain = [&](int n, int slot, bool layer0) {
-        const NetLayout* N = &NL[n];
-        const NetWork* nw = &NW[n];
+        const BwdNet bn = nets[n];
         const int64_t b = u.blk(slot);
         const int rows_pad = u.rows_pad;
-        for (int i = (int)N->layers.size() - 1; i >= (layer0 ? 0 : 1); --i) {
-            push([=]() -> int {
-                const Layer& l = N->layers[i];
-                const float* mask = i > 0 ? w + nw->act[i - 1] + b * l.ld : nullptr;
-                float* out = i > 0 ? w + nw->dz[i - 1] + b * l.ld : w + nw->d_in + b * l.ld;
-                const int ps = g_prof.begin(1, 2.0 * rowsf * l.n_in * l.n_out, st);
-                HIP_TRY(gemm_dgrad(w + nw->dz[i] + b * l.n_out_pad, l.n_out_pad, c->params + l.w_off, l.ld, mask, l.ld,
-                                   out, l.ld, rows_pad, l.ld, l.n_out_pad, st, i > 0 ? N->layers[i - 1].act : 1));
-                g_prof.end(ps, st);
-                return 0;
-            });
-        }
+        for (int i = bn.last(); i >= (layer0 ? 0 : 1); --i) push(plan, [=] { return bn.dgrad(i, b, rows_pad); });
     };
     const int ld_te = NL[PVAE_NET_TE].layers[0].ld, ld_md = NL[PVAE_NET_MD].layers[0].ld;
     const int ld_wm = NL[PVAE_NET_WM].layers[0].ld;
@@ -190,7 +174,7 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
                 if (act[b]) continue;
                 const int64_t r0 = u.blk(b);
                 const size_t nrows = (size_t)u.rows_pad;
-                push([=]() -> int {
+                push(plan, [=]() -> int {
                     for (const Layer& l : N->layers)
                         HIP_TRY(hipMemsetAsync(w + nw->dz[l.index] + r0 * l.n_out_pad, 0, nrows * l.n_out_pad * sizeof(float), st));
                     return 0;
@@ -204,61 +188,44 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
     // input gradient of step 0 is launched, dz[i] is final for every step: its weight gradient (over all steps) can
     // share that launch -- the same-layer pairing of the lookahead-1 schedule (gradient stored, Adam deferred to
     // workgroups of the next launch), instead of 3 weight-gradient launches per stack at the end (PVAE_LOOK_PAIR=0).
-    const bool can_defer = fused && c->defer_adam && c->grads != nullptr;
-    const bool look_pair = backward && g_look_pair && c->pair_launch && c->same_layer_pairs && (!fused || can_defer);
+    const bool look_pair = backward && g_look_pair && c->pair_launch && c->same_layer_pairs && (!fused || can_defer_adam(c, fused));
     bool paired_done[PVAE_NUM_NETS] = {};
     // layers last .. lo of stack n: dgrad_i over row block `slot` || wgrad_i over rows [0, krows); then, when lo == 1,
     // layer 0's weight gradient on its own.  `with_fold`: the stack's last launch also finalises the losses.
     auto paired_chain = [&](int n, int slot, int lo, bool with_fold) {
-        const NetLayout* N = &NL[n];
-        const NetWork* nw = &NW[n];
+        const BwdNet bn = nets[n];
         const int64_t b = u.blk(slot);
         const int rows_pad = u.rows_pad, krows = krows_of[n];
-        const AdamScalars as = adam_scalars(sp, n);
         LossFinal foldv;
         memset(&foldv, 0, sizeof(foldv));
         if (with_fold && fold) foldv = *fold;
-        for (int i = (int)N->layers.size() - 1; i >= 0; --i) {
+        for (int i = bn.last(); i >= 0; --i) {
             const bool has_d = i >= lo;
             const bool f = with_fold && fold && i == 0;
-            Stage& sref = push([=]() -> int {
-                const Layer& l = N->layers[i];
-                const float* mask = i > 0 ? w + nw->act[i - 1] + b * l.ld : nullptr;
-                float* out = i > 0 ? w + nw->dz[i - 1] + b * l.ld : w + nw->d_in + b * l.ld;
-                const float* dz = w + nw->dz[i];
-                const float* xin = i == 0 ? w + nw->in : w + nw->act[i - 1];
-                EpiGradAdam ea{c->params + l.w_off, c->m + l.w_off, c->v + l.w_off, l.ld, as};
-                ea.b = c->params + l.b_off; ea.bm = c->m + l.b_off; ea.bv = c->v + l.b_off;
-                EpiGradStore es{c->grads + l.w_off, l.ld};
-                es.gb = c->grads + l.b_off;
-                if (f) { ea.loss = foldv; es.loss = foldv; }
-                const AdamPair ad = take_pending(c);
+            bn.ready(push(plan, [=]() -> int {
+                const Layer& l = bn.layer(i);
+                const double fl = 2.0 * bn.rowsf * l.n_in * l.n_out;
+                const AdamPair ad = take_pending(c);               // (every launch takes all that is pending: no narrow rule here)
                 hipError_t he;
                 if (has_d) {
-                    const int pp = g_prof.begin(3, 2.0 * rowsf * l.n_in * l.n_out * (1.0 + (double)krows / rows_pad), st);
-                    he = gemm_bwd_pair(dz + b * l.n_out_pad, l.n_out_pad, c->params + l.w_off, l.ld, mask, l.ld, out, l.ld,
-                                       rows_pad, l.ld, l.n_out_pad, dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, krows, es,
-                                       st, &ad, i > 0 ? N->layers[i - 1].act : 1);
+                    EpiGradStore es = bn.store_epi(i);
+                    if (f) es.loss = foldv;
+                    const int pp = g_prof.begin(3, fl * (1.0 + (double)krows / rows_pad), st);
+                    he = bn.wgrad_with_dgrad(i, krows, bn.dgrad_args(i, b, rows_pad), es, ad);
                     g_prof.end(pp, st);
-                    if (he == hipSuccess && fused) {                 // (this launch read W_i: its update waits for the next one)
-                        AdamSeg a;
-                        a.p = c->params + l.w_off; a.g = c->grads + l.w_off; a.m = c->m + l.w_off; a.v = c->v + l.w_off;
-                        a.n4 = (l.b_off + l.n_out_pad - l.w_off) / 4;
-                        a.s = as;
-                        c->pending_adam = a;
-                    }
+                    // (this launch read W_i: its update waits for the next one)
+                    if (he == hipSuccess && fused) c->pending_adam = bn.adam_seg(i);
                 } else {
-                    const int pw = g_prof.begin(2, 2.0 * rowsf * l.n_in * l.n_out * ((double)krows / rows_pad), st);
-                    he = fused ? gemm_wgrad(dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, krows, ea, st, &ad)
-                               : gemm_wgrad(dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, krows, es, st, &ad);
+                    const int pw = g_prof.begin(2, fl * ((double)krows / rows_pad), st);
+                    he = bn.with_grad_epi<false>(i, fused, [&](auto e) -> hipError_t {
+                        if (f) e.loss = foldv;
+                        return bn.wgrad(i, krows, e, &ad);
+                    });
                     g_prof.end(pw, st);
                 }
                 if (he != hipSuccess) return fail(-10, "paired backward launch: %s", hipGetErrorString(he));
                 return 0;
-            });
-            sref.ready_off = N->layers[i].w_off;
-            sref.ready_cnt = N->layers[i].b_off + N->layers[i].n_out_pad - N->layers[i].w_off;
-            sref.net = n;
+            }), i, i);
         }
         paired_done[n] = true;
     };
@@ -283,7 +250,7 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
                 const float* s_md = md_act[t + 1] ? w + wmd->d_in + nt * ld_md : nullptr;
                 const float* s_p = p_act[t + 1] ? w + wwm->d_in + np * ld_wm : nullptr;
                 const float* s_g = u.use_g ? w + wwm->d_in + nt * ld_wm : nullptr;
-                push([=] {
+                push(plan, [=] {
                     return add_cols_launch(w + wwm->dz.back() + bp * ldo_wm, ldo_wm, rows, Db, s_te, ld_te, s_md, ld_md, s_p, ld_wm,
                                            s_g, ld_wm, st);
                 });
@@ -297,13 +264,13 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
             const float ga = joint ? sp->a_rec_coeff * S.gs / (S.Bg * Da) : 0.0f;
             const int nparts = S.nparts_a, l1 = S.l1;
             const bool extra = p_act[t] && backward;
-            push([=] { return action_loss_launch(c, rows, t, bt, bp, nparts, ga, l1, backward, extra, st); });
+            push(plan, [=] { return action_loss_launch(c, rows, t, bt, bp, nparts, ga, l1, backward, extra, st); });
         }
         if (!backward || !md_act[t]) continue;
         if (helper) {
             // d a_hat_t (just formed) -> the helper's output layer through range * tanh', then its own layers; its input
             // gradient matters where the decoder's does (z -> encoder, s1_t -> the previous step)
-            push([=] { return helper_seed_launch(c, rows, bt, st); });
+            push(plan, [=] { return helper_seed_launch(c, rows, bt, st); });
             dgrad_chain(PVAE_NET_MH, t, upstream);
         }
         if (!upstream) continue;
@@ -312,13 +279,13 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
         else dgrad_chain(PVAE_NET_MD, t, true);
         if (helper) {                              // x_t = [s1_t | z_t] feeds the helper too: its input gradient joins the decoder's
             const int ld_mh = NL[PVAE_NET_MH].layers[0].ld;
-            push([=] {
+            push(plan, [=] {
                 return add_cols_launch(w + wmd->d_in + bt * ld_md, ld_md, rows, Db + Z, w + wmh->d_in + bt * ld_mh, ld_mh, nullptr, 0,
                                        nullptr, 0, nullptr, 0, st);
             });
         }
         const float kls = S.kl_active ? sp->kl_coeff / S.Bg : 0.0f;
-        push([=] { return reparam_bwd_launch(c, rows, bt, kls, st); });
+        push(plan, [=] { return reparam_bwd_launch(c, rows, bt, kls, st); });
         if (pair_here && krows_of[PVAE_NET_TE] > 0) paired_chain(PVAE_NET_TE, t, 1, true);
         else dgrad_chain(PVAE_NET_TE, t, t > 0);
     }
@@ -329,60 +296,40 @@ void plan_backward_unrolled(pvae_ctx* c, int phase, int rows, const pvae_step_pa
     for (size_t k = 0; k < train_nets.size(); ++k) {
         const int n = train_nets[k];
         if (paired_done[n]) continue;
-        const NetLayout* N = &NL[n];
-        const NetWork* nw = &NW[n];
+        const BwdNet bn = nets[n];
         const int blocks = krows_of[n] / u.rows_pad;
         const int krows = krows_of[n];
-        const AdamScalars as = adam_scalars(sp, n);
         const bool last_net = k + 1 == train_nets.size();
         // two layers per launch (wgrad_pair_kernel), last layer first; an odd layer count leaves layer 0
         // on its own.  The launch that contains layer 0 of the last net also finalises the losses.
         const bool pairs = c->pair_launch && krows > 0;
-        for (int i = (int)N->layers.size() - 1; i >= 0;) {
+        for (int i = bn.last(); i >= 0;) {
             const int j = (pairs && i >= 1) ? i - 1 : -1;             // second layer of this launch
             const int lo = j >= 0 ? j : i;
             const bool with_fold = fold && last_net && lo == 0;
             LossFinal foldv;
             memset(&foldv, 0, sizeof(foldv));
             if (with_fold) foldv = *fold;
-            Stage& sref = push([=]() -> int {
-                const Layer& l = N->layers[i];
-                const float* dz = w + nw->dz[i];
-                const float* xin = i == 0 ? w + nw->in : w + nw->act[i - 1];
-                double fl = 2.0 * rowsf * blocks * l.n_in * l.n_out;
-                if (j >= 0) fl += 2.0 * rowsf * blocks * N->layers[j].n_in * N->layers[j].n_out;
+            bn.ready(push(plan, [=]() -> int {
+                const Layer& l = bn.layer(i);
+                double fl = 2.0 * bn.rowsf * blocks * l.n_in * l.n_out;
+                if (j >= 0) fl += 2.0 * bn.rowsf * blocks * bn.layer(j).n_in * bn.layer(j).n_out;
                 const int pw = g_prof.begin(2, fl, st);
                 int rc2 = 0;
-                auto adam_of = [&](const Layer& y) {
-                    EpiGradAdam e{c->params + y.w_off, c->m + y.w_off, c->v + y.w_off, y.ld, as};
-                    e.b = c->params + y.b_off; e.bm = c->m + y.b_off; e.bv = c->v + y.b_off;
-                    return e;
-                };
-                auto store_of = [&](const Layer& y) {
-                    EpiGradStore e{c->grads + y.w_off, y.ld};
-                    e.gb = c->grads + y.b_off;
-                    return e;
-                };
-                auto go = [&](auto e1, auto e2) -> hipError_t {
-                    if (with_fold) e1.loss = foldv;                   // block 0 of the launch runs e1's problem
-                    if (j < 0) return gemm_wgrad(dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, krows, e1, st);
-                    const Layer& l2 = N->layers[j];
-                    const float* dz2 = w + nw->dz[j];
-                    const float* xin2 = j == 0 ? w + nw->in : w + nw->act[j - 1];
-                    return gemm_wgrad_pair(dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, e1, dz2, l2.n_out_pad, xin2, l2.ld,
-                                           l2.n_out_pad, l2.ld, e2, krows, st);
-                };
                 if (krows > 0) {                   // (0: nothing reached this net, its gradient stays as it is)
-                    const Layer& l2 = N->layers[j >= 0 ? j : i];
-                    const hipError_t he = fused ? go(adam_of(l), adam_of(l2)) : go(store_of(l), store_of(l2));
+                    // (Adam in the epilogues: these launches take no pending segment)
+                    const hipError_t he = bn.with_grad_epi<false>(i, fused, [&](auto e1) -> hipError_t {
+                        if (with_fold) e1.loss = foldv;                   // block 0 of the launch runs e1's problem
+                        if (j < 0) return bn.wgrad(i, krows, e1, nullptr);
+                        const Layer& l2 = bn.layer(j);
+                        return gemm_wgrad_pair(bn.dz(i), l.n_out_pad, bn.x(i), l.ld, l.n_out_pad, l.ld, e1, bn.dz(j), l2.n_out_pad,
+                                               bn.x(j), l2.ld, l2.n_out_pad, l2.ld, bn.like(e1, j), krows, st);
+                    });
                     if (he != hipSuccess) rc2 = fail(-10, "weight-gradient launch: %s", hipGetErrorString(he));
                 }
                 g_prof.end(pw, st);
                 return rc2;
-            });
-            sref.ready_off = N->layers[lo].w_off;
-            sref.ready_cnt = N->layers[i].b_off + N->layers[i].n_out_pad - N->layers[lo].w_off;
-            sref.net = n;
+            }), lo, i);
             i = lo - 1;
         }
     }

@@ -254,6 +254,140 @@ int flush_pending_adam(pvae_ctx* c, hipStream_t st) {
     return rc;
 }
 
+// ---- the backward plan of one stack at lookahead 1 ---------------------------------------------------------------
+// What the schedules below launch: the stack's BwdNet on row block 0, and what this call of plan_backward_net was told.
+struct NetPass {
+    BwdNet bn;
+    int rows_pad;
+    bool input_grad, fused;
+    bool can_defer;                // a stored gradient's update may ride in a later launch (can_defer_adam)
+    bool wide_follows_layer0;
+    bool dx0;                      // direct step: the weight gradient of layer 0 contracts over the gathered input (XSrc), not over a staged panel
+    XSrc xs0;
+    LossFinal fold;                // executed by the blocks of the launch planned `with_fold`
+    InputSeed seed;
+    bool has_dgrad(int i) const { return i > 0 || input_grad; }
+    int dgrad(int i) const;
+    int wgrad(int i, int j, bool with_fold) const;
+    int wgrad_pair10(bool with_fold) const;
+    int wgrad_last0(bool with_fold) const;
+};
+
+// The seeded input gradient of layer 0: only the input columns the seed consumes are contracted (a 32-aligned window
+// of W_0), and the seed's epilogue counts its columns from the window's first one.
+template <class Seed>
+struct SeededW0 { const float* W; int width; Seed epi; };
+template <class Seed>
+static SeededW0<Seed> seeded_w0(const BwdNet& bn, Seed e, int cols) {
+    const SeedWindow sw = seed_window(e.c0, cols);
+    e.c0 -= sw.lo;
+    return SeededW0<Seed>{bn.c->params + bn.layer(0).w_off + sw.lo, sw.width, e};
+}
+
+int NetPass::dgrad(int i) const {
+    if (i > 0 || seed.kind == 0) return bn.dgrad(i, 0, rows_pad);
+    const Layer& l = bn.layer(0);
+    const int ps = g_prof.begin(1, 2.0 * bn.rowsf * bn.dgrad_cols(0) * l.n_out, bn.st);
+    if (seed.kind == 1) {
+        const auto s = seeded_w0(bn, seed.a, seed.a.n);
+        HIP_TRY(gemm_dgrad_epi(bn.dz(0), l.n_out_pad, s.W, l.ld, rows_pad, s.width, l.n_out_pad, s.epi, bn.st));
+    } else {
+        const auto s = seeded_w0(bn, seed.s, seed.s.Z);
+        HIP_TRY(gemm_dgrad_epi(bn.dz(0), l.n_out_pad, s.W, l.ld, rows_pad, s.width, l.n_out_pad, s.epi, bn.st));
+    }
+    g_prof.end(ps, bn.st);
+    return 0;
+}
+
+// wgrad of layer i, optionally fused with the dgrad of layer j (j < 0: alone).  In a fused pair
+// that is not the step's last launch the gradient is stored and Adam deferred to workgroups of
+// the next weight-gradient launch (AdamSeg); every launch carries whatever is pending.
+int NetPass::wgrad(int i, int j, bool with_fold) const {
+    pvae_ctx* c = bn.c;
+    const Layer& l = bn.layer(i);
+    const int last = bn.last();
+    // (j == i: the launch also reads W_i, so the update MUST wait for the next one)
+    const bool defer = can_defer && j >= 0 && (!with_fold || j == i);
+    // (narrow launches -- a stack's last and first layer -- hand a big pending update on to the next hidden-layer
+    //  pair of the step, when there is one: take_pending)
+    const bool narrow = j == i && !with_fold && ((i == last && last >= 2) || (i == 0 && wide_follows_layer0));
+    auto go = [&](auto e) -> int {
+        if (with_fold) e.loss = fold;
+        const AdamPair ad = take_pending(c, narrow ? kTakeSmall : kTakeAll);
+        if (j >= 0) {
+            const Layer& d = bn.layer(j);
+            const int pp = g_prof.begin(3, 2.0 * bn.rowsf * ((double)l.n_in * l.n_out + (double)bn.dgrad_cols(j) * d.n_out), bn.st);
+            if (j == 0 && seed.kind == 2) {
+                const auto s = seeded_w0(bn, seed.s, seed.s.Z);
+                if (dx0)                  // (i == 0 too: the decoder's first layer, X = [s_t | z] gathered)
+                    HIP_TRY(gemm_bwd_pair_epi_gather(bn.dz(0), d.n_out_pad, s.W, d.ld, rows_pad, s.width, d.n_out_pad, s.epi, bn.dz(i),
+                                                     l.n_out_pad, xs0, l.n_out_pad, l.ld, rows_pad, e, bn.st, &ad));
+                else
+                    HIP_TRY(gemm_bwd_pair_epi(bn.dz(0), d.n_out_pad, s.W, d.ld, rows_pad, s.width, d.n_out_pad, s.epi, bn.dz(i),
+                                              l.n_out_pad, bn.x(i), l.ld, l.n_out_pad, l.ld, rows_pad, e, bn.st, &ad));
+            } else {
+                HIP_TRY(bn.wgrad_with_dgrad(i, rows_pad, bn.dgrad_args(j, 0, rows_pad), e, ad));
+            }
+            g_prof.end(pp, bn.st);
+        } else {
+            const int pw = g_prof.begin(2, 2.0 * bn.rowsf * l.n_in * l.n_out, bn.st);
+            HIP_TRY(bn.wgrad(i, rows_pad, e, &ad));
+            g_prof.end(pw, bn.st);
+        }
+        return 0;
+    };
+    // (with_grad_epi plus the deferring arm, spelt out: the code object holds this unit's kernels in the order in which
+    //  the unit first names their launchers, and this is the order it has had -- docs/experiments.md, "Device code, byte for byte")
+    if (!fused) return c->grad_accum ? go(bn.accum_epi(i)) : go(bn.store_epi(i));
+    if (!defer) return go(bn.adam_epi(i));
+    const int rc = go(bn.store_epi(i));
+    if (rc == 0) c->pending_adam = bn.adam_seg(i);
+    return rc;
+}
+
+// The step's last launch of a stack without input gradient: the loss finalisation, the pending update and the gather
+// of the next minibatch ride in it.  One-behind schedule: layers 1 and 0 in one launch ...
+int NetPass::wgrad_pair10(bool with_fold) const {
+    pvae_ctx* c = bn.c;
+    const Layer& l1 = bn.layer(1);
+    const Layer& l0 = bn.layer(0);
+    const int pw2 = g_prof.begin(2, 2.0 * bn.rowsf * ((double)l1.n_in * l1.n_out + (double)l0.n_in * l0.n_out), bn.st);
+    const int rc = bn.with_grad_epi(1, fused, [&](auto e1) -> int {
+        if (with_fold) e1.loss = fold;            // block 0 of the launch belongs to the first problem
+        // the step's LAST launch also gathers the next minibatch into the alternate panels
+        const bool carry = with_fold && c->next_stage.rows_pad > 0;
+        const AdamPair ad = take_pending(c);
+        HIP_TRY(gemm_wgrad_pair(bn.dz(1), l1.n_out_pad, bn.x(1), l1.ld, l1.n_out_pad, l1.ld, e1, bn.dz(0), l0.n_out_pad, bn.x(0),
+                                l0.ld, l0.n_out_pad, l0.ld, bn.like(e1, 0), rows_pad, bn.st, carry ? &c->next_stage : nullptr, &ad));
+        if (carry) c->next_carried = true;
+        return 0;
+    });
+    g_prof.end(pw2, bn.st);
+    return rc;
+}
+// ... same-layer schedule: layer 0 alone
+int NetPass::wgrad_last0(bool with_fold) const {
+    pvae_ctx* c = bn.c;
+    const Layer& l0 = bn.layer(0);
+    const int pw = g_prof.begin(2, 2.0 * bn.rowsf * l0.n_in * l0.n_out, bn.st);
+    const int rc = bn.with_grad_epi(0, fused, [&](auto e0) -> int {
+        if (with_fold) e0.loss = fold;
+        const bool carry = with_fold && c->next_stage.rows_pad > 0;
+        const AdamPair ad = take_pending(c);
+        if (dx0) {                        // X gathered from the demonstration set: nothing was staged, nothing to stage
+            HIP_TRY(gemm_wgrad_pair_gather(bn.dz(0), l0.n_out_pad, xs0, l0.n_out_pad, l0.ld, e0, rows_pad, bn.st, &ad,
+                                           with_fold && c->next_touch.blocks > 0 ? &c->next_touch : nullptr));
+            return 0;
+        }
+        HIP_TRY(gemm_wgrad_pair(bn.dz(0), l0.n_out_pad, bn.x(0), l0.ld, l0.n_out_pad, l0.ld, e0, (const float*)nullptr, 0,
+                                (const float*)nullptr, 0, 0, l0.ld, e0, rows_pad, bn.st, carry ? &c->next_stage : nullptr, &ad));
+        if (carry) c->next_carried = true;
+        return 0;
+    });
+    g_prof.end(pw, bn.st);
+    return rc;
+}
+
 // dz[last] must be filled.  Layer by layer, last to first: the input gradient of layer i reads
 // W_i; a weight gradient of layer i with Adam in its epilogue overwrites W_i.  Two schedules:
 //  * same layer (the default whenever the update can be deferred, and for the gradient-store path
@@ -264,272 +398,93 @@ int flush_pending_adam(pvae_ctx* c, hipStream_t st) {
 //    dgrad_{i-1} (needs dz_{i-1}, W_{i-1}) and wgrad_i (needs dz_i, x_i; writes W_i) are independent:
 //        dgrad_L | dgrad_{L-1} + wgrad_L | ... | dgrad_1 + wgrad_2 | [dgrad_0] + wgrad_1 | wgrad_0
 //    (without an input gradient the two last weight gradients share a launch).
-// `fold` (optional) is executed by the blocks of the last launch.
-void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool input_grad, const pvae_step_params* sp, bool fused,
-                       hipStream_t st, const LossFinal* fold, Plan& plan, const InputSeed* seed, CarriedWgrad* carry_out,
-                       const CarriedWgrad* carry_in, bool wide_follows_layer0) {
-    const NetLayout* N = &c->L.net[n];
-    const NetWork* w = &c->W.net[n];
-    const AdamScalars as = adam_scalars(sp, n);
-    const int last = (int)N->layers.size() - 1;
-    const bool pair = train && c->pair_launch;
-    const double rowsf = c->staged_rows_f;
-    // act_grad code of the layer whose output masks the input gradient of layer i (layer i - 1; none for i == 0)
-    auto mask_act = [=](int i) { return i > 0 ? N->layers[i - 1].act : 1; };
-    const int need = n == PVAE_NET_WM ? c->L.cfg.dim_action : c->L.cfg.latent;
-    // direct step: the weight gradient of layer 0 contracts over the gathered input (XSrc), not over a staged panel
-    const bool dx0 = c->dx.on && train && n != PVAE_NET_PR;
-    const XSrc xs0 = dx0 ? xsrc_of(c, n, n == PVAE_NET_WM ? PVAE_PHASE_WORLD : PVAE_PHASE_JOINT, true, (int)c->staged_rows_f) : XSrc();
-    LossFinal foldv;
-    memset(&foldv, 0, sizeof(foldv));
-    if (fold) foldv = *fold;
-    InputSeed seedv;
-    if (seed) seedv = *seed;
-
-    auto has_dgrad = [=](int i) { return i > 0 || input_grad; };
-    auto seg_of = [=](int lo, int hi, Stage& s) {       // layers lo..hi (lo <= hi) of this net
-        s.ready_off = N->layers[lo].w_off;
-        s.ready_cnt = N->layers[hi].b_off + N->layers[hi].n_out_pad - N->layers[lo].w_off;
-        s.net = n;
-    };
-    // dgrad of layer i: dz[i] (.) W_i -> dz[i-1] (masked) or d_in (i == 0, unmasked)
-    auto dgrad = [=](int i) -> int {
-        const Layer& l = N->layers[i];
-        const float* xin = i == 0 ? c->ws + w->in : c->ws + w->act[i - 1];
-        const int ps = g_prof.begin(1, 2.0 * rowsf * (i > 0 ? l.n_in : need) * l.n_out, st);
-        if (i == 0 && seedv.kind == 1) {
-            // only the input columns the seed consumes are contracted (a 32-aligned window of W_0)
-            const SeedWindow sw = seed_window(seedv.a.c0, seedv.a.n);
-            EpiActionSeed e = seedv.a;
-            e.c0 -= sw.lo;
-            HIP_TRY(gemm_dgrad_epi(c->ws + w->dz[0], l.n_out_pad, c->params + l.w_off + sw.lo, l.ld, rows_pad, sw.width,
-                                   l.n_out_pad, e, st));
-        } else if (i == 0 && seedv.kind == 2) {
-            const SeedWindow sw = seed_window(seedv.s.c0, seedv.s.Z);
-            EpiSamplerSeed e = seedv.s;
-            e.c0 -= sw.lo;
-            HIP_TRY(gemm_dgrad_epi(c->ws + w->dz[0], l.n_out_pad, c->params + l.w_off + sw.lo, l.ld, rows_pad, sw.width,
-                                   l.n_out_pad, e, st));
-        } else {
-            HIP_TRY(gemm_dgrad(c->ws + w->dz[i], l.n_out_pad, c->params + l.w_off, l.ld, i > 0 ? xin : nullptr, l.ld,
-                               i > 0 ? c->ws + w->dz[i - 1] : c->ws + w->d_in, l.ld, rows_pad, l.ld, l.n_out_pad, st, mask_act(i)));
-        }
-        g_prof.end(ps, st);
-        return 0;
-    };
-    auto adam_epi = [=](const Layer& l) {
-        EpiGradAdam e{c->params + l.w_off, c->m + l.w_off, c->v + l.w_off, l.ld, as};
-        e.b = c->params + l.b_off; e.bm = c->m + l.b_off; e.bv = c->v + l.b_off;
-        return e;
-    };
-    auto store_epi = [=](const Layer& l) {
-        EpiGradStore e{c->grads + l.w_off, l.ld};
-        e.gb = c->grads + l.b_off;
-        return e;
-    };
-    auto accum_epi = [=](const Layer& l) {
-        EpiGradAccum e{c->grads + l.w_off, l.ld};
-        e.gb = c->grads + l.b_off;
-        return e;
-    };
-    // wgrad of layer i, optionally fused with the dgrad of layer j (j < 0: alone).  In a fused pair
-    // that is not the step's last launch the gradient is stored and Adam deferred to workgroups of
-    // the next weight-gradient launch (AdamSeg); every launch carries whatever is pending.
-    const bool can_defer = fused && c->defer_adam && c->grads != nullptr;
-    auto wgrad = [=](int i, int j, bool with_fold) -> int {
-        const Layer& l = N->layers[i];
-        const float* dz = c->ws + w->dz[i];
-        const float* xin = i == 0 ? c->ws + w->in : c->ws + w->act[i - 1];
-        // (j == i: the launch also reads W_i, so the update MUST wait for the next one)
-#ifdef PVAE_DIAG_EPI_ADAM
-        // TIMING-ONLY diagnostic build (docs/experiments.md, round 5): Adam in the epilogue of the same-layer pair, as a
-        // second ("ping-pong") parameter arena would allow -- here it overwrites the W_i that the pair's input-gradient half
-        // is reading, so the results are wrong; launches, traffic and epilogues are those of the ping-pong schedule.
-        const bool defer = can_defer && j >= 0 && j != i && !with_fold;
-#else
-        const bool defer = can_defer && j >= 0 && (!with_fold || j == i);
-#endif
-        // (narrow launches -- a stack's last and first layer -- hand a big pending update on to the next hidden-layer
-        //  pair of the step, when there is one: take_pending)
-        const bool narrow = j == i && !with_fold && ((i == last && last >= 2) || (i == 0 && wide_follows_layer0));
-        auto go = [&](auto e) -> int {
-            if (with_fold) e.loss = foldv;
-            const AdamPair ad = take_pending(c, narrow ? kTakeSmall : kTakeAll);
-            if (j >= 0) {
-                const Layer& d = N->layers[j];
-                const float* dx_in = j == 0 ? c->ws + w->in : c->ws + w->act[j - 1];
-                const int pp = g_prof.begin(3, 2.0 * rowsf * ((double)l.n_in * l.n_out +
-                                               (double)(j > 0 ? d.n_in : need) * d.n_out), st);
-                if (j == 0 && seedv.kind == 2) {
-                    const SeedWindow sw = seed_window(seedv.s.c0, seedv.s.Z);
-                    EpiSamplerSeed es = seedv.s;
-                    es.c0 -= sw.lo;
-                    if (dx0)                  // (i == 0 too: the decoder's first layer, X = [s_t | z] gathered)
-                        HIP_TRY(gemm_bwd_pair_epi_gather(c->ws + w->dz[0], d.n_out_pad, c->params + d.w_off + sw.lo, d.ld, rows_pad,
-                                                         sw.width, d.n_out_pad, es, dz, l.n_out_pad, xs0, l.n_out_pad, l.ld,
-                                                         rows_pad, e, st, &ad));
-                    else
-                    HIP_TRY(gemm_bwd_pair_epi(c->ws + w->dz[0], d.n_out_pad, c->params + d.w_off + sw.lo, d.ld, rows_pad,
-                                              sw.width, d.n_out_pad, es, dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld,
-                                              rows_pad, e, st, &ad));
-                } else {
-                    HIP_TRY(gemm_bwd_pair(c->ws + w->dz[j], d.n_out_pad, c->params + d.w_off, d.ld,
-                                          j > 0 ? dx_in : nullptr, d.ld, j > 0 ? c->ws + w->dz[j - 1] : c->ws + w->d_in,
-                                          d.ld, rows_pad, d.ld, d.n_out_pad, dz, l.n_out_pad, xin, l.ld, l.n_out_pad,
-                                          l.ld, rows_pad, e, st, &ad, mask_act(j)));
-                }
-                g_prof.end(pp, st);
-            } else {
-                const int pw = g_prof.begin(2, 2.0 * rowsf * l.n_in * l.n_out, st);
-                HIP_TRY(gemm_wgrad(dz, l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, rows_pad, e, st, &ad));
-                g_prof.end(pw, st);
-            }
-            return 0;
-        };
-        if (!fused) return c->grad_accum ? go(accum_epi(l)) : go(store_epi(l));
-        if (!defer) return go(adam_epi(l));
-        const int rc = go(store_epi(l));
-        if (rc == 0) {
-            AdamSeg a;
-            a.p = c->params + l.w_off; a.g = c->grads + l.w_off; a.m = c->m + l.w_off; a.v = c->v + l.w_off;
-            a.n4 = (l.b_off + l.n_out_pad - l.w_off) / 4;
-            a.s = as;
-            c->pending_adam = a;
-        }
-        return rc;
-    };
-    auto wgrad_pair10 = [=](bool with_fold) -> int {    // layers 1 and 0 in one launch
-        const Layer& l1 = N->layers[1];
-        const Layer& l0 = N->layers[0];
-        const int pw2 = g_prof.begin(2, 2.0 * rowsf * ((double)l1.n_in * l1.n_out + (double)l0.n_in * l0.n_out), st);
-        auto go = [&](auto e1, auto e0) -> int {
-            if (with_fold) e1.loss = foldv;            // block 0 of the launch belongs to the first problem
-            // the step's LAST launch also gathers the next minibatch into the alternate panels
-            const bool carry = with_fold && c->next_stage.rows_pad > 0;
-            const AdamPair ad = take_pending(c);
-            HIP_TRY(gemm_wgrad_pair(c->ws + w->dz[1], l1.n_out_pad, c->ws + w->act[0], l1.ld, l1.n_out_pad, l1.ld, e1,
-                                    c->ws + w->dz[0], l0.n_out_pad, c->ws + w->in, l0.ld, l0.n_out_pad, l0.ld, e0,
-                                    rows_pad, st, carry ? &c->next_stage : nullptr, &ad));
-            if (carry) c->next_carried = true;
-            return 0;
-        };
-        const int rc = fused ? go(adam_epi(l1), adam_epi(l0))
-                             : (c->grad_accum ? go(accum_epi(l1), accum_epi(l0)) : go(store_epi(l1), store_epi(l0)));
-        g_prof.end(pw2, st);
-        return rc;
-    };
-
-    // layer 0 alone (same-layer schedule): the step's last launch of a stack without input gradient;
-    // carries the loss finalisation, the pending update and the gather of the next minibatch
-    auto wgrad_last0 = [=](bool with_fold) -> int {
-        const Layer& l0 = N->layers[0];
-        const int pw = g_prof.begin(2, 2.0 * rowsf * l0.n_in * l0.n_out, st);
-        auto go = [&](auto e0) -> int {
-            if (with_fold) e0.loss = foldv;
-            const bool carry = with_fold && c->next_stage.rows_pad > 0;
-            const AdamPair ad = take_pending(c);
-            if (dx0) {                        // X gathered from the demonstration set: nothing was staged, nothing to stage
-                HIP_TRY(gemm_wgrad_pair_gather(c->ws + w->dz[0], l0.n_out_pad, xs0, l0.n_out_pad, l0.ld, e0, rows_pad, st, &ad,
-                                               with_fold && c->next_touch.blocks > 0 ? &c->next_touch : nullptr));
-                return 0;
-            }
-            HIP_TRY(gemm_wgrad_pair(c->ws + w->dz[0], l0.n_out_pad, c->ws + w->in, l0.ld, l0.n_out_pad, l0.ld, e0,
-                                    (const float*)nullptr, 0, (const float*)nullptr, 0, 0, l0.ld, e0,
-                                    rows_pad, st, carry ? &c->next_stage : nullptr, &ad));
-            if (carry) c->next_carried = true;
-            return 0;
-        };
-        const int rc = fused ? go(adam_epi(l0)) : (c->grad_accum ? go(accum_epi(l0)) : go(store_epi(l0)));
-        g_prof.end(pw, st);
-        return rc;
-    };
-
-    auto push = [&](std::function<int()> f) -> Stage& {
-        plan.emplace_back();
-        plan.back().run = std::move(f);
-        return plan.back();
-    };
-    if (!train) {
-        for (int i = last; i >= 0; --i)
-            if (has_dgrad(i)) push([=] { return dgrad(i); });
-        return;
+// `fold`: the blocks of the stack's last launch execute NetPass::fold.
+static void plan_dgrad_only(const NetPass& p, Plan& plan) {             // a frozen stack
+    for (int i = p.bn.last(); i >= 0; --i)
+        if (p.has_dgrad(i)) push(plan, [=] { return p.dgrad(i); });
+}
+static void plan_unpaired(const NetPass& p, bool fold, Plan& plan) {    // PVAE_PAIR=0: every contraction its own launch
+    for (int i = p.bn.last(); i >= 0; --i) {
+        if (p.has_dgrad(i)) push(plan, [=] { return p.dgrad(i); });
+        const bool f = fold && i == 0;
+        p.bn.ready(push(plan, [=] { return p.wgrad(i, -1, f); }), i, i);
     }
-    if (!pair) {
-        for (int i = last; i >= 0; --i) {
-            if (has_dgrad(i)) push([=] { return dgrad(i); });
-            const bool f = fold && i == 0;
-            seg_of(i, i, push([=] { return wgrad(i, -1, f); }));
-        }
-        return;
+}
+// Same-layer schedule: with the update deferred (or no update at all: gradient store for the
+// data-parallel exchange) wgrad_i no longer writes W_i, so it shares a launch with dgrad_i
+// instead of trailing one launch behind it:
+//     dgrad_L + wgrad_L | dgrad_{L-1} + wgrad_{L-1} [+ Adam_L] | ... | wgrad_0 [+ Adam_1]
+// The short first launch (K = output width) and the short last one (narrow layer 0) each get
+// a partner of their own size, instead of a lone short launch at one end and two narrow
+// problems in one launch at the other.
+static void plan_same_layer(const NetPass& p, bool fold, Plan& plan) {
+    for (int i = p.bn.last(); i >= 0; --i) {
+        const bool f = fold && i == 0;
+        if (p.has_dgrad(i)) p.bn.ready(push(plan, [=] { return p.wgrad(i, i, f); }), i, i);
+        else p.bn.ready(push(plan, [=] { return p.wgrad_last0(f); }), 0, 0);
     }
-    if ((!fused || can_defer) && c->same_layer_pairs) {
-        // Same-layer schedule: with the update deferred (or no update at all: gradient store for the
-        // data-parallel exchange) wgrad_i no longer writes W_i, so it shares a launch with dgrad_i
-        // instead of trailing one launch behind it:
-        //     dgrad_L + wgrad_L | dgrad_{L-1} + wgrad_{L-1} [+ Adam_L] | ... | wgrad_0 [+ Adam_1]
-        // The short first launch (K = output width) and the short last one (narrow layer 0) each get
-        // a partner of their own size, instead of a lone short launch at one end and two narrow
-        // problems in one launch at the other.
-        for (int i = last; i >= 0; --i) {
-            const bool f = fold && i == 0;
-            if (has_dgrad(i)) seg_of(i, i, push([=] { return wgrad(i, i, f); }));
-            else seg_of(0, 0, push([=] { return wgrad_last0(f); }));
-        }
-        return;
-    }
-    if (has_dgrad(last)) {
+}
+// One behind.  A lone trailing weight gradient (`carry_out`, no fold) is handed to the next stack's plan, whose first
+// input gradient (`carry_in`) it then shares a launch with.
+static void plan_one_behind(const NetPass& p, bool fold, Plan& plan, CarriedWgrad* carry_out, const CarriedWgrad* carry_in) {
+    const BwdNet bn = p.bn;
+    const int last = bn.last(), rows_pad = p.rows_pad;
+    if (p.has_dgrad(last)) {
         if (carry_in && carry_in->valid) {
             // the previous stack's trailing weight gradient rides with this stack's first input gradient
             const CarriedWgrad cw = *carry_in;
-            const Layer& l = N->layers[last];
-            DgradArgs da{c->ws + w->dz[last], l.n_out_pad, c->params + l.w_off, l.ld,
-                         last > 0 ? c->ws + w->act[last - 1] : nullptr, l.ld,
-                         last > 0 ? c->ws + w->dz[last - 1] : c->ws + w->d_in, l.ld, rows_pad, l.ld, l.n_out_pad,
-                         2.0 * rowsf * l.n_in * l.n_out, mask_act(last)};
-            Stage& sref = push([=] { return cw.run_with_dgrad(da); });
+            const DgradArgs da = bn.dgrad_args(last, 0, rows_pad);
+            Stage& sref = push(plan, [=] { return cw.run_with_dgrad(da); });
             sref.ready_off = cw.ready_off; sref.ready_cnt = cw.ready_cnt; sref.net = cw.net;
         } else {
-            push([=] { return dgrad(last); });
+            push(plan, [=] { return p.dgrad(last); });
         }
     }
     for (int i = last; i >= 0; --i) {
         const int j = i - 1;                       // dgrad_{i-1} rides with wgrad_i
-        if (j >= 0 && has_dgrad(j)) {
+        if (j >= 0 && p.has_dgrad(j)) {
             const bool f = fold && i == 0;
-            seg_of(i, i, push([=] { return wgrad(i, j, f); }));
-        } else if (i == 1 && !has_dgrad(0)) {
-            const bool f = fold != nullptr;
-            seg_of(0, 1, push([=] { return wgrad_pair10(f); }));
+            bn.ready(push(plan, [=] { return p.wgrad(i, j, f); }), i, i);
+        } else if (i == 1 && !p.has_dgrad(0)) {
+            bn.ready(push(plan, [=] { return p.wgrad_pair10(fold); }), 0, 1);
             return;
         } else if (i == 0 && carry_out && !fold) {
             // hand the lone trailing weight gradient to the next stack's plan
-            const Layer& l = N->layers[0];
-            const float* dz = c->ws + w->dz[0];
-            const float* xin = c->ws + w->in;
+            const bool fused = p.fused;
             carry_out->valid = true;
-            carry_out->ready_off = l.w_off;
-            carry_out->ready_cnt = l.b_off + l.n_out_pad - l.w_off;
-            carry_out->net = n;
+            bn.ready(*carry_out, 0, 0);
             carry_out->run_with_dgrad = [=](const DgradArgs& d) -> int {
-                const int pp = g_prof.begin(3, d.flops + 2.0 * rowsf * l.n_in * l.n_out, st);
-                hipError_t he;
-                const AdamPair ad = take_pending(c);
-                if (fused) {
-                    he = gemm_bwd_pair(d.dZ, d.ldz, d.W, d.ldw, d.mask, d.ldm, d.dX, d.ldo, d.M, d.Kin, d.Nd, dz,
-                                       l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, rows_pad, adam_epi(l), st, &ad, d.act);
-                } else {
-                    he = gemm_bwd_pair(d.dZ, d.ldz, d.W, d.ldw, d.mask, d.ldm, d.dX, d.ldo, d.M, d.Kin, d.Nd, dz,
-                                       l.n_out_pad, xin, l.ld, l.n_out_pad, l.ld, rows_pad, store_epi(l), st, &ad, d.act);
-                }
-                g_prof.end(pp, st);
+                const Layer& l = bn.layer(0);
+                const int pp = g_prof.begin(3, d.flops + 2.0 * bn.rowsf * l.n_in * l.n_out, bn.st);
+                const AdamPair ad = take_pending(bn.c);
+                // (Adam or store, never the accumulating form; spelt out for the kernel order, as in NetPass::wgrad)
+                const hipError_t he = fused ? bn.wgrad_with_dgrad(0, rows_pad, d, bn.adam_epi(0), ad)
+                                            : bn.wgrad_with_dgrad(0, rows_pad, d, bn.store_epi(0), ad);
+                g_prof.end(pp, bn.st);
                 if (he != hipSuccess) return fail(-10, "gemm_bwd_pair: %s", hipGetErrorString(he));
                 return 0;
             };
         } else {
             const bool f = fold && i == 0;
-            seg_of(i, i, push([=] { return wgrad(i, -1, f); }));
+            bn.ready(push(plan, [=] { return p.wgrad(i, -1, f); }), i, i);
         }
     }
+}
+
+void plan_backward_net(pvae_ctx* c, int n, int rows_pad, bool train, bool input_grad, const pvae_step_params* sp, bool fused,
+                       hipStream_t st, const LossFinal* fold, Plan& plan, const InputSeed* seed, CarriedWgrad* carry_out,
+                       const CarriedWgrad* carry_in, bool wide_follows_layer0) {
+    NetPass p{BwdNet(c, n, sp, st), rows_pad, input_grad, fused, can_defer_adam(c, fused), wide_follows_layer0};
+    p.bn.dx0_cols = n == PVAE_NET_WM ? c->L.cfg.dim_action : c->L.cfg.latent;
+    p.dx0 = c->dx.on && train && n != PVAE_NET_PR;
+    if (p.dx0) p.xs0 = xsrc_of(c, n, n == PVAE_NET_WM ? PVAE_PHASE_WORLD : PVAE_PHASE_JOINT, true, (int)c->staged_rows_f);
+    memset(&p.fold, 0, sizeof(p.fold));
+    if (fold) p.fold = *fold;
+    if (seed) p.seed = *seed;
+    if (!train) return plan_dgrad_only(p, plan);
+    if (!c->pair_launch) return plan_unpaired(p, fold != nullptr, plan);
+    if ((!fused || p.can_defer) && c->same_layer_pairs) return plan_same_layer(p, fold != nullptr, plan);
+    plan_one_behind(p, fold != nullptr, plan, carry_out, carry_in);
 }
 
 // The sampler of the configured prior kind (rmt:795-819): reparam_kernel (N(mu, s^2); KL to N(0, I) or to

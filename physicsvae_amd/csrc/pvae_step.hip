@@ -206,7 +206,7 @@ static bool direct_ok(const pvae_ctx* c, int phase, int rows, const pvae_step_pa
     // the other OR to 3, which is also what "both" is spelt as
     if (c->L.cfg.te_inputs % 3 != 0 || c->L.cfg.md_inputs % 3 != 0) return false;
     if (!c->L.net[PVAE_NET_MH].layers.empty()) return false;                     // the helper reads the staged decoder panel
-    if (fused && !(c->defer_adam && c->grads)) return false;          // (the same-layer schedule of plan_backward_net)
+    if (fused && !can_defer_adam(c, fused)) return false;             // (the same-layer schedule of plan_backward_net)
     if (Da > ProCols::kMaxN || Z > ProCols::kMaxN || Db < 64 || 2 * Db >= 65536) return false;
     const int rp = pad32(rows);
     // a first layer on 64-row tiles has no Pro patch: its second column block is chunk-selected, which needs dim_body % 4 == 0
@@ -450,8 +450,7 @@ static void plan_backward(pvae_ctx* c, int phase, int rows, const pvae_step_para
     if (!seed_action) {
         const int nparts = S.nparts_a, l1 = S.l1;
         const bool cyc = S.cyc_grad;
-        plan.emplace_back();
-        plan.back().run = [=] { return action_loss_launch(c, rows, 0, 0, 0, nparts, ga, l1, backward, cyc, st); };
+        push(plan, [=] { return action_loss_launch(c, rows, 0, 0, 0, nparts, ga, l1, backward, cyc, st); });
     }
     if (!backward) return;
     const NetLayout* MH = &c->L.net[PVAE_NET_MH];
@@ -460,8 +459,7 @@ static void plan_backward(pvae_ctx* c, int phase, int rows, const pvae_step_para
     if (helper) {
         // d a_hat (just formed above: reconstruction + what came back through the world model) -> the helper's output layer,
         // then the helper's own backward: trained like the decoder (adam_t[PVAE_NET_MH] > 0) or passed through
-        plan.emplace_back();
-        plan.back().run = [=] { return helper_seed_launch(c, rows, 0, st); };
+        push(plan, [=] { return helper_seed_launch(c, rows, 0, st); });
         plan_backward_net(c, PVAE_NET_MH, S.rows_pad, sp->adam_t[PVAE_NET_MH] > 0, true, sp, fused, st, nullptr, plan);
     }
     const float kls = S.kl_active ? sp->kl_coeff / S.Bg : 0.0f;
@@ -486,8 +484,7 @@ static void plan_backward(pvae_ctx* c, int phase, int rows, const pvae_step_para
                       !learned_prior && TE->layers.size() >= 3);
     if (!seed_sampler) {
         const int rows_pad = S.rows_pad;
-        plan.emplace_back();
-        plan.back().run = [=]() -> int {
+        push(plan, [=]() -> int {
             int rc = 0;                        // z feeds the helper too: its input gradient joins the decoder's
             if (helper && (rc = add_cols_launch(w + wmd->d_in + Db, MD->layers[0].ld, rows, Z, w + wmh->d_in + Db, MH->layers[0].ld,
                                                 nullptr, 0, nullptr, 0, nullptr, 0, st)))
@@ -498,7 +495,7 @@ static void plan_backward(pvae_ctx* c, int phase, int rows, const pvae_step_para
                                w + wte->dz.back(), TE->layers.back().n_out_pad, rows, rows_pad, Z, kls, sphere_norm);
             HIP_TRY(hipGetLastError());
             return 0;
-        };
+        });
     }
     // the learned prior mean trains through the KL term only (its output gradient was written beside the
     // encoder's by the sampler backward above); no input gradient

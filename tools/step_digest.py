@@ -5,13 +5,16 @@ rows 1 / 4 / 33 / 64 (the GEMV path, pad rows, two row tiles), both phases, look
 a helper stack, fused Adam and store + Adam, the backward pass stage by stage, evaluation, the prefetch, direct and
 data-parallel steps (the direct step needs Db >= 64, Z % 4 == 0 and first layers on 32-row tiles: Db 68, Z 4, 256 rows, 512
 wide; `direct_active` in its scenarios says whether the library took that path), rollout at 1 - 8 rows, the per-stack
-forward / backward, the sampler and its backward, and one step at 1024 rows x 1024 wide.  Prints one JSON line:
-scenario -> output tensor -> sha256 of its raw bytes.  The library is the in-tree one, or the one PVAE_LIB_PATH names:
+forward / backward, the sampler and its backward, one step at 1024 rows x 1024 wide, and the non-default backward schedules
+(`schedules`: contexts created under PVAE_PAIR=0, PVAE_SAME_LAYER=0, PVAE_DEFER_ADAM=0 and the last two together, each with
+what `pvae_backward_plan` returns beside the digests).  Prints one JSON line: scenario -> output tensor -> sha256 of its raw
+bytes (`plan`: the stage list itself, [net, offset, count] per stage).  The library is the in-tree one, or the one PVAE_LIB_PATH names:
 
     python tools/step_digest.py > new.json;  PVAE_LIB_PATH=/path/to/other/libpvae_gfx950.so python tools/step_digest.py > old.json
 
 The digests belong to one compiler and one pair of builds: they are compared, never pinned.
 """
+import contextlib
 import hashlib
 import json
 import os
@@ -272,6 +275,82 @@ def wide(out):
         out["wide phase%d" % phase] = state(eng, 1024, l)
 
 
+SCHEDULES = (("pair0", {"PVAE_PAIR": "0"}), ("same_layer0", {"PVAE_SAME_LAYER": "0"}), ("defer_adam0", {"PVAE_DEFER_ADAM": "0"}),
+             ("same_layer0+defer_adam0", {"PVAE_SAME_LAYER": "0", "PVAE_DEFER_ADAM": "0"}))
+# hidden layers per stack, every stack once at every depth.  One hidden layer is the shallowest stack a context accepts
+# (two layers: with no input gradient its two weight gradients share the last launch), two make the three-layer stack whose
+# last layer is a narrow launch in front of a hidden-layer pair, three add a second pair.
+DEPTHS = ({"te": (17, 1), "md": (64, 2), "wm": (129, 3)}, {"te": (17, 3), "md": (64, 1), "wm": (129, 2)},
+          {"te": (17, 2), "md": (64, 3), "wm": (129, 1)})
+
+
+@contextlib.contextmanager
+def context_env(env):
+    """The per-context switches as `_lib.apply_context_options` reads them: a context created inside keeps them."""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def schedules(out):
+    """The three non-default schedules of plan_backward_net (unpaired, one behind with and without a gradient arena's
+    deferral) and what they make of the unroll, at the small shapes: both phases, lookahead 1 and 3, fused Adam and store,
+    33 and 64 rows, every stack at every depth, a helper stack trained and frozen, a learned prior (a stack without input
+    gradient ahead of the encoder), the zero-mean prior of the default model (the seeded first-layer input gradients and,
+    one behind, the weight gradient carried from the decoder's plan into the encoder's), and the direct step wherever
+    the schedule admits it (`direct_active`)."""
+    def step(eng, tag, phase, rows, fused, seed, **kw):
+        sp = params_of(phase, **kw)
+        fill(eng, seed)
+        eng.gather(3, rows)
+        l = eng.forward_backward(phase, rows, sp, eps_for(eng, rows), fused_adam=fused, loss_out=torch.zeros(5, device=DEV))
+        out[tag] = dict(state(eng, rows, l), plan=[list(s) for s in eng.backward_plan(phase, sp)])
+
+    for name, env in SCHEDULES:
+        with context_env(env):
+            for look in (1, 3):
+                for d, depths in enumerate(DEPTHS):
+                    eng = make(lookahead=look, **depths)
+                    for rows in (33, 64):
+                        for phase in (W, J):
+                            for fused in (True, False):
+                                step(eng, "schedule %s look%d depths%d rows%d phase%d fused%d" % (name, look, d, rows, phase, fused),
+                                     phase, rows, fused, 16)
+                eng = make(mh=(17, 1), lookahead=look)
+                for trained in (1, 0):
+                    for phase in (W, J):
+                        for fused in (True, False):
+                            step(eng, "schedule %s look%d helper trained%d phase%d fused%d" % (name, look, trained, phase, fused),
+                                 phase, 33, fused, 17, helper_t=trained)
+            eng = make(prior=PRIORS[1])
+            for fused in (True, False):
+                step(eng, "schedule %s learned_prior fused%d" % (name, fused), J, 33, fused, 18)
+            # the direct step (train_steps' shapes): taken where the schedule pairs same-layer and, fused, can defer Adam
+            eng = make(Db=68, Z=4, te=(512, 1), md=(512, 2), wm=(512, 1), max_batch=256, direct=True, episodes=(300, 100, 300))
+            for phase in (W, J):
+                sp = params_of(phase)
+                fill(eng, 19)
+                l = eng.train_step(phase, 100, 256, sp, eps_for(eng, 256), loss_out=torch.zeros(5, device=DEV))
+                out["schedule %s direct train_step phase%d" % (name, phase)] = dict(
+                    state(eng, 256, l), plan=[list(s) for s in eng.backward_plan(phase, sp)],
+                    direct_active=int(eng.direct_active(phase, 256, sp)), direct_active_store=int(eng.direct_active(phase, 256, sp, fused=False)))
+            if eng.direct_active(W, 256, params_of(W), fused=False):      # (the data-parallel step stores its gradients)
+                eng.comm_init(0, 1, eng.comm_unique_id())
+                for phase in (W, J):
+                    fill(eng, 19)
+                    l = eng.dp_train_step(phase, 100, 256, params_of(phase), eps_for(eng, 256), loss_out=torch.zeros(5, device=DEV),
+                                          next_span=(200, 256)).clone()
+                    out["schedule %s direct dp_train_step phase%d" % (name, phase)] = state(eng, 256, l)
+                eng.comm_destroy()
+
+
 def main():
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
     out = {}
@@ -279,7 +358,7 @@ def main():
     stdout = os.dup(1)                      # (RCCL greets on the C level's stdout: only the JSON line goes there)
     os.dup2(2, 1)
     try:
-        for scenario in (steps, priors_and_helper, train_steps, rollout, autograd, wide):
+        for scenario in (steps, priors_and_helper, train_steps, rollout, autograd, wide, schedules):
             scenario(out)
     finally:
         os.dup2(stdout, 1)
