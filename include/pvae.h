@@ -1116,6 +1116,37 @@ int pvae_ppo_act(pvae_ctx* ctx, const pvae_ppo_act_in* in, const pvae_gae_params
                  const pvae_ppo_act_out* out, void* stream);
 int pvae_ppo_act_sizeof(int which);
 
+/* ---- Minibatch order of the PPO learner: every pass's row order, drawn on the device from the Philox stream -------------
+ * pvae_fc_ppo_sgd / pvae_ppo_sgd take the row order of every pass as `perm` (NULL: row order, no shuffling).  This call
+ * makes it from a (seed, offset) of the stream the latent draws and the action noise come from, so that the learner's
+ * result is a function of the module's own (seed, call counter).  The rule is the project's own (it is not RLlib's
+ * shuffle) and is integer arithmetic only: `ppo.minibatch_order` reproduces it bit for bit in numpy.  For a train batch of
+ * n_rows rows and pass p of num_sgd_iter:
+ *   w[0..3](g)  = Philox4x32-10(counter = {lo32(offset), hi32(offset), g, 0xC0000000 + p}, key = {lo32(seed), hi32(seed)})
+ *   key32(p, i) = w[i & 3](i >> 2)                  one Philox call serves four consecutive rows
+ *   packed(p,i) = (uint64(key32(p, i)) << 32) | i   unique: equal 32-bit keys are ordered by row
+ *   perm[p]     = the rows i = 0 .. n_rows - 1 sorted by packed(p, i), ascending
+ * Minibatch j of pass p takes rows perm[p][j * mb .. (j + 1) * mb - 1].  The counter's fourth word keeps the order apart
+ * from the other streams at the same offset: latent draws use groups below Z / 4, action noise groups from 0x80000000,
+ * the order groups from 0xC0000000 -- hence num_sgd_iter < 2^30.
+ *
+ * Launches (all on `stream`; no atomics, no workgroup waits for another, no allocation, no host synchronisation):
+ *   n_rows <= 8192   ONE: a workgroup per pass forms the packed keys in LDS (64 KiB), sorts them there (a bitonic network
+ *                    over max(256, next power of two >= n_rows) keys, all-ones keys behind the rows) and writes perm.
+ *   n_rows >  8192   1 + ceil(log2(tiles)), tiles = ceil(n_rows / 8192): the same kernel sorts every tile of every pass into
+ *                    the scratch, then each merge launch doubles the sorted run (every key finds its rank in the sibling
+ *                    run by binary search), ping-pong between the scratch's two buffers; the last one writes perm.
+ * Scratch: 16 bytes (unused) up to 8192 rows; above, two buffers of uint64 [num_sgd_iter][n_rows], one behind the other.
+ *
+ *   pvae_ppo_order_workspace_bytes   size of the scratch, a multiple of 16; 0 on error
+ *   pvae_ppo_order                   perm: device int32 [num_sgd_iter][n_rows].  Returns the number of launches it
+ *                                    enqueued, or a negative code and launches nothing.
+ * Refused with a message, before any HIP call: n_rows < 1 or >= 2^31, num_sgd_iter < 1 or >= 2^30, perm NULL or not
+ * 4-byte aligned, scratch NULL or not 16-byte aligned, scratch_bytes below the size above. */
+size_t pvae_ppo_order_workspace_bytes(int64_t n_rows, int32_t num_sgd_iter);
+int pvae_ppo_order(int64_t n_rows, int32_t num_sgd_iter, uint64_t seed, uint64_t offset, int32_t* perm, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's `roofline` object).
  * While enabled every contraction launch carries an event pair stamped by the device at the
  * kernel's own start and end (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace

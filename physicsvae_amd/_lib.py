@@ -267,6 +267,8 @@ _SIGS = {
     "pvae_fc_ppo_act": (C.c_int, [_P, C.POINTER(PpoActIn), C.POINTER(GaeParams), C.POINTER(PpoActOut), _P]),
     "pvae_ppo_act": (C.c_int, [_P, C.POINTER(PpoActIn), C.POINTER(GaeParams), C.POINTER(PpoDraws), C.POINTER(PpoActOut), _P]),
     "pvae_ppo_act_sizeof": (C.c_int, [C.c_int]),
+    "pvae_ppo_order_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "pvae_ppo_order": (C.c_int, [C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, _P, _P, C.c_size_t, _P]),
     "pvae_mfma_clock_probe": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "pvae_profile_enable": (C.c_int, [C.c_int]),
     "pvae_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),

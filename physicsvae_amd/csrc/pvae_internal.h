@@ -12,7 +12,8 @@
 //   pvae_probe.hip           measurement entry points (clock probe, profiler read-out, contraction probe)
 //   pvae_fc.hip              the stack set, and what its PPO learner runs of it: the model adapter of pvae_ppo_learner.h
 //   pvae_ppo_core.hip        the PPO learner's model-independent kernels, launches and checks (loss head, Adam + stats and its
-//                            two-halves and exchanged forms, evaluate epilogue, pad copy, zero rows, GAE), pvae_ppo_loss and pvae_gae
+//                            two-halves and exchanged forms, evaluate epilogue, pad copy, zero rows, GAE, minibatch order),
+//                            pvae_ppo_loss, pvae_gae and pvae_ppo_order
 //   pvae_ppo.hip             what PhysicsVAE's PPO learner runs of pvae_infer.hip and pvae_fc.hip: its model adapter
 //   pvae_ppo_learner.h       the PPO learner's host driver, once for both models: step, sgd loop, the two halves, exchange set-up,
 //                            evaluate, prepare and act, as function templates over a unit's model adapter

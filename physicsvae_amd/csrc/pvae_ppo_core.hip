@@ -1,8 +1,9 @@
 // pvae_ppo_core.hip -- what the on-device PPO learner holds that no model owns (include/pvae.h "PPO learner step",
 // "Train-batch preparation", "Action sampling", "Learner diagnostics"): the loss head and its finishing reduction (with the
 // per-step diagnostics and the gradient norm's partial sums as template instantiations), the Adam + stats launch, the
-// evaluate and the sampling epilogue, the pad copy, the zero-rows launch, GAE and standardisation, their argument checks,
-// and the entry points that need no model at all (pvae_ppo_loss, pvae_gae).  The stack set's learner (pvae_fc.hip) and
+// evaluate and the sampling epilogue, the pad copy, the zero-rows launch, GAE and standardisation, the minibatch order
+// ("Minibatch order of the PPO learner"), their argument checks, and the entry points that need no model at all
+// (pvae_ppo_loss, pvae_gae, pvae_ppo_order).  The stack set's learner (pvae_fc.hip) and
 // PhysicsVAE's (pvae_ppo.hip) fill the argument structs of pvae_internal.h from their own panels and call the launch
 // functions here: one kernel per job.
 #include "pvae_internal.h"
@@ -660,6 +661,127 @@ gae_standardize_kernel(float* __restrict__ adv, long long n, const double* __res
 }
 
 // ---------------------------------------------------------------------------------------
+// minibatch order: every pass's row order from the Philox stream (include/pvae.h "Minibatch order of the PPO learner")
+// ---------------------------------------------------------------------------------------
+// packed(p, i) = key32(p, i) << 32 | i is unique, so sorting it ascending is the whole job and neither stability nor timing
+// can show.  Pass p is its own problem: blockIdx.y, striding by gridDim.y past kOrderMaxY passes.  No atomics, no workgroup
+// waits for another: a sort that spans workgroups synchronises at kernel boundaries; every loop's trip count is known at
+// launch.  The sizes at which the algorithm changes form:
+//   * n <= kOrderTile (8192): ONE launch.  One workgroup per pass forms the keys in LDS (thread q: one Philox call, rows
+//     4q .. 4q + 3), sorts them there with a bitonic network and writes the low words to perm.  8192 packed keys are 64 KiB
+//     of the CU's 160 KiB (MI355X: LDS per CU), what a workgroup may declare statically.  The network runs over
+//     n_pad = max(256, the next power of two >= n) keys, rows >= n holding the all-ones key, which sorts behind every
+//     packed one (i < 2^31): the stage count changes at n = 256, 512, 1024, 2048, 4096.
+//   * n > kOrderTile: tiles = ceil(n / 8192) workgroups per pass sort one tile each (the last one partial, padded as
+//     above) into the scratch's first key buffer, then ceil(log2(tiles)) merge launches double the sorted run, ping-pong
+//     between the scratch's two buffers: element i of a run finds its rank in the sibling run by a binary search (<= 31
+//     probes) and stores itself at (its place in its own run + that rank) -- a scatter of distinct places, since the keys
+//     are unique.  A run without a sibling (an odd run count) is copied.  The LAST merge launch writes the low words to perm.
+//     The merge count changes at n = 16384 (2), 32768 (3), 65536 (4), ...; an odd run count first shows at 3 tiles.
+constexpr int kOrderTile = 8192;
+constexpr int kOrderThreads = 1024;
+constexpr int kOrderMinPad = 256;
+constexpr int kOrderMaxY = 1024;           // grid rows (passes side by side); more passes: a workgroup strides
+constexpr int kOrderMaxX = 4096;           // grid columns of either launch; more tiles / elements: a workgroup strides
+struct OrderArgs {
+    uint64_t seed, offset;
+    long long n, tiles;
+    int passes, n_pad;                     // n_pad: the keys a workgroup sorts in LDS, a power of two in [256, 8192]
+    const uint64_t* src;                   // merge: the runs
+    uint64_t* dst;                         // the packed keys, [passes][n]; null: the low words go to perm
+    int32_t* perm;                         // [passes][n]
+    int run_shift;                         // merge: sorted runs of 1 << run_shift keys come in
+};
+
+// w[0..3](g) of pass p: Philox4x32-10 at counter {offset, g, 0xC0000000 + p}, philox_normal4's key schedule
+__device__ inline void order_words(uint32_t (&c)[4], uint64_t seed, uint64_t offset, uint32_t g, uint32_t p) {
+    c[0] = (uint32_t)offset; c[1] = (uint32_t)(offset >> 32); c[2] = g; c[3] = 0xC0000000u + p;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+__global__ void __launch_bounds__(kOrderThreads)
+ppo_order_tile_kernel(OrderArgs a) {
+    __shared__ uint64_t key[kOrderTile];
+    const int tid = threadIdx.x, n_pad = a.n_pad;
+    for (int p = blockIdx.y; p < a.passes; p += gridDim.y) {
+        for (long long t = blockIdx.x; t < a.tiles; t += gridDim.x) {       // (both trip counts: the same for the whole workgroup)
+            const long long row0 = t * kOrderTile;
+            for (int q = tid; q < n_pad / 4; q += kOrderThreads) {
+                const long long i0 = row0 + 4ll * q;
+                uint32_t w[4] = {0u, 0u, 0u, 0u};
+                if (i0 < a.n) order_words(w, a.seed, a.offset, (uint32_t)(i0 >> 2), (uint32_t)p);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    key[4 * q + c] = i0 + c < a.n ? ((uint64_t)w[c] << 32) | (uint64_t)(i0 + c) : ~0ull;
+            }
+            __syncthreads();
+            for (int k = 2; k <= n_pad; k <<= 1)
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    for (int u = tid; u < n_pad / 2; u += kOrderThreads) {
+                        const int lo = ((u & ~(j - 1)) << 1) | (u & (j - 1)), hi = lo + j;
+                        const uint64_t x = key[lo], y = key[hi];
+                        if ((x > y) == ((lo & k) == 0)) { key[lo] = y; key[hi] = x; }
+                    }
+                    __syncthreads();
+                }
+            const long long live = a.n - row0 < n_pad ? a.n - row0 : n_pad;      // the all-ones keys lie behind them
+            const size_t out0 = (size_t)p * (size_t)a.n + (size_t)row0;
+            for (int j = tid; j < live; j += kOrderThreads) {
+                if (a.dst) a.dst[out0 + j] = key[j];
+                else a.perm[out0 + j] = (int32_t)(uint32_t)key[j];
+            }
+            __syncthreads();                                                   // (the next tile overwrites the keys)
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+ppo_order_merge_kernel(OrderArgs a) {
+    const long long n = a.n, run = 1ll << a.run_shift;
+    for (int p = blockIdx.y; p < a.passes; p += gridDim.y) {
+        const uint64_t* __restrict__ src = a.src + (size_t)p * (size_t)n;
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+            const uint64_t x = src[i];
+            const long long r = i >> a.run_shift, a0 = (r & ~1ll) << a.run_shift;
+            const long long mid = a0 + run < n ? a0 + run : n, end = a0 + 2 * run < n ? a0 + 2 * run : n;
+            const bool first = i < mid;                                        // i lies in the pair's first run
+            const long long s0 = first ? mid : a0;                             // the sibling run: [s0, s1), empty for a lone run
+            long long lo = s0, hi = first ? end : mid;
+            for (int it = 0; it < 32 && lo < hi; ++it) {                       // (a run has < 2^31 keys)
+                const long long m = lo + ((hi - lo) >> 1);
+                if (src[m] < x) lo = m + 1; else hi = m;
+            }
+            const size_t pos = (size_t)p * (size_t)n + (size_t)(a0 + (i - (first ? a0 : mid)) + (lo - s0));
+            if (a.dst) a.dst[pos] = x;
+            else a.perm[pos] = (int32_t)(uint32_t)x;
+        }
+    }
+}
+
+long long order_tiles(long long n) { return (n + kOrderTile - 1) / kOrderTile; }
+int order_merges(long long tiles) {
+    int m = 0;
+    while ((1ll << m) < tiles) ++m;
+    return m;
+}
+int check_order_sizes(long long n_rows, int passes) {
+    if (n_rows < 1 || n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range [1, 2^31)", n_rows);
+    if (passes < 1 || passes >= (1 << 30)) return fail(-1, "num_sgd_iter %d out of range [1, 2^30)", passes);
+    return 0;
+}
+// the scratch: nothing but 16 bytes up to one tile; past it two buffers of [passes][n] packed keys, one behind the other
+size_t order_scratch_bytes(long long n_rows, int passes) {
+    if (n_rows <= kOrderTile) return 16;
+    return ((size_t)2 * (size_t)passes * (size_t)n_rows * sizeof(uint64_t) + 15) / 16 * 16;
+}
+
+// ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
 AdamScalars ppo_adam_scalars(const pvae_fc_ppo_params* p, int t) {
@@ -1076,6 +1198,49 @@ int pvae_gae(const float* rewards, const float* vf_preds, const float* last_valu
                       (hipStream_t)stream, launches)))
         return rc;
     return launches;
+}
+
+size_t pvae_ppo_order_workspace_bytes(int64_t n_rows, int32_t num_sgd_iter) {
+    if (check_order_sizes(n_rows, num_sgd_iter)) return 0;
+    if (n_rows > kOrderTile && (uint64_t)num_sgd_iter > (UINT64_MAX / 32) / (uint64_t)n_rows) {
+        fail(-1, "%d passes over %lld rows: the packed keys do not fit a size_t", num_sgd_iter, (long long)n_rows);
+        return 0;
+    }
+    return order_scratch_bytes(n_rows, num_sgd_iter);
+}
+
+int pvae_ppo_order(int64_t n_rows, int32_t num_sgd_iter, uint64_t seed, uint64_t offset, int32_t* perm, void* scratch,
+                   size_t scratch_bytes, void* stream) {
+    const size_t need = pvae_ppo_order_workspace_bytes(n_rows, num_sgd_iter);
+    if (!need) return -1;
+    if (!perm) return fail(-1, "perm is null");
+    if ((uintptr_t)perm & 3) return fail(-1, "perm must be 4-byte aligned");
+    if (!scratch) return fail(-1, "scratch is null");
+    if ((uintptr_t)scratch & 15) return fail(-1, "scratch must be 16-byte aligned");
+    if (scratch_bytes < need) return fail(-1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    OrderArgs a;
+    memset((void*)&a, 0, sizeof(a));
+    a.seed = seed; a.offset = offset; a.n = n_rows; a.passes = num_sgd_iter; a.perm = perm;
+    a.tiles = order_tiles(n_rows);
+    a.n_pad = kOrderMinPad;
+    while (a.n_pad < kOrderTile && a.n_pad < n_rows) a.n_pad <<= 1;
+    const int merges = order_merges(a.tiles);
+    uint64_t* buf[2] = {(uint64_t*)scratch, (uint64_t*)scratch + (size_t)num_sgd_iter * (size_t)n_rows};
+    const int gy = num_sgd_iter < kOrderMaxY ? num_sgd_iter : kOrderMaxY;
+    a.dst = merges ? buf[0] : nullptr;
+    hipLaunchKernelGGL(ppo_order_tile_kernel, dim3((int)std::min<long long>(a.tiles, kOrderMaxX), gy), dim3(kOrderThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    const int gx = (int)std::min<long long>((n_rows + 255) / 256, kOrderMaxX);
+    for (int m = 0; m < merges; ++m) {
+        a.src = buf[m & 1];
+        a.dst = m == merges - 1 ? nullptr : buf[(m + 1) & 1];
+        a.run_shift = 13 + m;
+        hipLaunchKernelGGL(ppo_order_merge_kernel, dim3(gx, gy), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    static_assert(kOrderTile == 1 << 13, "run_shift of the first merge");
+    return 1 + merges;
 }
 
 }  // extern "C"

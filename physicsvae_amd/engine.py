@@ -7,7 +7,7 @@ happens in the library (physicsvae_amd/csrc).  Split by job:
                        net_forward / net_backward, reparam -- GraphedInfer, make_step_params, gemm_probe
     engine_dp.py       DataParallelExchange: comm_*, p2p_*, dp_train_step (the supervised trainer's exchange)
     engine_rollout.py  RolloutClient: infer_host and the rollout server's client
-    engine_ppo.py      PpoSurface: the PPO learner surface both engines inherit, its struct builders, ppo_loss, gae
+    engine_ppo.py      PpoSurface: the PPO learner surface both engines inherit, its struct builders, ppo_loss, gae, ppo_order
     stack_set.py       StackSetEngine, set_fc_per_stack
 
 HipEngine = core + DataParallelExchange + RolloutClient + PpoSurface; StackSetEngine = core + PpoSurface.  The first
@@ -22,7 +22,7 @@ from ._lib import FLAG_FUSED_ADAM, FLAG_NO_BACKWARD, NET_MD, NET_MH, NET_NAMES, 
 from .arch import TENSOR_IDS, Arch, Stack                                                                  # noqa: F401
 from .engine_dp import DataParallelExchange
 from .engine_ppo import (PPO_COLUMNS, PpoSurface, evaluate_plan, gae, gae_scratch_for, make_act, make_ppo_batch,   # noqa: F401
-                         make_prepared, make_rollout, ppo_loss, ppo_loss_diag, prepare_plan)
+                         make_prepared, make_rollout, ppo_loss, ppo_loss_diag, ppo_order, prepare_plan)
 from .engine_rollout import RolloutClient
 from .stack_set import StackSetEngine, set_fc_per_stack                                                    # noqa: F401
 

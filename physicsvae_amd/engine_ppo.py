@@ -1,5 +1,6 @@
 """The PPO learner surface of both engines (`PpoSurface`), the structs its calls take (`make_ppo_batch`, `make_rollout`,
-`make_prepared`, `make_act`, the evaluate / prepare plans) and the entry points that need no engine (`ppo_loss`, `gae`).
+`make_prepared`, `make_act`, the evaluate / prepare plans) and the entry points that need no engine (`ppo_loss`, `gae`,
+`ppo_order`).
 """
 import ctypes as C
 
@@ -296,6 +297,9 @@ class PpoPolicy:
         _ppo_draws(call, eps, dp_shape=None)    the draw keywords of the engine's call; `dp_shape` = (steps, minibatch):
                                    the torch transport takes supplied draws as one tensor
         _ppo_after(call, n)        n steps or chunks drew at the module's RNG counter; the last forward's results are gone
+                                   (call "order", after "learn" under perm="philox": the minibatch order was drawn; it moves
+                                   the counter only of a model whose learner draws nothing else)
+        _ppo_order_key()           (seed, offset) the minibatch order is drawn at: the counter + 1 as the learn call finds it
         _ppo_dp_tensors(train_ls)  what `PPODataParallel.attach` copies from rank 0, after `_ppo_bind_engine`
         _PPO_PARTIAL_SAMPLER       prepare hands the sampler's columns on when only some are there (the library refuses them)
     """
@@ -320,6 +324,10 @@ class PpoPolicy:
     def _policy_learn(self, batch, config, perm, eps, dp, diag_out):
         from . import ppo as P
         eng = self.engine
+        drawn = isinstance(perm, str)
+        if drawn and perm not in P.ORDERS:
+            raise ValueError("perm=%r: the minibatch order is None (row order), an int32 tensor [num_sgd_iter, n_rows] or "
+                             "one of %s" % (perm, ", ".join('"%s"' % o for o in P.ORDERS)))
         train_mask = self._ppo_learn_mask(config)
         kind, base, train_ls = self._ppo_bind_engine()
         if kind == "state_independent" and not train_ls:
@@ -328,7 +336,9 @@ class PpoPolicy:
         n = int(cols[0].n_rows)
         t = self.__dict__.get("_ppo_t", 0)
         params = config.params(kind, base, adam_t=t + 1, train_mask=train_mask)
-        if perm is not None:
+        if drawn:                                # its own library call; from here on it is a caller's tensor
+            perm = ppo_order(n, config.num_sgd_iter, *self._ppo_order_key(), eng.device)
+        elif perm is not None:
             perm = perm.to(eng.device, torch.int32).contiguous()
         if dp is not None:
             dp.check_steps(n, config, eng.device)
@@ -350,6 +360,8 @@ class PpoPolicy:
                 eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
         self.__dict__["_ppo_t"] = t + stats.shape[0]
         self._ppo_after("learn", stats.shape[0])
+        if drawn:
+            self._ppo_after("order", 1)
         return stats
 
     def _policy_prepare(self, rollout, config, eps):
@@ -624,6 +636,41 @@ def _ppo_loss(mean, log_std, value, batch, params, index, diag_out):
         else:
             _lib.check(lib.pvae_ppo_loss_diag(*args, diag_out.data_ptr(), st), "pvae_ppo_loss_diag")
     return stats, d_mean, d_ls, d_val
+
+
+_order_scratch = {}
+
+
+def ppo_order(n_rows, num_sgd_iter, seed, offset, device, out=None, info=None):
+    """`pvae_ppo_order`: the minibatch order of `num_sgd_iter` passes over `n_rows` rows at (seed, offset) of the Philox
+    stream (the rule: `ppo.py`'s module docstring; `ppo.minibatch_order` gives the same bits on the host).  Returns int32
+    [num_sgd_iter, n_rows] on `device`, what `ppo_sgd` takes as `perm`; `out`: the tensor to write into; `info`: a dict
+    that receives the number of kernel launches.  Enqueued on the current stream, nothing synchronises; the scratch is
+    made once per (device, stream, size) and kept."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    assert dev.type == "cuda", "pvae_ppo_order needs a GPU (there is no CPU fallback)"
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    n, passes = int(n_rows), int(num_sgd_iter)
+    need = int(lib.pvae_ppo_order_workspace_bytes(n, passes))
+    if need == 0:
+        _lib.check(-1, "pvae_ppo_order_workspace_bytes")
+    if out is None:
+        out = torch.empty(passes, n, dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.device == dev and out.is_contiguous() and tuple(out.shape) == (passes, n), \
+        "out must be contiguous int32 [%d, %d] on %s" % (passes, n, dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        key = (out.device, st, need)
+        scratch = _order_scratch.get(key)
+        if scratch is None:
+            scratch = _order_scratch[key] = torch.empty(need // 8, dtype=torch.int64, device=out.device)
+        rc = _lib.check(lib.pvae_ppo_order(n, passes, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), out.data_ptr(),
+                                           scratch.data_ptr(), need, st), "pvae_ppo_order")
+    if info is not None:
+        info["launches"] = rc
+    return out
 
 
 def _seg_start(seg_start, n_segs, n_rows, device):

@@ -189,9 +189,14 @@ class FullyConnectedPolicy(PpoPolicy, nn.Module):
     def _ppo_draws(self, call, eps, dp_shape=None):
         return dict(seed=self._rng_seed, offset=self._rng_calls + 1) if call == "act" else {}
 
+    def _ppo_order_key(self):
+        return self._rng_seed, self._rng_calls + 1
+
     def _ppo_after(self, call, n):
-        if call == "act":                        # (the learner draws nothing: there is no latent)
+        if call in ("act", "order"):             # (the learner draws nothing but the minibatch order: there is no latent)
             self._rng_calls += n
+        if call == "order":
+            return
         if call != "prepare":
             self._cur_value = None
 
@@ -231,7 +236,9 @@ class FullyConnectedPolicy(PpoPolicy, nn.Module):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step
         forward + PPO loss + backward + Adam in 9 launches, nothing synchronised.  `batch`: device tensors under RLlib's
         sample-batch keys (obs, actions, action_dist_inputs, action_logp, advantages, value_targets, vf_preds); `perm`: int32
-        [num_sgd_iter, n_rows] on the device, the row order of every pass (None: row order).  Returns the per-step stats
+        [num_sgd_iter, n_rows] on the device, the row order of every pass (None: row order, no shuffling; "philox": drawn on
+        the device by `pvae_ppo_order` from `seed()`'s key at the call counter + 1, which this call then advances by 1 -- the
+        rule: `ppo.py`'s module docstring; any other string is a ValueError).  Returns the per-step stats
         [steps, 5] (total, policy loss, vf loss, kl, entropy) on the device.  Adam's moments and time step live in this
         module (`reset_ppo_optimizer`); frozen stacks (`requires_grad_(False)`) are left alone, parameters and moments.
         `dp`: a `parallel.PPODataParallel` this module is attached to -- every step's gradient is then averaged over the

@@ -830,7 +830,12 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         noise = "latent_noise" if call == "act" else "noise"
         return {"eps": eps, noise: bool(self.latent_prior_noise), "seed": self._rng_seed, "offset": self._st._rng_calls + 1}
 
+    def _ppo_order_key(self):
+        return self._rng_seed, self._st._rng_calls + 1
+
     def _ppo_after(self, call, n):
+        if call == "order":                      # (drawn at step 0's offset, in its own group domain: the steps move the counter)
+            return
         st = self._st
         st._rng_calls += n
         st._lazy = st._mu = st._logvar = st._cur_value = None          # the panels of the last forward are gone
@@ -880,7 +885,9 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         `config.num_sgd_iter` passes in minibatches of `config.sgd_minibatch_size` rows (the last one short), each step the
         forward of rmt:742-771 without the world model, the PPO loss, backward and Adam, nothing synchronised.  `batch`:
         device tensors under RLlib's sample-batch keys (`ppo.SAMPLE_BATCH_KEYS`); `perm`: int32 [num_sgd_iter, n_rows] on the
-        device (None: row order); `eps`: [steps, sgd_minibatch_size, Z] draws, step i row r uses eps[i, r] (None: Philox from
+        device (None: row order, no shuffling; "philox": drawn on the device by `pvae_ppo_order` from the module's seed at
+        `_rng_calls` + 1, step 0's offset in a group domain of its own, so the latent draws are what they are under a tensor --
+        the rule: `ppo.py`'s module docstring; any other string is a ValueError); `eps`: [steps, sgd_minibatch_size, Z] draws, step i row r uses eps[i, r] (None: Philox from
         the module's seed, one offset of the `_rng_calls` counter per step, as every learner forward upstream draws afresh).
         Returns the per-step stats [steps, 5] (`ppo.STATS`) on the device.  Adam's moments and time step live in this module
         (`reset_ppo_optimizer`) apart from the supervised trainer's; the encoder, the decoder and the value branch are each

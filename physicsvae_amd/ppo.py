@@ -70,6 +70,30 @@ for a state-dependent stack) and standard-normal noise n[r], all [k] (`sample_ac
     latent draws (groups < Z / 4) --, chunk i of a call at offset + i; the noise used comes back as `action_noise`, as
     `latent_eps` does, because Philox goes through hardware transcendentals and cannot be reproduced on the host;
   * `RolloutBuffer` holds the train batch's columns on the device and lets every step write its rows in place.
+
+The minibatch order (`ppo_learn(..., perm="philox")`, `pvae_ppo_order`): every pass's row order drawn on the device from the
+module's Philox stream, so that a learner call is a function of the module's own (seed, call counter) like the action noise
+and the latent draws.  The rule is this project's own (RLlib 1.11's `minibatches` shuffle could not be checked, no ray
+installation was at hand).  For a train batch of n rows, pass p of num_sgd_iter, the module's seed and the call's offset
+(both uint64):
+
+    w[0..3](g)  = Philox4x32-10( counter = { lo32(offset), hi32(offset), g, 0xC0000000 + p },
+                                 key = { lo32(seed), hi32(seed) } )
+                  (philox_round of pvae_internal.h, ten rounds, the key schedule philox_normal4 uses)
+    key32(p, i) = w[i & 3](i >> 2)                  one Philox call serves four consecutive rows
+    packed(p,i) = (uint64(key32(p, i)) << 32) | i   unique: equal 32-bit keys are ordered by row
+    order[p]    = the rows i = 0 .. n-1 sorted by packed(p, i), ascending
+
+  * minibatch j of pass p takes rows order[p][j * mb : (j + 1) * mb];
+  * the counter's fourth word keeps the order apart from the other streams: latent draws use groups below Z / 4, action
+    noise groups from 0x80000000, the order groups from 0xC0000000, so num_sgd_iter < 2^30;
+  * the integer stage of Philox needs no hardware transcendental, so -- unlike the normal draws -- the order is reproduced
+    bit for bit on the host: `minibatch_order` is the rule in numpy and the tests' oracle;
+  * the order is drawn at offset = `_rng_calls` + 1 as the call finds it: the offset step 0's latent draws use, in a disjoint
+    group domain.  `PhysicsVAE`'s counter advances by the number of steps, as without it; `FullyConnectedPolicy`'s learner
+    draws nothing else, so under perm="philox", and only then, its `ppo_learn` advances `_rng_calls` by 1 (two consecutive
+    iterations would otherwise draw the same order).  perm=None (row order) or a tensor: the accounting is unchanged;
+  * workers with the same seed draw the same order over their own rows (the rank does not enter the stream).
 """
 import math
 
@@ -448,6 +472,42 @@ def batch_columns(batch):
     if missing:
         raise KeyError("sample batch lacks %s" % ", ".join(missing))
     return {v: batch[k] for k, v in SAMPLE_BATCH_KEYS.items()}
+
+
+ORDERS = ("philox",)             # what `ppo_learn(..., perm=)` accepts besides None and a tensor
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in exact integer numpy: `counter` four and `key` two arrays (or scalars) of
+    32-bit values that broadcast against each other; returns the four output words as uint64 arrays below 2^32."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=np.uint64) & m32 for x in counter]
+    k0, k1 = (np.asarray(x, dtype=np.uint64) & m32 for x in key)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]          # 32 x 32 -> 64 bits: exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c
+
+
+def minibatch_keys(n_rows, num_sgd_iter, seed, offset):
+    """packed(p, i) of the module docstring's rule: uint64 [num_sgd_iter, n_rows]."""
+    n, passes, seed, offset = int(n_rows), int(num_sgd_iter), int(seed), int(offset)
+    assert 1 <= n < 2 ** 31 and 1 <= passes < 2 ** 30 and 0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64
+    g = np.arange((n + 3) // 4, dtype=np.uint64)
+    rows = np.arange(n, dtype=np.uint64)
+    out = np.empty((passes, n), dtype=np.uint64)
+    for p in range(passes):
+        w = philox4x32((offset & 0xFFFFFFFF, offset >> 32, g, 0xC0000000 + p), (seed & 0xFFFFFFFF, seed >> 32))
+        key32 = np.stack([np.broadcast_to(x, g.shape) for x in w], axis=1).reshape(-1)[:n]       # [g, c] -> row 4 g + c
+        out[p] = (key32 << np.uint64(32)) | rows
+    return out
+
+
+def minibatch_order(n_rows, num_sgd_iter, seed, offset):
+    """The minibatch order of the module docstring in numpy, exact integer arithmetic on the host: int32
+    [num_sgd_iter, n_rows], pass p's rows in the order `ppo_learn(..., perm="philox")` takes them at (seed, offset)."""
+    return np.argsort(minibatch_keys(n_rows, num_sgd_iter, seed, offset), axis=1, kind="stable").astype(np.int32)
 
 
 def dp_mean_torch(grads):

@@ -12,6 +12,9 @@ drift hit all of them alike; reported per way: median, min and max of the per-ro
 and (d) the acceptance figure: (a.median - x.median) / (a.max - a.min), which must exceed 3.  Prints one JSON line.
 
     python tools/ppo_bench.py [--rows 500] [--steps 200] [--rounds 7] [--warmup 30] [--one-step] [--diag]
+    python tools/ppo_bench.py --order philox torch [none] [--rounds 7] [--learn-rows 6250] [--out profiles/ppo_order_bench.json]
+`--order`: time the minibatch order instead (tools/order_bench.py): `pvae_ppo_order` against the torch.randperm stack it
+replaces, and the whole `ppo_learn` call (sgd_minibatch_size `--rows`, 20 passes) with the order made each of the ways named.
 `--diag`: ways c and d run with a learner-diagnostics buffer bound (`ppo_diag`; one small launch more per step).
 `--one-step`: run a single fused step per log-std type and exit (for a kernel trace of one step).
 """
@@ -26,7 +29,9 @@ import time
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import order_bench                                               # noqa: E402
 from physicsvae_amd import FullyConnectedPolicy                  # noqa: E402
 from physicsvae_amd import ppo as P                              # noqa: E402
 from physicsvae_amd.spaces import Box                            # noqa: E402
@@ -53,6 +58,20 @@ def make_batch(m, n, g):
             "action_logp": logp - 0.35 * rn(n), "advantages": rn(n), "value_targets": rn(n), "vf_preds": rn(n)}
 
 
+def order_mode(a):
+    """`--order`: the imitation spec's learner call -- a worker's train batch, sgd_minibatch_size `--rows`, num_sgd_iter 20."""
+    cfg = P.PPOConfig(clip_param=0.2, kl_coeff=0.0, vf_clip_param=1000.0, lr=1e-6, sgd_minibatch_size=a.rows, num_sgd_iter=20)
+    torch.manual_seed(0)
+    m = make_policy("constant", max(a.rows, 32))
+    batch = make_batch(m, a.learn_rows, torch.Generator(device="cuda").manual_seed(0))
+    out = dict(order_bench.run(m, batch, cfg, a), model="fcnn", obs=OBS)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=500)
@@ -62,7 +81,10 @@ def main():
     ap.add_argument("--one-step", action="store_true")
     ap.add_argument("--diag", action="store_true",
                     help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
+    order_bench.add_arguments(ap)
     a = ap.parse_args()
+    if a.order:
+        return order_mode(a)
     cfg = P.PPOConfig(clip_param=0.2, kl_coeff=0.0, vf_clip_param=1000.0, lr=1e-6, sgd_minibatch_size=a.rows, num_sgd_iter=1)
     out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": OBS, "diag": bool(a.diag)}
     for kind in ("constant", "state_dependent"):

@@ -15,7 +15,14 @@ to one compiler and one pair of builds: they are compared, never pinned.
 
 `--diag` binds a learner-diagnostics buffer (`ppo_diag`) on every engine of the learner scenarios and adds its rows to
 their digests under "diag": every other digest must then be the one printed without the flag.
+
+`--order none` (the default) leaves every scenario on its hand-made `perm` (numpy permutations from the scenario's seed):
+the line is the one printed without the flag.  `--order philox` draws every `perm` of the sgd and step scenarios on the
+device instead (`ppo_order` at seed 11, offset 5; a library without `pvae_ppo_order` cannot run it) and adds the scenario
+"order": the order itself at 70, 8192, 8193 and 20000 rows -- one workgroup in LDS, and tiles with one and two merge
+launches.
 """
+import argparse
 import hashlib
 import json
 import os
@@ -33,6 +40,7 @@ K = 5
 CFG = P.PPOConfig(clip_param=0.2, kl_coeff=0.3, entropy_coeff=0.01, vf_clip_param=0.7, vf_loss_coeff=0.5, lr=1e-3,
                   gamma=0.98, lambda_=0.95)
 DIAG = False                                                     # set by main() from `--diag`
+ORDER = "none"                                                   # set by main() from `--order`
 
 
 def bind_diag(eng):
@@ -74,7 +82,14 @@ def batch(rng, n, n_in):
 
 
 def perms(rng, passes, n):
-    return dev(np.stack([rng.permutation(n) for _ in range(passes)]).astype(np.int32))
+    made = dev(np.stack([rng.permutation(n) for _ in range(passes)]).astype(np.int32))       # (drawn either way: the rng moves alike)
+    return E.ppo_order(n, passes, 11, 5, DEV) if ORDER == "philox" else made
+
+
+def order(out):
+    for n, passes in ((70, 2), (8192, 3), (8193, 3), (20000, 2)):
+        out["order n%d passes%d" % (n, passes)] = digest({"perm": E.ppo_order(n, passes, 11, 5, DEV),
+                                                         "high_words": E.ppo_order(n, passes, 11 << 32, 5 << 32, DEV)})
 
 
 def rollout(rng, n_in):
@@ -282,11 +297,16 @@ def vae_act(out):
 
 
 def main():
-    global DIAG
-    DIAG = "--diag" in sys.argv[1:]
+    global DIAG, ORDER
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--diag", action="store_true")
+    ap.add_argument("--order", choices=("philox", "none"), default="none")
+    a = ap.parse_args()
+    DIAG, ORDER = a.diag, a.order
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
     out = {}
-    for scenario in (fc_sgd, fc_steps, fc_act, loss, gae, fc_prepare, vae_sgd, vae_steps, vae_act, vae_prepare):
+    for scenario in (fc_sgd, fc_steps, fc_act, loss, gae, fc_prepare, vae_sgd, vae_steps, vae_act, vae_prepare) + (
+            (order,) if ORDER == "philox" else ()):
         scenario(out)
     print(json.dumps(out, sort_keys=True))
 
