@@ -967,7 +967,8 @@ int pvae_ppo_peer_status(pvae_ctx* ctx, int* rank, int* world, uint32_t* timeout
  *                         stacks (train_mask) do not enter.  Squares and sums in double; every workgroup of the Adam launch
  *                         leaves ONE partial in a slot of its own (no atomics) and ONE SMALL LAUNCH PER STEP adds the slots in
  *                         slot order -- the same inputs and grid give the same bits.
- *   [5..7]                reserved, written as 0
+ *   [5..7]                reserved, written as 0 (5 and 6 get a meaning while a clip is bound: "Gradient clipping inside the
+ *                         PPO learners")
  *   *_diag_bytes    the scratch *_ppo_diag wants (gradient-norm slots + the loss head's diagnostics partial rows); `steps`
  *                   >= 1 is accepted for a later per-call finish and does not enter today.
  *   *_ppo_diag      binds `diag` (device, capacity_steps x PVAE_PPO_DIAG floats) and the scratch (device, 16-byte aligned);
@@ -985,6 +986,46 @@ int pvae_ppo_diag(pvae_ctx* ctx, float* diag, int32_t capacity_steps, void* scra
 int pvae_ppo_loss_diag(const float* mean, const float* log_std, int64_t log_std_row_stride, const float* value,
                        const pvae_fc_ppo_batch* batch, const int32_t* index, int32_t rows, const pvae_fc_ppo_params* params,
                        float* d_mean, float* d_log_std, float* d_value, float* stats_out, float* diag_out, void* stream);
+
+/* ---- Gradient clipping inside the PPO learners ---------------------------------------------------------------------------
+ * RLlib's `grad_clip` (global-norm clipping, torch.nn.utils.clip_grad_norm_; the usual setting for continuous control is
+ * 40) inside the fused steps of both learners; there is no reference counterpart.  The rule (the specification:
+ * physicsvae_amd/ppo.py `clip_coef_torch`, `dp_clip_mean_torch`), for one minibatch step of one worker with g this worker's
+ * own gradient over everything its Adam launch would consume -- every trained segment and a trained state-independent
+ * log-std vector; stacks frozen by train_mask do not enter; before weight decay:
+ *     s    = sum g_i^2                                    squares and sums in double, fixed order, no atomics
+ *     norm = float32(sqrt(s))
+ *     coef = min(1.0f, max_norm / (norm + 1e-6f))         float32 throughout; a NaN quotient stays NaN (torch.clamp)
+ *     g'_i = g_i * coef                                   one float32 multiply per element, also when coef == 1
+ * and Adam consumes g'.  With coef == 1.0f the product is g bit for bit: a threshold that never bites gives the unclipped
+ * step's parameters, moments and stats.  More than one worker: EVERY WORKER CLIPS ITS OWN GRADIENT FIRST, then the clipped
+ * gradients are averaged by the rule of "Gradient exchange between workers":
+ *     g = (((g'_0 + g'_1) + ...) + g'_{N-1}) * float32(1 / N)
+ * (RLlib 1.11's order as recalled -- the clip runs after backward() and before the all-reduce --, not checked against a ray
+ * installation).  Non-finite norms follow the float32 formula, whatever it gives.
+ *   *_grad_clip_bytes   the scratch *_ppo_grad_clip wants (a multiple of 16): one double per workgroup of the sum-of-squares
+ *                       launch, whose grid is bounded, so no size of the model enters.
+ *   *_ppo_grad_clip     binds the threshold and the scratch (device, 16-byte aligned); max_norm == 0 with a NULL scratch
+ *                       unbinds.  max_norm < 0 or non-finite, a null handle, a null or misaligned scratch and too few
+ *                       bytes are answered with a negative code; nothing is ever launched.  pvae_fc_ppo_params keeps its
+ *                       layout.  While bound:
+ *       *_ppo_step, *_ppo_sgd   (plain and with a peer exchange open) clip as above: ONE launch more per step, the sum of
+ *                       squares between the backward and the Adam launch; every workgroup of the Adam launch adds its slots in
+ *                       slot order and forms coef.  Exchanged: the owner hands coef over in a word of its flag block with
+ *                       the "ready" release, the readers scale peer q's gradient and log-std slot by coef_q; no new wait.
+ *       *_ppo_grad      the gradient left in the bound buffers and ls_grad are the CLIPPED ones, scaled in place behind the
+ *                       norm: the caller's all-reduce sums clipped gradients.  Two launches more.
+ *       *_ppo_apply     ignores the binding (it must not clip a second time): grad + all-reduce + apply(1 / N) is the rule
+ *                       above, grad + apply(1.0) the clipped step bit for bit; with NO clip bound, grad + apply(coef) is too.
+ *       diagnostics     (both bound) entry 4 grad_gnorm keeps its meaning -- what Adam consumes, after clip and average;
+ *                       [5] grad_gnorm_raw = this worker's own `norm` before the clip (what RLlib reports as grad_gnorm),
+ *                       [6] grad_clip_coef = coef; *_ppo_grad writes 5 and 6, *_ppo_apply leaves them.  Without a clip
+ *                       bound, entries 5..7 stay 0.
+ *   Not bound: every entry point is what it was, bit for bit and launch for launch. */
+size_t pvae_fc_ppo_grad_clip_bytes(const pvae_fc_config* cfg);
+int pvae_fc_ppo_grad_clip(pvae_fc* fc, float max_norm, void* scratch, size_t scratch_bytes);
+size_t pvae_ppo_grad_clip_bytes(pvae_ctx* ctx);
+int pvae_ppo_grad_clip(pvae_ctx* ctx, float max_norm, void* scratch, size_t scratch_bytes);
 
 /* ---- Train-batch preparation for PhysicsVAE: evaluate, bootstrap, GAE, standardisation -------------------------------
  * "Train-batch preparation for the PPO learner" above, with PhysicsVAE as the policy: from a device-resident rollout to the

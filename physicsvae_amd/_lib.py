@@ -229,6 +229,10 @@ _SIGS = {
     "pvae_ppo_diag": (C.c_int, [_P, _P, C.c_int32, _P, C.c_size_t]),
     "pvae_ppo_loss_diag": (C.c_int, [_P, _P, C.c_int64, _P, C.POINTER(FcPpoBatch), _P, C.c_int32, C.POINTER(FcPpoParams),
                                      _P, _P, _P, _P, _P, _P]),
+    "pvae_fc_ppo_grad_clip_bytes": (C.c_size_t, [C.POINTER(FcConfig)]),
+    "pvae_fc_ppo_grad_clip": (C.c_int, [_P, C.c_float, _P, C.c_size_t]),
+    "pvae_ppo_grad_clip_bytes": (C.c_size_t, [_P]),
+    "pvae_ppo_grad_clip": (C.c_int, [_P, C.c_float, _P, C.c_size_t]),
     "pvae_fc_ppo_sizeof": (C.c_int, [C.c_int]),
     "pvae_fc_gae_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "pvae_gae": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(GaeParams), _P, _P, _P,

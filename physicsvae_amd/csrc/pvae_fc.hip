@@ -941,6 +941,18 @@ int pvae_fc_ppo_diag(pvae_fc* c, float* diag, int32_t capacity_steps, void* scra
     return ppo_diag_bind(c->ppo.diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
 }
 
+size_t pvae_fc_ppo_grad_clip_bytes(const pvae_fc_config* cfg) {
+    if (!cfg) return 0;
+    const FcLayout L = make_fc_layout(*cfg);
+    if (!L.ok) { fail(-1, "bad stack-set config: %s", L.why); return 0; }
+    return ppo_clip_bytes();                             // (one slot per workgroup of a bounded grid: no size enters)
+}
+
+int pvae_fc_ppo_grad_clip(pvae_fc* c, float max_norm, void* scratch, size_t scratch_bytes) {
+    if (!c) return fail(-1, "null stack set");
+    return ppo_clip_bind(c->ppo.clip, max_norm, scratch, scratch_bytes);
+}
+
 int pvae_fc_ppo_grad(pvae_fc* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                      const pvae_fc_ppo_params* p, float* stats_out, float* ls_grad, void* stream) {
     return learner_grad(FcLearner{c}, b, index, first, rows, p, stats_out, ls_grad, (hipStream_t)stream);

@@ -166,7 +166,8 @@ inline int rccl_load() {
 // [rank] = the local pointers).  Parameters and moments are NOT mapped: every rank reads all gradients and updates its own
 // replica whole.  Flag block: [0, 8) ready[src], [8, 16) done[src], 16 ticket, 17 waits that gave up, [32, 64) the attach-time
 // check's tokens, then from word kPpoPeerLs the k floats of this rank's log-std gradient, where the peers read them.
-constexpr int kPpoPeerReady = 0, kPpoPeerDone = 8, kPpoPeerTicket = 16, kPpoPeerErr = 17, kPpoPeerSelf = 32, kPpoPeerGradA = 40,
+// Word 18: this rank's clip coefficient of the step in flight, a float (a clip bound: PpoClip).
+constexpr int kPpoPeerReady = 0, kPpoPeerDone = 8, kPpoPeerTicket = 16, kPpoPeerErr = 17, kPpoPeerCoef = 18, kPpoPeerSelf = 32, kPpoPeerGradA = 40,
               kPpoPeerGradB = 48, kPpoPeerFin = 56, kPpoPeerPayload = 64, kPpoPeerLs = 256;
 constexpr int kPpoPeerArenas = 2;                // a stack set has one gradient arena, PhysicsVAE two (its own + the value stack set's)
 struct PpoPeers {
@@ -200,6 +201,19 @@ inline PpoDiagRow diag_row(const PpoDiag& d, long long step) {
     return d.out ? PpoDiagRow{d.out + step * PVAE_PPO_DIAG, d.gslot, d.dpart} : PpoDiagRow{nullptr, nullptr, nullptr};
 }
 
+// Gradient clipping (include/pvae.h "Gradient clipping inside the PPO learners"): what *_ppo_grad_clip bound -- the
+// threshold and the scratch, one double per workgroup of the sum-of-squares launch that goes between the backward and the
+// Adam launch.  `slot` null: nothing bound, every launch runs its instantiation without a clip.  Not the diagnostics'
+// gslot: the Adam launch writes that one later.  The launch's grid is at most kClipGrid workgroups over the segments + the
+// log-std vector's: every workgroup of the Adam launch behind it (up to 2049) adds ALL slots again, one wave, four loads
+// per lane at 256 slots, while 255 workgroups of 256 threads already put a wave on every SIMD of the device for the read.
+constexpr int kClipGrid = 255;
+constexpr int kClipSlots = 256;
+struct PpoClip {
+    float max_norm = 0.f;
+    double* slot = nullptr;
+};
+
 // What a PPO learner keeps, whichever model it trains (the stack set: in pvae_fc; PhysicsVAE: pvae_ctx::ppo): what *_ppo_bind
 // bound, the launch counts of the last calls, the exchange and the diagnostics binding.  Its host driver: pvae_ppo_learner.h.
 struct PpoLearner {
@@ -210,6 +224,7 @@ struct PpoLearner {
     int eval_launches = 0, gae_launches = 0;             // *_gae_launches
     PpoPeers peers;                                      // gradient exchange between workers (*_ppo_peer_*)
     PpoDiag diag;                                        // learner diagnostics (*_ppo_diag)
+    PpoClip clip;                                        // gradient clipping (*_ppo_grad_clip)
 };
 
 struct pvae_ctx {
@@ -759,9 +774,17 @@ struct PpoAdamSegs {
 // learner diagnostics (PpoDiag, above pvae_ctx)
 size_t ppo_diag_bytes(int max_batch);
 int ppo_diag_bind(PpoDiag& d, float* diag, int capacity, void* scratch, size_t bytes, int max_batch);
+// gradient clipping (PpoClip, above pvae_ctx): the bind, the sum-of-squares launch ahead of the Adam launch (or of
+// *_ppo_grad's finish) and *_ppo_grad's in-place scale; with `clip.slot` the two Adam launches below run their CLIP form
+size_t ppo_clip_bytes();
+int ppo_clip_bind(PpoClip& c, float max_norm, void* scratch, size_t bytes);
+int ppo_clip_sumsq_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int rows, int k, const float* part, int colsum,
+                          float* ls, const PpoClip& clip, hipStream_t st, int* launches);
+int ppo_clip_scale_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int k, float* ls_grad, int colsum,
+                          const PpoClip& clip, const PpoDiagRow& dg, hipStream_t st, int* launches);
 int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, hipStream_t st,
-                    int* launches);
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, const PpoClip& clip,
+                    hipStream_t st, int* launches);
 // The step in two halves (include/pvae.h "Gradient exchange between workers").  The first half ends with
 // ppo_grad_finish_launch in place of the Adam launch: stats_out[5] (ppo_finish_kernel) and, colsum, ls_grad[k] = the column
 // sums of the partial rows, the value the Adam launch's last workgroup forms; `launches` counts what went out.  The second
@@ -797,7 +820,7 @@ inline long long g_ppo_peer_timeout_ticks = 20ll * 100000000ll;     // stack set
 // The exchanged form of ppo_adam_launch: one launch, the N ranks' gradients summed in rank order and scaled by float(1 / N)
 int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
                              int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
-                             float* stats_out, const PpoDiagRow& dg, hipStream_t st, int* launches);
+                             float* stats_out, const PpoDiagRow& dg, const PpoClip& clip, hipStream_t st, int* launches);
 int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,
                       const float* log_std_m, const float* log_std_v);      // the alignment and pairing rules of *_ppo_bind
 // Rows [r0, r1) of up to kZeroPanels panels (columns [0, width) of row stride ld) set to zero: a <= 4-row forward runs on

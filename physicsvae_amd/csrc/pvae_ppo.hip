@@ -395,6 +395,16 @@ int pvae_ppo_diag(pvae_ctx* c, float* diag, int32_t capacity_steps, void* scratc
     return ppo_diag_bind(c->ppo.diag, diag, capacity_steps, scratch, scratch_bytes, c->L.cfg.max_batch);
 }
 
+size_t pvae_ppo_grad_clip_bytes(pvae_ctx* c) {
+    if (!c) { fail(-1, "null ctx"); return 0; }
+    return ppo_clip_bytes();                             // (one slot per workgroup of a bounded grid: no size enters)
+}
+
+int pvae_ppo_grad_clip(pvae_ctx* c, float max_norm, void* scratch, size_t scratch_bytes) {
+    if (!c) return fail(-1, "null ctx");
+    return ppo_clip_bind(c->ppo.clip, max_norm, scratch, scratch_bytes);
+}
+
 int pvae_ppo_grad(pvae_ctx* c, const pvae_fc_ppo_batch* b, const int32_t* index, int64_t first, int32_t rows,
                   const pvae_fc_ppo_params* p, const float* eps, int noise, uint64_t rng_seed, uint64_t rng_offset,
                   float* stats_out, float* ls_grad, void* stream) {

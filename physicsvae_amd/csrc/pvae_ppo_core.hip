@@ -237,20 +237,138 @@ struct PpoAdam {
     // DIAG instantiations only: the head's diagnostics partial rows and the row they finish into (entries 0..3), the
     // minibatch's rows, and the gradient-norm slots, one per workgroup of the launch
     const float* dpart; int rows; float* diag; double* gslot;
+    // CLIP instantiations and the clip launches only (include/pvae.h "Gradient clipping inside the PPO learners"): the
+    // slots the sum-of-squares launch filled, their number, and the threshold
+    double* cslot; int ncslots; float max_norm;
 };
+
+// ---------------------------------------------------------------------------------------
+// global-norm gradient clipping (include/pvae.h "Gradient clipping inside the PPO learners")
+// ---------------------------------------------------------------------------------------
+// The sum-of-squares launch, between the backward and the Adam launch: a grid-stride pass over the segments the Adam
+// launch runs over, every workgroup's squares (sq4 / block_sum_sq: in double) into ITS slot of the clip scratch; ONE extra
+// workgroup, the last, squares the state-independent log-std vector's gradient, the column sums the Adam launch's last
+// workgroup forms again (ppo_ls_colsum: the same bits).  Its grid is its own (kClipGrid + 1 workgroups at the most):
+// every workgroup of the launch behind it re-adds all slots.
+__global__ void __launch_bounds__(256)
+ppo_clip_sumsq_kernel(PpoAdam a) {
+    double sq = 0.0;
+    if (blockIdx.x == gridDim.x - 1) {
+        if (a.ls)
+            for (int j = threadIdx.x; j < a.k; j += 256) {
+                const float g = ppo_ls_colsum(a.part, a.nparts, a.part_stride, j);
+                sq += (double)g * (double)g;
+            }
+    } else {
+        const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
+            int k = 0;
+            while (i >= a.end4[k]) ++k;
+            const long long q = i - (k ? a.end4[k - 1] : 0);
+            sq += sq4(reinterpret_cast<const v4f*>(a.seg.g[k])[q]);
+        }
+    }
+    block_sum_sq(sq, a.cslot + blockIdx.x);
+}
+// norm = float32(sqrt(sum of the slots)), coef = min(1, max_norm / (norm + 1e-6)) in float32 (torch's clip_grad_norm_;
+// a NaN quotient stays NaN, as torch.clamp leaves it), by ONE full wave: lane l adds slots l, l + 64, ... then the double
+// butterfly, as ppo_gnorm_kernel -- an order that depends on nothing but the slot count, so every workgroup of every launch
+// forms the same bits.  Every lane returns the same pair.
+__device__ inline float clip_coef_wave(const double* __restrict__ cslot, int ncslots, float max_norm, int lane, float* norm_out) {
+    double s = 0.0;
+    for (int i = lane; i < ncslots; i += 64) s += cslot[i];
+    s = wave_sum_d(s);
+    const float norm = (float)sqrt(s);
+    const float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+    *norm_out = norm;
+    return c > 1.0f ? 1.0f : c;
+}
+// ... by a workgroup's first wave, handed to the others through LDS (every thread of the workgroup must call)
+__device__ inline float block_clip_coef(const PpoAdam& a, float* norm_out) {
+    __shared__ float cc[2];
+    if (threadIdx.x < 64) {
+        float norm;
+        const float c = clip_coef_wave(a.cslot, a.ncslots, a.max_norm, threadIdx.x, &norm);
+        if (threadIdx.x == 0) { cc[0] = c; cc[1] = norm; }
+    }
+    __syncthreads();
+    *norm_out = cc[1];
+    return cc[0];
+}
+__device__ inline v4f scale4(const v4f& g, float s) {       // (pinned: no contraction with Adam's first operation)
+    return v4f{__fmul_rn(g[0], s), __fmul_rn(g[1], s), __fmul_rn(g[2], s), __fmul_rn(g[3], s)};
+}
+// The clip's product g * coef.  __fmul_rn is a plain `*` to this compiler: what keeps scale4's products whole is that each
+// has several uses in Adam.  A product with ONE use -- a term of the exchanged launch's rank-order sum -- would be
+// contracted into an fma and round differently from the product *_ppo_grad stores; without the contract flag no later
+// addition can absorb it.
+__device__ inline float clip_mul(float g, float coef) {
+#pragma clang fp contract(off)
+    return g * coef;
+}
+__device__ inline v4f clip4(const v4f& g, float coef) {
+    return v4f{clip_mul(g[0], coef), clip_mul(g[1], coef), clip_mul(g[2], coef), clip_mul(g[3], coef)};
+}
+// *_ppo_grad's last launch while a clip is bound: the gradient in the arena(s) and ls_grad scaled IN PLACE by coef, so
+// that a transport outside the library sums clipped gradients.  The extra last workgroup takes ls_grad and, with a
+// diagnostics row, writes its entries 5 (the raw norm) and 6 (coef).
+__global__ void __launch_bounds__(256)
+ppo_clip_scale_kernel(PpoAdam a, float* __restrict__ ls_grad) {
+    float norm;
+    const float coef = block_clip_coef(a, &norm);
+    if (blockIdx.x == gridDim.x - 1) {
+        if (a.ls)
+            for (int j = threadIdx.x; j < a.k; j += 256) ls_grad[j] = clip_mul(ls_grad[j], coef);
+        if (a.diag && threadIdx.x == 0) { a.diag[5] = norm; a.diag[6] = coef; }
+        return;
+    }
+    const long long n4 = a.seg.n ? a.end4[a.seg.n - 1] : 0;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (gridDim.x - 1) * 256ll) {
+        int k = 0;
+        while (i >= a.end4[k]) ++k;
+        const long long q = i - (k ? a.end4[k - 1] : 0);
+        v4f* g = reinterpret_cast<v4f*>(const_cast<float*>(a.seg.g[k])) + q;
+        *g = clip4(*g, coef);
+    }
+}
+// the diagnostics' finishing launch of a clipped step: wave 0 is ppo_gnorm_kernel (entry 4: what Adam consumed), wave 1
+// writes entry 5, this worker's own norm before the clip, and entry 6, coef
+__global__ void __launch_bounds__(128)
+ppo_gnorm_clip_kernel(const double* __restrict__ gslot, int nslots, const double* __restrict__ cslot, int ncslots, float max_norm,
+                      float* __restrict__ row) {
+    if (threadIdx.x < 64) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nslots; i += 64) s += gslot[i];
+        s = wave_sum_d(s);
+        if (threadIdx.x == 0) row[4] = (float)sqrt(s);
+    } else {
+        float norm;
+        const float c = clip_coef_wave(cslot, ncslots, max_norm, threadIdx.x - 64, &norm);
+        if (threadIdx.x == 64) { row[5] = norm; row[6] = c; }
+    }
+}
+
 // DIAG: + the diagnostics entries 0..3 by the extra workgroup's second wave, and every workgroup's sum of squares of the
 // gradient values it consumed into its slot (block_sum_sq; the extra workgroup: the log-std vector's gradient)
-template <bool DIAG>
+// CLIP: every workgroup forms coef from the clip slots (block_clip_coef) and multiplies each gradient value it loads by
+// it -- one pinned float32 multiply, also when coef == 1, where the product is the value itself
+template <bool DIAG, bool CLIP>
 __global__ void __launch_bounds__(256)
 ppo_adam_kernel(PpoAdam a) {
     [[maybe_unused]] double sq = 0.0;
+    [[maybe_unused]] float coef = 1.0f;
+    if constexpr (CLIP) {
+        float norm;
+        coef = block_clip_coef(a, &norm);
+    }
     if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x < 64) ppo_finish(a.part, a.nparts, a.part_stride, a.inv_rows, a.stats_out, threadIdx.x);
         if constexpr (DIAG)
             if (threadIdx.x >= 64 && threadIdx.x < 128) ppo_diag_finish(a.dpart, a.nparts, a.rows, a.diag, 0, threadIdx.x - 64);
         if (a.ls)
             for (int j = threadIdx.x; j < a.k; j += 256) {
-                const float g = ppo_ls_colsum(a.part, a.nparts, a.part_stride, j);
+                float g = ppo_ls_colsum(a.part, a.nparts, a.part_stride, j);
+                if constexpr (CLIP) g = clip_mul(g, coef);
                 if constexpr (DIAG) sq += (double)g * (double)g;
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
                 adam_update(g, p, m, v, a.s);
@@ -265,7 +383,8 @@ ppo_adam_kernel(PpoAdam a) {
         while (i >= a.end4[k]) ++k;
         const long long q = i - (k ? a.end4[k - 1] : 0);
         v4f pp = reinterpret_cast<v4f*>(a.seg.p[k])[q];
-        const v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
+        v4f gg = reinterpret_cast<const v4f*>(a.seg.g[k])[q];
+        if constexpr (CLIP) gg = clip4(gg, coef);
         if constexpr (DIAG) sq += sq4(gg);
         v4f mm = reinterpret_cast<v4f*>(a.seg.m[k])[q];
         v4f vv = reinterpret_cast<v4f*>(a.seg.v[k])[q];
@@ -296,10 +415,6 @@ __device__ inline void ppo_adam_elem(const PpoAdam& a, int k, long long q, const
     reinterpret_cast<v4f*>(a.seg.m[k])[q] = mm;
     reinterpret_cast<v4f*>(a.seg.v[k])[q] = vv;
 }
-__device__ inline v4f scale4(const v4f& g, float s) {       // (pinned: no contraction with Adam's first operation)
-    return v4f{__fmul_rn(g[0], s), __fmul_rn(g[1], s), __fmul_rn(g[2], s), __fmul_rn(g[3], s)};
-}
-
 // second half: ppo_adam_kernel on scale * gradient, the log-std vector from scale * ls_grad; no stats (the first half wrote them)
 // (DIAG: the slots get the squares of scale * gradient, what Adam consumes)
 template <bool DIAG>
@@ -353,12 +468,25 @@ struct PpoAdamPeers {
     float inv_n;
 };
 // DIAG: as ppo_adam_kernel's -- the slots get the squares of the AVERAGED gradient, so every rank reports the same norm
-template <int N, bool DIAG>
+// CLIP: every worker clips its own gradient first, then the clipped gradients are averaged.  Every workgroup forms this
+// rank's coef from its own clip slots; workgroup 0 stores it to word kPpoPeerCoef of the flag block ahead of the "ready"
+// release, and a reader loads peer q's coef_q behind the acquire, with the system-scope load it reads the log-std slot
+// with -- no new wait.  The sum in rank order is over the products g_q * coef_q, each rounded on its own (clip_mul); the
+// log-std slots hold the RAW column sums and are scaled by the reader in the same way.
+template <int N, bool DIAG, bool CLIP>
 __global__ void __launch_bounds__(256)
 ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
     [[maybe_unused]] double sq = 0.0;
     unsigned* mine = x.f[x.me];
     const int tid = threadIdx.x, me = x.me;
+    [[maybe_unused]] __shared__ float coefs[N];
+    if constexpr (CLIP) {
+        float norm;
+        const float coef = block_clip_coef(a, &norm);
+        if (tid == 0) coefs[me] = coef;                  // (read behind the barriers below)
+        if (blockIdx.x == 0 && tid == 0)
+            __hip_atomic_store((float*)(mine + kPpoPeerCoef), coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     if (blockIdx.x == 0) {
         if (a.ls)
             for (int j = tid; j < a.k; j += 256)
@@ -378,6 +506,8 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
     if (tid < N && tid != me) {
         if (!p2p_wait(mine + kPpoPeerReady + tid, x.epoch, x.timeout_ticks, mine + kPpoPeerErr)) abort_ = 1;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        if constexpr (CLIP)
+            coefs[tid] = __hip_atomic_load((const float*)(x.f[tid] + kPpoPeerCoef), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
     const bool go = !abort_;
@@ -390,9 +520,10 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
                 float g = 0.f;                 // (the own column is summed here again: no workgroup waits for another of its launch)
 #pragma unroll
                 for (int q = 0; q < N; ++q) {
-                    const float gq = q == me ? ppo_ls_colsum(a.part, a.nparts, a.part_stride, j)
-                                             : __hip_atomic_load((const float*)(x.f[q] + kPpoPeerLs) + j, __ATOMIC_RELAXED,
-                                                                 __HIP_MEMORY_SCOPE_SYSTEM);
+                    float gq = q == me ? ppo_ls_colsum(a.part, a.nparts, a.part_stride, j)
+                                       : __hip_atomic_load((const float*)(x.f[q] + kPpoPeerLs) + j, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_SYSTEM);
+                    if constexpr (CLIP) gq = clip_mul(gq, coefs[q]);
                     g = q == 0 ? gq : g + gq;                         // rank order
                 }
                 float p = a.ls[j], m = a.ls_m[j], v = a.ls_v[j];
@@ -414,6 +545,10 @@ ppo_adam_exchange_kernel(PpoAdam a, PpoAdamPeers x) {
 #pragma unroll
                 for (int q = 0; q < N; ++q)
                     g[q] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rg[q], (unsigned)(i * 16), 0, 17));
+                if constexpr (CLIP) {
+#pragma unroll
+                    for (int q = 0; q < N; ++q) g[q] = clip4(g[q], coefs[q]);
+                }
                 v4f sum = g[0];
 #pragma unroll
                 for (int q = 1; q < N; ++q) sum += g[q];              // rank order
@@ -876,9 +1011,32 @@ int ppo_diag_bind(PpoDiag& d, float* diag, int capacity, void* scratch, size_t b
     d.gslot = (double*)scratch; d.dpart = (float*)((double*)scratch + kDiagSlots);
     return 0;
 }
-// the slots of an Adam launch of `nslots` workgroups added into entry 4 of the row
-static int ppo_gnorm_launch(const PpoDiagRow& dg, int nslots, hipStream_t st, int* launches) {
-    hipLaunchKernelGGL(ppo_gnorm_kernel, dim3(1), dim3(64), 0, st, (const double*)dg.gslot, nslots, dg.row + 4);
+// ---- gradient clipping: the bound scratch ----
+size_t ppo_clip_bytes() { return (size_t)kClipSlots * sizeof(double); }
+int ppo_clip_bind(PpoClip& c, float max_norm, void* scratch, size_t bytes) {
+    if (!(max_norm >= 0.f) || !std::isfinite(max_norm)) return fail(-1, "max_norm must be finite and >= 0, got %g", (double)max_norm);
+    if (max_norm == 0.f && !scratch) { c = PpoClip(); return 0; }
+    if (max_norm == 0.f) return fail(-1, "max_norm 0 unbinds: its scratch must be NULL");
+    if (!scratch) return fail(-1, "clip scratch is null");
+    if ((uintptr_t)scratch & 15) return fail(-1, "clip scratch must be 16-byte aligned");
+    if (bytes < ppo_clip_bytes()) return fail(-1, "clip scratch too small: %zu < %zu bytes", bytes, ppo_clip_bytes());
+    c.max_norm = max_norm; c.slot = (double*)scratch;
+    return 0;
+}
+static int clip_slots(long long total4) {                 // workgroups of the sum-of-squares launch = slots it fills
+    long long grid = (total4 + 255) / 256;
+    if (grid > kClipGrid) grid = kClipGrid;
+    return (int)grid + 1;
+}
+
+// the slots of an Adam launch of `nslots` workgroups added into entry 4 of the row; `a`: that launch's arguments -- with a
+// clip, entries 5 and 6 from the clip slots in the same launch
+static int ppo_gnorm_launch(const PpoDiagRow& dg, int nslots, const PpoAdam& a, hipStream_t st, int* launches) {
+    if (a.cslot)
+        hipLaunchKernelGGL(ppo_gnorm_clip_kernel, dim3(1), dim3(128), 0, st, (const double*)dg.gslot, nslots, (const double*)a.cslot,
+                           a.ncslots, a.max_norm, dg.row);
+    else
+        hipLaunchKernelGGL(ppo_gnorm_kernel, dim3(1), dim3(64), 0, st, (const double*)dg.gslot, nslots, dg.row + 4);
     HIP_TRY(hipGetLastError());
     if (launches) ++*launches;
     return 0;
@@ -887,7 +1045,7 @@ static int ppo_gnorm_launch(const PpoDiagRow& dg, int nslots, hipStream_t st, in
 // the arguments of the Adam launch in its three forms; returns the float4 elements of all segments
 static long long fill_adam(PpoAdam& a, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k,
                            const float* part, int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out,
-                           const PpoDiagRow& dg) {
+                           const PpoDiagRow& dg, const PpoClip& clip = PpoClip()) {
     memset((void*)&a, 0, sizeof(a));
     a.seg = segs;
     long long total4 = 0;
@@ -898,22 +1056,54 @@ static long long fill_adam(PpoAdam& a, const PpoAdamSegs& segs, const pvae_fc_pp
     a.k = k;
     if (colsum) { a.ls = ls; a.ls_m = ls_m; a.ls_v = ls_v; }
     a.dpart = dg.dpart; a.rows = rows; a.diag = dg.row; a.gslot = dg.gslot;
+    if (clip.slot) { a.cslot = clip.slot; a.ncslots = clip_slots(total4); a.max_norm = clip.max_norm; }
     return total4;
 }
 
-int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
-                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, hipStream_t st,
-                    int* launches) {
+// the sum-of-squares launch of a clipped step: between the backward and the Adam launch (or *_ppo_grad's finish)
+int ppo_clip_sumsq_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int rows, int k, const float* part, int colsum,
+                          float* ls, const PpoClip& clip, hipStream_t st, int* launches) {
     PpoAdam a;
-    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg);
+    fill_adam(a, segs, p, 1, rows, k, part, colsum, ls, nullptr, nullptr, nullptr, PpoDiagRow{nullptr, nullptr, nullptr}, clip);
+    static_assert(kClipGrid + 1 <= kClipSlots, "one clip slot per workgroup");
+    hipLaunchKernelGGL(ppo_clip_sumsq_kernel, dim3(a.ncslots), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+    return 0;
+}
+
+// *_ppo_grad's last launch of a clipped first half: the arena(s) and ls_grad scaled in place (+ diagnostics entries 5, 6)
+int ppo_clip_scale_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int k, float* ls_grad, int colsum,
+                          const PpoClip& clip, const PpoDiagRow& dg, hipStream_t st, int* launches) {
+    PpoAdam a;
+    const long long total4 = fill_adam(a, segs, p, 1, 1, k, nullptr, colsum, ls_grad, nullptr, nullptr, nullptr, dg, clip);
+    long long grid = (total4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(ppo_clip_scale_kernel, dim3((int)grid + 1), dim3(256), 0, st, a, ls_grad);
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+    return 0;
+}
+
+int ppo_adam_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int adam_t, int rows, int k, const float* part,
+                    int colsum, float* ls, float* ls_m, float* ls_v, float* stats_out, const PpoDiagRow& dg, const PpoClip& clip,
+                    hipStream_t st, int* launches) {
+    PpoAdam a;
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg, clip);
     long long grid = (total4 + 255) / 256;
     if (grid > 2048) grid = 2048;
     static_assert(2048 + 1 <= kDiagSlots, "one gradient-norm slot per workgroup");
-    if (dg.row) hipLaunchKernelGGL(ppo_adam_kernel<true>, dim3((int)grid + 1), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(ppo_adam_kernel<false>, dim3((int)grid + 1), dim3(256), 0, st, a);
+    const dim3 g((int)grid + 1);
+    if (clip.slot) {
+        if (dg.row) hipLaunchKernelGGL((ppo_adam_kernel<true, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((ppo_adam_kernel<false, true>), g, dim3(256), 0, st, a);
+    } else {
+        if (dg.row) hipLaunchKernelGGL((ppo_adam_kernel<true, false>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((ppo_adam_kernel<false, false>), g, dim3(256), 0, st, a);
+    }
     HIP_TRY(hipGetLastError());
     ++*launches;
-    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, a, st, launches) : 0;
 }
 
 int ppo_grad_finish_launch(int rows, int k, const float* part, int colsum, float* ls_grad, float* stats_out,
@@ -945,16 +1135,16 @@ int ppo_apply_launch(const PpoAdamSegs& segs, const pvae_fc_ppo_params* p, int a
     else hipLaunchKernelGGL(ppo_apply_kernel<false>, dim3((int)grid + 1), dim3(256), 0, st, a, grad_scale, ls_grad);
     HIP_TRY(hipGetLastError());
     ++*launches;
-    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, a, st, launches) : 0;
 }
 
 int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdamSegs& segs, const pvae_fc_ppo_params* p,
                              int adam_t, int rows, int k, const float* part, int colsum, float* ls, float* ls_m, float* ls_v,
-                             float* stats_out, const PpoDiagRow& dg, hipStream_t st, int* launches) {
+                             float* stats_out, const PpoDiagRow& dg, const PpoClip& clip, hipStream_t st, int* launches) {
     if (!P.open) return fail(-2, "the PPO gradient exchange is not open");
     if (colsum && k != P.k) return fail(-2, "log-std vector of %d values, the exchange was exported for %d", k, P.k);
     PpoAdam a;
-    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg);
+    const long long total4 = fill_adam(a, segs, p, adam_t, rows, k, part, colsum, ls, ls_m, ls_v, stats_out, dg, clip);
     PpoAdamPeers x;
     memset((void*)&x, 0, sizeof(x));
     for (int q = 0; q < P.world; ++q) {
@@ -977,11 +1167,17 @@ int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdam
     long long grid = (total4 + 255) / 256;
     if (grid > kExchangeMaxBlocks) grid = kExchangeMaxBlocks;
     if (grid < 1) grid = 1;
+    const dim3 g((int)grid + 1);
     switch (P.world) {
 #define PVAE_PPO_PEER_CASE(N)                                                                                              \
     case N:                                                                                                                \
-        if (dg.row) hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, true>), dim3((int)grid + 1), dim3(256), 0, st, a, x);  \
-        else hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, false>), dim3((int)grid + 1), dim3(256), 0, st, a, x);        \
+        if (clip.slot) {                                                                                                   \
+            if (dg.row) hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, true, true>), g, dim3(256), 0, st, a, x);          \
+            else hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, false, true>), g, dim3(256), 0, st, a, x);                \
+        } else {                                                                                                           \
+            if (dg.row) hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, true, false>), g, dim3(256), 0, st, a, x);         \
+            else hipLaunchKernelGGL((ppo_adam_exchange_kernel<N, false, false>), g, dim3(256), 0, st, a, x);               \
+        }                                                                                                                  \
         break;
         PVAE_PPO_PEER_CASE(1) PVAE_PPO_PEER_CASE(2) PVAE_PPO_PEER_CASE(3) PVAE_PPO_PEER_CASE(4)
         PVAE_PPO_PEER_CASE(5) PVAE_PPO_PEER_CASE(6) PVAE_PPO_PEER_CASE(7) PVAE_PPO_PEER_CASE(8)
@@ -990,7 +1186,7 @@ int ppo_adam_exchange_launch(PpoPeers& P, long long timeout_ticks, const PpoAdam
     }
     HIP_TRY(hipGetLastError());
     ++*launches;
-    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, st, launches) : 0;
+    return dg.row ? ppo_gnorm_launch(dg, (int)grid + 1, a, st, launches) : 0;
 }
 
 int check_ppo_buffers(const float* grad, const float* m, const float* v, const void* scratch, const float* log_std,

@@ -18,8 +18,8 @@
 //                                   the gradient arena(s) the exchange maps (their number, or < 0: refused; `arg`: the
 //                                   caller's blob pointer), and its timeout ticks
 //   params_written(st), eps_out()   after a call that wrote parameters; where the epilogues copy the latent draws
-// What needs no adapter is not here: *_ppo_diag, *_ppo_peer_close and *_ppo_peer_status call ppo_diag_bind and ppo_peer_*
-// on the handle's PpoLearner directly.
+// What needs no adapter is not here: *_ppo_diag, *_ppo_grad_clip, *_ppo_peer_close and *_ppo_peer_status call
+// ppo_diag_bind, ppo_clip_bind and ppo_peer_* on the handle's PpoLearner directly.
 #pragma once
 #include "pvae_internal.h"
 
@@ -37,10 +37,12 @@ int learner_minibatch(M& m, const pvae_fc_ppo_batch* b, const int32_t* index, lo
     PpoAdamSegs sg;
     if ((rc = m.segments(p, sg))) return rc;
     const int colsum = p->log_std_kind == 1;
+    // a clip bound (*_ppo_grad_clip): this worker's sum of squares first, ONE launch more; the Adam launch forms coef from it
+    if (q.clip.slot && (rc = ppo_clip_sumsq_launch(sg, p, rows, b->k, q.scratch, colsum, q.log_std, q.clip, st, &launches))) return rc;
     rc = q.peers.open ? ppo_adam_exchange_launch(q.peers, m.peer_timeout(), sg, p, p->adam_t + step, rows, b->k, q.scratch, colsum,
-                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, dg, st, &launches)
+                                                 q.log_std, q.log_std_m, q.log_std_v, stats_out, dg, q.clip, st, &launches)
                       : ppo_adam_launch(sg, p, p->adam_t + step, rows, b->k, q.scratch, colsum, q.log_std, q.log_std_m,
-                                        q.log_std_v, stats_out, dg, st, &launches);
+                                        q.log_std_v, stats_out, dg, q.clip, st, &launches);
     if (rc) return rc;
     q.launches = launches;
     return 0;
@@ -94,7 +96,14 @@ int learner_grad(M m, const pvae_fc_ppo_batch* b, const int32_t* index, long lon
     int launches = 0;
     const PpoDiagRow dg = diag_row(q.diag, 0);
     if ((rc = m.grad_half(b, index, first, rows, p, 0, rows, dg.dpart, st, &launches))) return rc;
+    PpoAdamSegs sg;
+    if (q.clip.slot) {
+        if ((rc = m.segments(p, sg))) return rc;
+        if ((rc = ppo_clip_sumsq_launch(sg, p, rows, b->k, q.scratch, colsum, q.log_std, q.clip, st, &launches))) return rc;
+    }
     if ((rc = ppo_grad_finish_launch(rows, b->k, q.scratch, colsum, ls_grad, stats_out, dg, st, &launches))) return rc;
+    // a clip bound: the gradient left behind is the clipped one (and *_ppo_apply does not clip again)
+    if (q.clip.slot && (rc = ppo_clip_scale_launch(sg, p, b->k, ls_grad, colsum, q.clip, dg, st, &launches))) return rc;
     q.launches = launches;
     return 0;
 }

@@ -156,6 +156,29 @@ class PpoSurface:
         puts back afterwards (`ppo_diag(*bound)`)."""
         return getattr(self, "_ppo_diag_keep", None)
 
+    def ppo_grad_clip(self, max_norm=None):
+        """`*_ppo_grad_clip`: bind global-norm gradient clipping at `max_norm` (a positive finite float) into the fused
+        steps, or unbind (None).  While bound `ppo_step` / `ppo_sgd` clip this worker's gradient ahead of Adam (one launch
+        more), `ppo_grad_step` leaves the clipped gradient behind and `ppo_apply` does not clip again; see `ppo.py`'s module
+        docstring for the rule and `ppo.DIAG_CLIP` for the two diagnostics entries.  The scratch is allocated once and kept
+        with the engine."""
+        self._need_gpu()
+        what = self._PPO + "grad_clip"
+        if max_norm is None:
+            self._ppo_clip_keep = None
+            return _lib.check(getattr(self.lib, what)(self.ctx, 0.0, None, 0), what)
+        if getattr(self, "ppo_clip_scratch", None) is None:
+            cfg = C.byref(self.cfg) if self._PPO == "pvae_fc_ppo_" else self.ctx
+            self.ppo_clip_bytes = int(getattr(self.lib, what + "_bytes")(cfg))
+            self.ppo_clip_scratch = torch.zeros(self.ppo_clip_bytes // 8 + 2, dtype=torch.float64, device=self.device)
+        _lib.check(getattr(self.lib, what)(self.ctx, float(max_norm), self.ppo_clip_scratch.data_ptr(), self.ppo_clip_bytes), what)
+        self._ppo_clip_keep = float(max_norm)
+
+    def ppo_grad_clip_bound(self):
+        """`max_norm` as `ppo_grad_clip` bound it last, or None: what a caller that binds a clip of its own for one call puts
+        back afterwards."""
+        return getattr(self, "_ppo_clip_keep", None)
+
     def ppo_launches(self):
         """Kernel launches of the last PPO step."""
         n = C.c_int32()
@@ -346,7 +369,11 @@ class PpoPolicy:
             check_diag(diag_out, P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter), eng.device)
             bound = eng.ppo_diag_bound()
             eng.ppo_diag(diag_out)
+        clip = getattr(config, "grad_clip", None)
+        clip_bound = eng.ppo_grad_clip_bound() if clip is not None else None
         try:
+            if clip is not None:                 # (`ppo.ClippedPPOConfig`: bound in the library for this call)
+                eng.ppo_grad_clip(clip)
             if dp is not None and dp.transport == "torch":
                 shape = (P.dp_steps(n, config.sgd_minibatch_size, config.num_sgd_iter), config.sgd_minibatch_size)
                 stats = dp.sgd(eng, cols, lambda i: config.params(kind, base, adam_t=t + 1 + i, train_mask=train_mask), n,
@@ -356,6 +383,8 @@ class PpoPolicy:
                 stats = eng.ppo_sgd(cols, params, config.sgd_minibatch_size, config.num_sgd_iter, perm,
                                     **self._ppo_draws("learn", eps))
         finally:
+            if clip is not None:
+                eng.ppo_grad_clip(clip_bound)                 # what the caller had bound before comes back
             if diag_out is not None:
                 eng.ppo_diag(*(bound or (None,)))             # what the caller had bound before comes back
         self.__dict__["_ppo_t"] = t + stats.shape[0]

@@ -900,7 +900,10 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         minibatch is `pvae_ppo_grad`, an all-reduce of both gradient arenas, `pvae_ppo_apply`.  `diag_out`: a float32 device
         tensor [steps, PPO_DIAG] from `ppo.diag_buffer`, filled in place with the per-step learner diagnostics (`ppo.DIAG`;
         one small launch more per step, nothing synchronised); a wrong shape or device is a ValueError.  Rows the
-        caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns."""
+        caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns.
+        `config`: a `ppo.ClippedPPOConfig` with `grad_clip` set clips every step's gradient by its global norm ahead of Adam (the
+        rule: `ppo.py`'s module docstring; bound in the library for this call alone, one launch more per step; with `dp`
+        every worker clips its own gradient before the average; `diag_out` then also carries `ppo.DIAG_CLIP`)."""
         return self._policy_learn(batch, config, perm, eps, dp, diag_out)
 
     def set_exploration_std(self, std):

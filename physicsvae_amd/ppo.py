@@ -94,6 +94,33 @@ installation was at hand).  For a train batch of n rows, pass p of num_sgd_iter,
     draws nothing else, so under perm="philox", and only then, its `ppo_learn` advances `_rng_calls` by 1 (two consecutive
     iterations would otherwise draw the same order).  perm=None (row order) or a tensor: the accounting is unchanged;
   * workers with the same seed draw the same order over their own rows (the rank does not enter the stream).
+
+Global-norm gradient clipping (RLlib's `grad_clip`; `ClippedPPOConfig`, `*_ppo_grad_clip`).  For one minibatch step of one
+worker, with g this worker's own gradient over everything its Adam launch would consume -- every trained segment and a
+trained state-independent log-std vector; stacks frozen by the train mask do not enter; before weight decay:
+
+    s       = sum g_i^2                                    squares and sums in double, fixed order, no atomics
+    norm    = float32(sqrt(s))
+    coef    = min(1.0f, max_norm / (norm + 1e-6f))         float32 throughout (torch.nn.utils.clip_grad_norm_)
+    g'_i    = g_i * coef                                   one float32 multiply per element, pinned, ALSO when coef == 1
+
+and Adam consumes g'.  When coef == 1.0f the product is g bit for bit, so a threshold that never bites gives the unclipped
+step's parameters, moments and stats bit for bit.  More than one worker: every worker clips its own gradient first, then the
+clipped gradients are averaged by the rule above,
+
+    g = (((g'_0 + g'_1) + ...) + g'_{N-1}) * float32(1 / N)          rank order, float32
+
+  * this is RLlib 1.11's order AS RECALLED (torch_policy: `extra_grad_process` -> `apply_grad_clipping` runs after
+    `backward()` and before the `all_reduce`); it has not been checked against a ray installation, none was at hand.  It
+    is also the order under which the exchanged Adam launch stays one launch;
+  * non-finite norms follow the float32 formula, whatever it gives (a NaN quotient stays NaN, as `torch.clamp` leaves it);
+  * `clip_coef_torch` is the formula in torch, `dp_clip_mean_torch` composes it with `dp_mean_torch`;
+  * the plain `PPOConfig` keeps refusing `grad_clip`; `ClippedPPOConfig` is the opt-in.  `ppo_learn` binds the clip in the
+    library for the duration of the call: one launch more per step (a sum-of-squares pass between the backward and the Adam
+    launch); on the "torch" transport `*_ppo_grad` leaves the clipped gradient behind and `*_ppo_apply` does not clip again;
+  * with diagnostics bound as well, entry 4 `grad_gnorm` keeps its meaning (what Adam consumes, after clip and average) and
+    the reserved entries 5 and 6 are `DIAG_CLIP`: the worker's own norm before the clip (what RLlib reports as
+    `grad_gnorm`) and coef.
 """
 import math
 
@@ -109,6 +136,8 @@ SAMPLE_BATCH_KEYS = {"obs": "obs", "actions": "actions", "action_dist_inputs": "
 STATS = ("total_loss", "policy_loss", "vf_loss", "kl", "entropy")
 # the per-step learner diagnostics (include/pvae.h "Learner diagnostics"): rows of PPO_DIAG floats, entries 5..7 reserved (0)
 DIAG = ("vf_explained_var", "clip_frac", "vf_clip_frac", "ratio_max_dev", "grad_gnorm")
+# entries 5 and 6 of a diagnostics row while a clip is bound (0 otherwise): this worker's own norm before the clip, and coef
+DIAG_CLIP = ("grad_gnorm_raw", "grad_clip_coef")
 PPO_DIAG = _lib.PPO_DIAG
 
 
@@ -156,6 +185,22 @@ class PPOConfig:
         p.log_std_kind = _lib.LOG_STD_KINDS[log_std_kind] if isinstance(log_std_kind, str) else int(log_std_kind)
         p.log_std_base = float(log_std_base)
         return p
+
+
+class ClippedPPOConfig(PPOConfig):
+    """`PPOConfig` that takes RLlib's `grad_clip`: None, or a positive finite float, the `max_norm` of the global-norm clip
+    the fused steps apply ahead of Adam (the rule: the module docstring).  Everything else, `from_spec` included, is
+    inherited; the base class keeps refusing the key, so a clip is always asked for by name."""
+
+    def __init__(self, *args, grad_clip=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        if grad_clip is not None:
+            ok = isinstance(grad_clip, (int, float)) and not isinstance(grad_clip, bool) and math.isfinite(grad_clip) \
+                and grad_clip > 0
+            if not ok:
+                raise ValueError("grad_clip=%r: None or a positive finite float" % (grad_clip,))
+            grad_clip = float(grad_clip)
+        self.grad_clip = grad_clip
 
 
 def make_gae_params(gamma, lambda_, standardize=True, log_std_kind=0, log_std_base=0.0):
@@ -429,6 +474,25 @@ def grad_gnorm_torch(grads):
     for g in grads:
         total = total + (g.detach().double() ** 2).sum().cpu()
     return torch.sqrt(total)
+
+
+def clip_coef_torch(grads, max_norm):
+    """The clip of the module docstring in torch: (norm, coef), float32 scalars on the CPU, of the tensors given -- the
+    squares summed in float64 (`grad_gnorm_torch`), norm = float32(sqrt), coef = min(1, max_norm / (norm + 1e-6)) in
+    float32, what `torch.nn.utils.clip_grad_norm_` multiplies the gradients by."""
+    norm = grad_gnorm_torch(grads).to(torch.float32)
+    coef = torch.clamp(torch.tensor(float(max_norm), dtype=torch.float32) / (norm + torch.tensor(1e-6, dtype=torch.float32)), max=1.0)
+    return norm, coef
+
+
+def dp_clip_mean_torch(grads_by_rank, max_norm):
+    """Clip, then average: `grads_by_rank[r]` is worker r's list of gradient tensors (every list the same shapes, in rank
+    order).  Every worker's list is scaled by ITS `clip_coef_torch` -- one float32 multiply per element, also when the
+    coefficient is 1 -- and tensor j of the result is `dp_mean_torch` over the workers' scaled tensor j.  Returns (the list
+    of averaged tensors, [rank r's coef])."""
+    coefs = [clip_coef_torch(g, max_norm)[1] for g in grads_by_rank]
+    scaled = [[t * c.to(t.device, t.dtype) for t in g] for g, c in zip(grads_by_rank, coefs)]
+    return [dp_mean_torch([s[j] for s in scaled]) for j in range(len(grads_by_rank[0]))], coefs
 
 
 def diag_buffer(n_rows, config, device):

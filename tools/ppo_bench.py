@@ -16,6 +16,9 @@ and (d) the acceptance figure: (a.median - x.median) / (a.max - a.min), which mu
 `--order`: time the minibatch order instead (tools/order_bench.py): `pvae_ppo_order` against the torch.randperm stack it
 replaces, and the whole `ppo_learn` call (sgd_minibatch_size `--rows`, 20 passes) with the order made each of the ways named.
 `--diag`: ways c and d run with a learner-diagnostics buffer bound (`ppo_diag`; one small launch more per step).
+`--grad-clip X`: global-norm gradient clipping at max_norm X -- ways a and b get `clip_grad_norm_` between backward() and
+the optimizer step, and a fifth way is timed in the same rounds, alternating with (d): e  ppo_sgd_clip, (d) with the clip
+bound (`ppo_grad_clip`: one launch more per step); (c) and (d) stay unbound.  Reported beside it: e.median - d.median.
 `--one-step`: run a single fused step per log-std type and exit (for a kernel trace of one step).
 """
 import argparse
@@ -81,12 +84,14 @@ def main():
     ap.add_argument("--one-step", action="store_true")
     ap.add_argument("--diag", action="store_true",
                     help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
+    ap.add_argument("--grad-clip", type=float, default=None,
+                    help="max_norm: ways a and b with clip_grad_norm_, and way e = way d with the clip bound")
     order_bench.add_arguments(ap)
     a = ap.parse_args()
     if a.order:
         return order_mode(a)
     cfg = P.PPOConfig(clip_param=0.2, kl_coeff=0.0, vf_clip_param=1000.0, lr=1e-6, sgd_minibatch_size=a.rows, num_sgd_iter=1)
-    out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": OBS, "diag": bool(a.diag)}
+    out = {"rows": a.rows, "steps": a.steps, "rounds": a.rounds, "obs": OBS, "diag": bool(a.diag), "grad_clip": a.grad_clip}
     for kind in ("constant", "state_dependent"):
         torch.manual_seed(0)
         g = torch.Generator(device="cuda").manual_seed(0)
@@ -109,12 +114,18 @@ def main():
         loss_cols = {k: v for k, v in cols.items() if k != "obs"}
         hip_cols = None
         t = [0]
+        clipped = list(m.parameters())
+
+        def clip_twin():
+            if a.grad_clip is not None:
+                torch.nn.utils.clip_grad_norm_(clipped, a.grad_clip)
 
         def update_torch_loss():
             opt.zero_grad(set_to_none=True)
             logits, _ = m.forward({"obs_flat": obs}, [], None)
             total, _ = P.ppo_loss_torch(logits[:, :K], logits[:, K:], m.value_function(), cfg=cfg, **loss_cols)
             total.backward()
+            clip_twin()
             opt.step()
 
         def update_hip_loss():
@@ -122,6 +133,7 @@ def main():
             logits, _ = m.forward({"obs_flat": obs}, [], None)
             total, _ = P.HipPPOLoss.apply(logits[:, :K], logits[:, K:], m.value_function(), hip_cols, loss_params, None)
             total.backward()
+            clip_twin()
             opt.step()
 
         stats = torch.empty(5, device="cuda")
@@ -142,6 +154,14 @@ def main():
             t[0] += a.steps
             eng.ppo_sgd(fbig, cfg.params(kind, base, adam_t=t[0]), a.rows, 1)
 
+        def sgd_clip_block():
+            eng.ppo_grad_clip(a.grad_clip)
+            try:
+                sgd_block()
+                return eng.ppo_launches()
+            finally:
+                eng.ppo_grad_clip(None)
+
         per_call = (("a_update", update_torch_loss), ("b_hip_loss", update_hip_loss), ("c_ppo_step", step_once))
         for _, fn in per_call:
             for _ in range(a.warmup):
@@ -149,6 +169,9 @@ def main():
         sgd_block()
         means = {name: [] for name, _ in per_call}
         means["d_ppo_sgd"] = []
+        if a.grad_clip is not None:
+            clip_launches = sgd_clip_block()
+            means["e_ppo_sgd_clip"] = []
         for _ in range(a.rounds):                    # the ways alternate within the session
             for name, fn in per_call:
                 torch.cuda.synchronize()
@@ -162,11 +185,21 @@ def main():
             sgd_block()
             torch.cuda.synchronize()
             means["d_ppo_sgd"].append((time.perf_counter() - t0) / a.steps * 1e6)
+            if a.grad_clip is not None:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sgd_clip_block()
+                torch.cuda.synchronize()
+                means["e_ppo_sgd_clip"].append((time.perf_counter() - t0) / a.steps * 1e6)
         res = {name: {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
                for name, v in means.items()}
         spread = res["a_update"]["max"] - res["a_update"]["min"]
         for name in ("c_ppo_step", "d_ppo_sgd"):
             res[name]["gain_over_a_in_spreads_of_a"] = round((res["a_update"]["median"] - res[name]["median"]) / max(spread, 1e-9), 1)
+        if a.grad_clip is not None:
+            res["e_ppo_sgd_clip"]["over_d_us"] = round(res["e_ppo_sgd_clip"]["median"] - res["d_ppo_sgd"]["median"], 1)
+            res["e_ppo_sgd_clip"]["launches_per_step"] = clip_launches
+            sgd_block()                              # (the counter below is the unbound step's)
         res["launches_per_step"] = eng.ppo_launches()
         out[kind] = res
     print(json.dumps(out))

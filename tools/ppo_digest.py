@@ -21,6 +21,10 @@ the line is the one printed without the flag.  `--order philox` draws every `per
 device instead (`ppo_order` at seed 11, offset 5; a library without `pvae_ppo_order` cannot run it) and adds the scenario
 "order": the order itself at 70, 8192, 8193 and 20000 rows -- one workgroup in LDS, and tiles with one and two merge
 launches.
+
+`--grad-clip X` adds the learner scenarios (the sgd loops, the single steps and gradient + apply of both models) once more
+with global-norm gradient clipping bound at max_norm X (`ppo_grad_clip`), under names that start with "clip": every other
+digest is the one printed without the flag.  A library without `pvae_fc_ppo_grad_clip` cannot run it.
 """
 import argparse
 import hashlib
@@ -41,6 +45,7 @@ CFG = P.PPOConfig(clip_param=0.2, kl_coeff=0.3, entropy_coeff=0.01, vf_clip_para
                   gamma=0.98, lambda_=0.95)
 DIAG = False                                                     # set by main() from `--diag`
 ORDER = "none"                                                   # set by main() from `--order`
+CLIP = None                                                      # set by main() for the scenarios `--grad-clip` adds
 
 
 def bind_diag(eng):
@@ -49,6 +54,8 @@ def bind_diag(eng):
     if DIAG:
         eng.diag_rows = torch.zeros(8, P.PPO_DIAG, dtype=torch.float32, device=DEV)
         eng.ppo_diag(eng.diag_rows)
+    if CLIP is not None:
+        eng.ppo_grad_clip(CLIP)
 
 
 def digest(tensors):
@@ -297,10 +304,11 @@ def vae_act(out):
 
 
 def main():
-    global DIAG, ORDER
+    global DIAG, ORDER, CLIP
     ap = argparse.ArgumentParser()
     ap.add_argument("--diag", action="store_true")
     ap.add_argument("--order", choices=("philox", "none"), default="none")
+    ap.add_argument("--grad-clip", type=float, default=None)
     a = ap.parse_args()
     DIAG, ORDER = a.diag, a.order
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
@@ -308,6 +316,11 @@ def main():
     for scenario in (fc_sgd, fc_steps, fc_act, loss, gae, fc_prepare, vae_sgd, vae_steps, vae_act, vae_prepare) + (
             (order,) if ORDER == "philox" else ()):
         scenario(out)
+    if a.grad_clip is not None:
+        CLIP, clipped = a.grad_clip, {}
+        for scenario in (fc_sgd, fc_steps, vae_sgd, vae_steps):
+            scenario(clipped)
+        out.update({"clip%g %s" % (CLIP, name): d for name, d in clipped.items()})
     print(json.dumps(out, sort_keys=True))
 
 

@@ -16,6 +16,9 @@ and (d) the acceptance figure: (b.median - x.median) / (b.max - b.min), which mu
 `--order`: time the minibatch order instead (tools/order_bench.py): `pvae_ppo_order` against the torch.randperm stack it
 replaces, and the whole `ppo_learn` call (sgd_minibatch_size `--rows`, 20 passes) with the order made each of the ways named.
 `--diag`: ways c and d run with a learner-diagnostics buffer bound (`ppo_diag`; one small launch more per step).
+`--grad-clip X`: global-norm gradient clipping at max_norm X -- ways a and b get `clip_grad_norm_` between backward() and
+the optimizer step, and a fifth way is timed in the same rounds, alternating with (d): e  ppo_sgd_clip, (d) with the clip
+bound (`ppo_grad_clip`: one launch more per step); (c) and (d) stay unbound.  Reported beside it: e.median - d.median.
 `--one-step`: run a single fused step and exit (for a kernel trace of one step).
 """
 import argparse
@@ -84,6 +87,8 @@ def main():
     ap.add_argument("--one-step", action="store_true")
     ap.add_argument("--diag", action="store_true",
                     help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
+    ap.add_argument("--grad-clip", type=float, default=None,
+                    help="max_norm: ways a and b with clip_grad_norm_, and way e = way d with the clip bound")
     order_bench.add_arguments(ap)
     a = ap.parse_args()
     if a.order:
@@ -105,6 +110,7 @@ def main():
     eng = f.engine
     eng.ppo_bind(f._ppo_value_engine(), f._als.on_device(eng.device), False)
     out["diag"] = bool(a.diag)
+    out["grad_clip"] = a.grad_clip
     if a.diag:
         eng.ppo_diag(torch.zeros(a.steps, P.PPO_DIAG, dtype=torch.float32, device="cuda"))       # one row per step of way d
     fb, fbig = eng.ppo_batch(cols), eng.ppo_batch(P.batch_columns(big))
@@ -112,12 +118,18 @@ def main():
     loss_cols = {k: v for k, v in cols.items() if k != "obs"}
     hip_cols = make_ppo_batch(loss_cols, "cuda", DA)
     t = [0]
+    clipped = list([p for p in m.parameters() if p.requires_grad])
+
+    def clip_twin():
+        if a.grad_clip is not None:
+            torch.nn.utils.clip_grad_norm_(clipped, a.grad_clip)
 
     def update_torch_loss():
         opt.zero_grad(set_to_none=True)
         logits, _ = m.forward({"obs_flat": obs}, [], None)
         total, _ = P.ppo_loss_torch(logits[:, :DA], logits[:, DA:], m.value_function(), cfg=cfg, **loss_cols)
         total.backward()
+        clip_twin()
         opt.step()
 
     def update_hip_loss():
@@ -125,6 +137,7 @@ def main():
         logits, _ = m.forward({"obs_flat": obs}, [], None)
         total, _ = P.HipPPOLoss.apply(logits[:, :DA], logits[:, DA:], m.value_function(), hip_cols, loss_params, None)
         total.backward()
+        clip_twin()
         opt.step()
 
     stats = torch.empty(5, device="cuda")
@@ -144,6 +157,14 @@ def main():
         eng.ppo_sgd(fbig, cfg.params("constant", adam_t=t[0] + 1), a.rows, 1, offset=t[0] + 1)
         t[0] += a.steps
 
+    def sgd_clip_block():
+        eng.ppo_grad_clip(a.grad_clip)
+        try:
+            sgd_block()
+            return eng.ppo_launches()
+        finally:
+            eng.ppo_grad_clip(None)
+
     per_call = (("a_update", update_torch_loss), ("b_hip_loss", update_hip_loss), ("c_ppo_step", step_once))
     for _, fn in per_call:
         for _ in range(a.warmup):
@@ -151,6 +172,9 @@ def main():
     sgd_block()
     means = {name: [] for name, _ in per_call}
     means["d_ppo_sgd"] = []
+    if a.grad_clip is not None:
+        clip_launches = sgd_clip_block()
+        means["e_ppo_sgd_clip"] = []
     for _ in range(a.rounds):                    # the ways alternate within the session
         for name, fn in per_call:
             torch.cuda.synchronize()
@@ -164,11 +188,21 @@ def main():
         sgd_block()
         torch.cuda.synchronize()
         means["d_ppo_sgd"].append((time.perf_counter() - t0) / a.steps * 1e6)
+        if a.grad_clip is not None:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sgd_clip_block()
+            torch.cuda.synchronize()
+            means["e_ppo_sgd_clip"].append((time.perf_counter() - t0) / a.steps * 1e6)
     res = {name: {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
            for name, v in means.items()}
     spread = res["b_hip_loss"]["max"] - res["b_hip_loss"]["min"]
     for name in ("c_ppo_step", "d_ppo_sgd"):
         res[name]["gain_over_b_in_spreads_of_b"] = round((res["b_hip_loss"]["median"] - res[name]["median"]) / max(spread, 1e-9), 1)
+    if a.grad_clip is not None:
+        res["e_ppo_sgd_clip"]["over_d_us"] = round(res["e_ppo_sgd_clip"]["median"] - res["d_ppo_sgd"]["median"], 1)
+        res["e_ppo_sgd_clip"]["launches_per_step"] = clip_launches
+        sgd_block()                              # (the counter below is the unbound step's)
     res["launches_per_step"] = eng.ppo_launches()
     out["constant"] = res
     print(json.dumps(out))
