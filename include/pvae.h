@@ -237,7 +237,10 @@ int pvae_set_direct(pvae_ctx* ctx, int on);
  *   ctx, not a schedule switch:  "joint_s_rec" (0 / 1, default 0): the joint phase accepts pvae_step_params.s_rec_coeff != 0
  *       (see pvae_forward_backward).  A context that has not opted in keeps refusing that combination with -4, as every
  *       context did before the term was built; the supervised trainer opts in when its config holds a non-zero
- *       world_model_s_rec_coeff. */
+ *       world_model_s_rec_coeff.
+ *   "ppo_priors" (0 / 1, default 0): the PPO passes of PhysicsVAE (pvae_ppo_step / _sgd / _grad / _apply / _evaluate /
+ *       _prepare / _act) also run under the priors STATE_MEAN and HYPERSPHERE (see "PPO learner step of PhysicsVAE").  A
+ *       context that has not opted in keeps answering -1 with the message every context gave before they were built. */
 int pvae_set_option(pvae_ctx* ctx, const char* name, int64_t value);
 int pvae_direct_active(pvae_ctx* ctx, int phase, int32_t rows, const pvae_step_params* sp, int fused);
 
@@ -873,7 +876,24 @@ int pvae_gae_sizeof(int which);
  *                      not gathered through perm) or Philox offset rng_offset + i, and Adam time step adam_t + i.
  *   pvae_ppo_launches  kernel launches of the last step.
  *   pvae_ppo_sizeof    sizeof(pvae_fc_ppo_params) / sizeof(pvae_fc_ppo_batch) / sizeof(pvae_config): which = 0 / 1 / 2
- * Needs lookahead 1, prior ZERO_MEAN or NONE, no helper stack.  Bad arguments, an unbound buffer or rows > max_batch return a
+ * The priors STATE_MEAN and HYPERSPHERE are OPT-IN: pvae_set_option(ctx, "ppo_priors", 1); a context that was not told answers
+ * -1 for them ("the PPO step supports the priors normal_zero_mean_one_std and False ...").  With the option set:
+ *   STATE_MEAN   the policy's output does not depend on the learned prior mean (rmt:801-809 only records it) and the PPO
+ *                loss has no KL-to-prior term: every pass launches exactly what ZERO_MEAN launches, the sampler backward with
+ *                its logvar half.  The prior stack (PVAE_NET_PR) is never launched and is in no Adam segment: its bits in the
+ *                parameter arena and in grad / m / v are left alone, and it enters neither the clip norm nor grad_gnorm.
+ *   HYPERSPHERE  the encoder's output is Z wide; sampler: z = e / max(|e|, 1e-12) (sphere_kernel).  NOTHING is drawn: the prior
+ *                sample of rmt:810-814 reaches neither the action nor the loss, so the PPO passes run the sampler with noise
+ *                off whatever the caller passed; eps / noise are accepted and not read, and the draws that come back
+ *                (the panel of the draws used, pvae_ppo_draws.eps_out) are zeros, as under NONE.  Sampler backward: one wavefront per
+ *                row, grid rows_pad / 4, with e the encoder's output row and g the z columns of the decoder's input gradient
+ *                    ie = 1 / max(sqrt(sum e^2), 1e-12);   zg = (sum e g) ie;   de = (g - e ie zg) ie
+ *                in the summation order of pvae_reparam_backward (one device function serves both), over the whole padded
+ *                panel, no atomics, the same bits every run.  It takes the sampler-backward slot: the launch count is the
+ *                one above.  Under md_inputs = BODY the encoder's gradient is exactly zero.  (Z = 1: z = sign(e), and the
+ *                encoder's gradient is a rounding residue around an exact zero.)
+ * The helper stack and lookahead > 1 remain refused with or without the option.
+ * Needs lookahead 1, prior ZERO_MEAN or NONE (or the option above), no helper stack.  Bad arguments, an unbound buffer or rows > max_batch return a
  * negative code and launch nothing.  Within that, nothing else about the configuration is refused, and all of it is tested
  * against float64 (tests/test_gpu_ppo_vae_shapes.py, the evaluate pass below included): input subsets on either stack
  * (te_inputs / md_inputs; the columns outside a window stay exactly zero in parameters, gradients and both moments, and

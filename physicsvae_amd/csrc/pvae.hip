@@ -168,6 +168,7 @@ int pvae_set_option(pvae_ctx* c, const char* name, int64_t value) {
     else if (k == "same_layer") c->same_layer_pairs = v != 0;
     else if (k == "fold_sampler") c->fold_sampler = v != 0;
     else if (k == "joint_s_rec") c->joint_s_rec = v != 0;
+    else if (k == "ppo_priors") c->ppo_priors = v != 0;
     else if (k == "direct") return pvae_set_direct(c, v);
     else if (k == "p2p_timeout_ms") { if (value > 0) c->p2p.timeout_ticks = (long long)value * 100000ll; }
     else if (k == "p2p_selftest_flags_only") c->p2p_selftest_flags_only = v != 0;

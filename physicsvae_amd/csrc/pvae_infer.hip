@@ -47,13 +47,7 @@ sampler_bwd_kernel(const float* __restrict__ mu_logvar, int ldte, const float* _
     const float* g = dz + (size_t)r * Z;
     float* d = d_ml + (size_t)r * ldte;
     if (kind == PVAE_PRIOR_HYPERSPHERE) {
-        float e2 = 0.f, eg = 0.f;
-        for (int c = lane; c < Z; c += 64) { e2 += e[c] * e[c]; eg += e[c] * g[c]; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { e2 += __shfl_xor(e2, o, 64); eg += __shfl_xor(eg, o, 64); }
-        const float ie = 1.0f / fmaxf(sqrtf(e2), 1e-12f);
-        const float zg = eg * ie;                                  // <z, dz>
-        for (int c = lane; c < Z; c += 64) d[c] = (g[c] - e[c] * ie * zg) * ie;
+        sphere_bwd_row(e, g, Z, lane, d);                          // (pvae_internal.h: shared with the fused PPO step)
     } else if (kind == PVAE_PRIOR_NONE) {
         for (int c = lane; c < Z; c += 64) d[c] = g[c];
     } else {
@@ -550,6 +544,9 @@ int ppo_forward_net(pvae_ctx* c, int net, int rows, hipStream_t st, int* launche
 int ppo_sampler(pvae_ctx* c, const float* eps, int rows, int noise, uint64_t seed, uint64_t offset, hipStream_t st,
                 int* launches) {
     const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    // the sphere prior's sample reaches neither the action nor the PPO loss (rmt:810-814 records it): nothing is drawn,
+    // whatever the caller passed, and the draws that come back are zeros -- as under latent_prior_type False
+    if (c->L.cfg.prior_kind == PVAE_PRIOR_HYPERSPHERE) noise = 0;
     const int rc = launch_sampler(c, c->ws + c->W.net[PVAE_NET_TE].act.back(), TE.layers.back().n_out_pad, eps,
                                   c->ws + c->W.eps, c->ws + c->W.net[PVAE_NET_MD].in, c->L.net[PVAE_NET_MD].layers[0].ld, rows,
                                   pad32(rows), noise ? 1 : 0, (unsigned long long)seed, (unsigned long long)offset,

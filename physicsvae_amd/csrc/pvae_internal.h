@@ -285,6 +285,7 @@ struct pvae_ctx {
     bool p2p_selftest_flags_only = false;   // option: the attach-time self-test skips the cached-arena part
     int server_mailbox = 0;                 // option: where the rollout server's request block lives (0 auto, 1 host, 2 device)
     bool joint_s_rec = false;      // option "joint_s_rec": the joint phase runs with world_model_s_rec_coeff != 0 (default: refused, -4)
+    bool ppo_priors = false;       // option "ppo_priors": the PPO passes run under the learned and the sphere prior (default: refused, -1)
     bool fold_sampler = true;      // the sampler runs as the prologue of the decoder's first-layer launch (PVAE_FOLD_SAMPLER=0: its own launch)
                                    // (ProSampler).  Off by default: one launch less, but the step is not shorter -- the kernel
                                    // trace shows 6.4-7.0 us for the merged launch against 4.4 + 4.6, and the un-profiled
@@ -376,6 +377,22 @@ __device__ inline float philox_normal(uint64_t seed, uint64_t offset, uint32_t r
 __device__ inline float block_sum_256(float v) {
     __shared__ float red[4];
     return block_sum_256(v, red);
+}
+
+// Backward of the unit-sphere projection z = e / max(|e|, 1e-12) (sphere_kernel, pvae_net.hip) on ONE row by ONE wavefront
+// (all 64 lanes call it): e, g = dz, d = de each Z floats.  Lanes stride the columns by 64, then the xor-shuffle tree from 32
+// down -- the one summation order of the autograd path (sampler_bwd_kernel, pvae_infer.hip) and of the fused PPO step
+// (ppo_sphere_bwd_kernel, pvae_ppo.hip), which both call this.
+//   ie = 1 / max(sqrt(sum e^2), 1e-12);   zg = (sum e g) ie = <z, dz>;   de = (g - e ie zg) ie
+__device__ inline void sphere_bwd_row(const float* __restrict__ e, const float* __restrict__ g, int Z, int lane,
+                                      float* __restrict__ d) {
+    float e2 = 0.f, eg = 0.f;
+    for (int c = lane; c < Z; c += 64) { e2 += e[c] * e[c]; eg += e[c] * g[c]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { e2 += __shfl_xor(e2, o, 64); eg += __shfl_xor(eg, o, 64); }
+    const float ie = 1.0f / fmaxf(sqrtf(e2), 1e-12f);
+    const float zg = eg * ie;                                  // <z, dz>
+    for (int c = lane; c < Z; c += 64) d[c] = (g[c] - e[c] * ie * zg) * ie;
 }
 
 // The same sampler as the PROLOGUE of the decoder's first-layer launch (pvae_gemm_ws.h, splitk_ws_pertile_body): every

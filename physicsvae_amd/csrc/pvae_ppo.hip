@@ -65,6 +65,25 @@ ppo_sampler_bwd_kernel(const float* __restrict__ te_out, const float* __restrict
     }
 }
 
+// The same under the sphere prior (PVAE_PRIOR_HYPERSPHERE; forward: sphere_kernel, z = e / max(|e|, 1e-12)), which needs a
+// reduction over the row: one wavefront per row, four rows per workgroup, grid rows_pad / 4, the row's arithmetic that of
+// the autograd path (sphere_bwd_row, pvae_internal.h).  e = the encoder's output panel, g = the z columns of the decoder's
+// input gradient; de -> the encoder's output gradient panel, again over its WHOLE [rows_pad][ld] block: zeros in the pad
+// columns [Z, ld) and in the pad rows.  No atomics, one summation order: the same bits every run.
+__global__ void __launch_bounds__(256)
+ppo_sphere_bwd_kernel(const float* __restrict__ te_out, const float* __restrict__ d_md_in, int ld_md, int Db, int Z, int rows,
+                      int rows_pad, float* __restrict__ dz_te, int ld) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows_pad) return;
+    float* d = dz_te + (size_t)r * ld;
+    if (r >= rows) {
+        for (int c = lane; c < ld; c += 64) d[c] = 0.f;
+        return;
+    }
+    sphere_bwd_row(te_out + (size_t)r * ld, d_md_in + (size_t)r * ld_md + Db, Z, lane, d);
+    for (int c = Z + lane; c < ld; c += 64) d[c] = 0.f;
+}
+
 enum { kTrainTE = 1, kTrainMD = 2, kTrainValue = 4 };
 
 // the copy-in launch: rows `index[r]` (index NULL: row0 + r) of obs [n_rows][2 Db] into the three input panels
@@ -94,10 +113,12 @@ int ppo_copy_in(pvae_ctx* c, const FcValueStack& vs, const float* obs, const int
 
 size_t scratch_bytes(const pvae_config& cfg) { return ppo_scratch_bytes(cfg.max_batch, cfg.dim_action); }
 
-// what neither the step nor the evaluate pass runs: lookahead > 1, the learned and the sphere prior, the helper
-int check_ppo_config(const pvae_config& cfg) {
+// what neither the step nor the evaluate pass runs: lookahead > 1, the helper, and -- in a context that was not told
+// otherwise (option "ppo_priors") -- the learned and the sphere prior
+int check_ppo_config(const pvae_ctx* c) {
+    const pvae_config& cfg = c->L.cfg;
     if (cfg.lookahead != 1) return fail(-1, "the PPO step needs a lookahead 1 context, got %d", cfg.lookahead);
-    if (cfg.prior_kind != PVAE_PRIOR_ZERO_MEAN && cfg.prior_kind != PVAE_PRIOR_NONE)
+    if (!c->ppo_priors && cfg.prior_kind != PVAE_PRIOR_ZERO_MEAN && cfg.prior_kind != PVAE_PRIOR_NONE)
         return fail(-1, "the PPO step supports the priors normal_zero_mean_one_std and False, got prior_kind %d", cfg.prior_kind);
     if (cfg.mh_depth > 0) return fail(-1, "the PPO step does not run the motor decoder's helper");
     return 0;
@@ -152,7 +173,7 @@ struct VaeLearner {
         if (!b->obs) return fail(-1, "batch obs is null");
         if (!stats) return fail(-1, "stats_out is null");
         const pvae_config& cfg = c->L.cfg;
-        if ((rc = check_ppo_config(cfg)) || (rc = check_kind(p->log_std_kind))) return rc;
+        if ((rc = check_ppo_config(c)) || (rc = check_kind(p->log_std_kind))) return rc;
         if (!q.log_std) return fail(-2, "log_std vector not bound (pvae_ppo_bind)");
         if (p->log_std_kind == 1 && (!q.log_std_m || !q.log_std_v)) return fail(-2, "log_std moments not bound (pvae_ppo_bind)");
         if (b->k != cfg.dim_action) return fail(-1, "batch k %d != dim_action %d", b->k, cfg.dim_action);
@@ -249,11 +270,18 @@ int VaeLearner::grad_half(const pvae_fc_ppo_batch* b, const int32_t* index, long
     }
     if (md_back && (rc = ppo_backward_net(c, PVAE_NET_MD, rows, train_md, train_te, q.grad, st, &launches))) return rc;
     if (train_te) {
-        int gx = (rows_pad * te_last.n_out_pad + 255) / 256;
-        if (gx > 256) gx = 256;
-        hipLaunchKernelGGL(ppo_sampler_bwd_kernel, dim3(gx), dim3(256), 0, st, w + wte.act.back(), w + c->W.eps, w + wmd.d_in,
-                           MD.layers[0].ld, Db, Z, rows, rows_pad, cfg.prior_kind == PVAE_PRIOR_ZERO_MEAN ? 1 : 0, noise ? 1 : 0,
-                           w + wte.dz.back(), te_last.n_out_pad);
+        if (cfg.prior_kind == PVAE_PRIOR_HYPERSPHERE) {
+            hipLaunchKernelGGL(ppo_sphere_bwd_kernel, dim3(rows_pad / 4), dim3(256), 0, st, w + wte.act.back(), w + wmd.d_in,
+                               MD.layers[0].ld, Db, Z, rows, rows_pad, w + wte.dz.back(), te_last.n_out_pad);
+        } else {
+            // the learned prior mean (PVAE_PRIOR_STATE_MEAN) is recorded only (rmt:801-809): the sampler is the zero-mean one
+            const int with_logvar = cfg.prior_kind == PVAE_PRIOR_ZERO_MEAN || cfg.prior_kind == PVAE_PRIOR_STATE_MEAN;
+            int gx = (rows_pad * te_last.n_out_pad + 255) / 256;
+            if (gx > 256) gx = 256;
+            hipLaunchKernelGGL(ppo_sampler_bwd_kernel, dim3(gx), dim3(256), 0, st, w + wte.act.back(), w + c->W.eps, w + wmd.d_in,
+                               MD.layers[0].ld, Db, Z, rows, rows_pad, with_logvar ? 1 : 0, noise ? 1 : 0, w + wte.dz.back(),
+                               te_last.n_out_pad);
+        }
         HIP_TRY(hipGetLastError());
         ++launches;
         if ((rc = ppo_backward_net(c, PVAE_NET_TE, rows, true, false, q.grad, st, &launches))) return rc;
@@ -289,7 +317,7 @@ int VaeLearner::check_eval(const pvae_fc_rollout* ro, const pvae_gae_params* p, 
     const pvae_ctx::Ppo& q = c->ppo;
     if (!q.value) return fail(-2, "pvae_ppo_bind has not been called");
     const pvae_config& cfg = c->L.cfg;
-    if ((rc = check_ppo_config(cfg))) return rc;
+    if ((rc = check_ppo_config(c))) return rc;
     if (ro->n_rows < 1 || ro->n_rows > 0x7fffffffll) return fail(-1, "n_rows %lld out of range", (long long)ro->n_rows);
     if (rows_pass) {
         if ((rc = check_kind(p->log_std_kind))) return rc;

@@ -211,6 +211,13 @@ class HipEngine(PpoSurface, DataParallelExchange, RolloutClient):
         self._need_gpu()
         _lib.check(self.lib.pvae_set_option(self.ctx, b"joint_s_rec", 1 if on else 0), "pvae_set_option(joint_s_rec)")
 
+    def set_ppo_priors(self, on=True):
+        """The fused PPO passes run under the learned prior ("normal_state_mean_one_std") and the sphere prior
+        ("hypersphere_uniform") too (include/pvae.h pvae_set_option "ppo_priors"; the rules: `ppo.py`'s module docstring).
+        Opt-in: a context that was not told keeps refusing those two priors."""
+        self._need_gpu()
+        _lib.check(self.lib.pvae_set_option(self.ctx, b"ppo_priors", 1 if on else 0), "pvae_set_option(ppo_priors)")
+
     def direct_active(self, phase, rows, sp, fused=True):
         """Would a training step with these arguments take the direct path?"""
         self._need_gpu()

@@ -262,6 +262,9 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         "device": None,
         "max_batch": 256,
         "lookahead": 1,
+        # ours: the fused PPO passes (`compute_actions` / `ppo_prepare` / `ppo_learn`) also run under the priors
+        # "normal_state_mean_one_std" and "hypersphere_uniform" (the rules: `ppo.py`'s module docstring); off: refused by name
+        "ppo_priors": False,
     }
 
     def __init__(self, obs_space, action_space, num_outputs, model_config, name, **kwargs):
@@ -352,6 +355,10 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         self._value_branch = FC(vb_dims, act=vb.acts, inits=vb_init).to(self.engine.device)
         self._vb_act = vb.acts
         self.__dict__["_vb_stack"] = vb               # (the stack set of `ppo_learn` is built from it on first use)
+
+        self._ppo_priors = bool(cfg.get("ppo_priors"))
+        if self._ppo_priors and self.engine.ctx is not None:     # (no context on the CPU: nothing to tell)
+            self.engine.set_ppo_priors(True)
 
         self._st = _Cur()
         self._cur_value = None
@@ -767,10 +774,11 @@ class PhysicsVAE(PpoPolicy, nn.Module):
 
     # -- the fused PPO learner step (physicsvae_amd/ppo.py; include/pvae.h "PPO learner step of PhysicsVAE") ---------
     def _ppo_refusals(self):
-        """What the fused step does not run, refused by the configuration key that asks for it."""
+        """What the fused step does not run, refused by the configuration key that asks for it (the learned and the sphere
+        prior: unless the configuration opts in with "ppo_priors")."""
         if self._motor_decoder_helper is not None:
             raise NotImplementedError("motor_decoder_helper_enable: the fused PPO step does not run the decoder's helper")
-        if self._latent_prior_type not in ("normal_zero_mean_one_std", False):
+        if self._latent_prior_type not in ("normal_zero_mean_one_std", False) and not self._ppo_priors:
             raise NotImplementedError("latent_prior_type %r: the fused PPO step runs 'normal_zero_mean_one_std' and False"
                                       % (self._latent_prior_type,))
         if self.engine.lookahead != 1:
@@ -903,7 +911,9 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         caller bound before with `engine.ppo_diag(...)` are not written by this call and are bound again when it returns.
         `config`: a `ppo.ClippedPPOConfig` with `grad_clip` set clips every step's gradient by its global norm ahead of Adam (the
         rule: `ppo.py`'s module docstring; bound in the library for this call alone, one launch more per step; with `dp`
-        every worker clips its own gradient before the average; `diag_out` then also carries `ppo.DIAG_CLIP`)."""
+        every worker clips its own gradient before the average; `diag_out` then also carries `ppo.DIAG_CLIP`).  Under the learned
+        and the sphere prior (a configuration with "ppo_priors"; the rules: `ppo.py`'s module docstring) this call, `ppo_prepare`
+        and `compute_actions` take the same arguments; under the sphere `eps` is accepted and not read, and nothing is drawn."""
         return self._policy_learn(batch, config, perm, eps, dp, diag_out)
 
     def set_exploration_std(self, std):

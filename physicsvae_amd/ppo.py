@@ -71,6 +71,25 @@ for a state-dependent stack) and standard-normal noise n[r], all [k] (`sample_ac
     `latent_eps` does, because Philox goes through hardware transcendentals and cannot be reproduced on the host;
   * `RolloutBuffer` holds the train batch's columns on the device and lets every step write its rows in place.
 
+PhysicsVAE's latent under the learned and the sphere prior (`custom_model_config["ppo_priors"]: True`, `pvae_set_option
+"ppo_priors"`; without the key both priors are refused by name, as before they were built).  The rules hold for
+`compute_actions`, `ppo_prepare` and `ppo_learn` alike:
+
+    normal_state_mean_one_std   z = mu + eps exp(logvar / 2), the zero-mean prior's sampler and draws: the learned prior mean
+                                does not enter the policy's output (rmt:801-809 records it) and the PPO loss has no KL-to-prior
+                                term.  `latent_eps` holds the draws used; the prior stack is never run, and its parameters, its
+                                gradient segment and its Adam moments are left alone
+    hypersphere_uniform         z = e / max(|e|, 1e-12), e the encoder's Z outputs.  NOTHING is drawn: the prior sample of
+                                rmt:810-814 reaches neither the action nor the loss.  `eps` / `latent_prior_noise` are accepted
+                                and not read, `latent_eps` comes back all zeros (as under latent_prior_type False), and
+                                `_rng_calls` moves as under every prior: one per step, one per chunk.  Backward, per row, with
+                                g the gradient that arrives at z:
+                                    ie = 1 / max(sqrt(sum_c e_c^2), 1e-12);  zg = (sum_c e_c g_c) ie;  de_c = (g_c - e_c ie zg) ie
+                                -- the arithmetic and summation order of `pvae_reparam_backward` (the autograd path), so that
+                                the fused step and `forward()` + `backward()` cannot drift apart
+
+  * the decoder's helper and `lookahead > 1` remain refused with or without the key.
+
 The minibatch order (`ppo_learn(..., perm="philox")`, `pvae_ppo_order`): every pass's row order drawn on the device from the
 module's Philox stream, so that a learner call is a function of the module's own (seed, call counter) like the action noise
 and the latent draws.  The rule is this project's own (RLlib 1.11's `minibatches` shuffle could not be checked, no ray

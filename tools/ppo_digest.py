@@ -25,6 +25,11 @@ launches.
 `--grad-clip X` adds the learner scenarios (the sgd loops, the single steps and gradient + apply of both models) once more
 with global-norm gradient clipping bound at max_norm X (`ppo_grad_clip`), under names that start with "clip": every other
 digest is the one printed without the flag.  A library without `pvae_fc_ppo_grad_clip` cannot run it.
+
+`--priors` adds PhysicsVAE's scenarios (the sgd loop, the single steps, gradient + apply, evaluate, prepare and the action
+sampling) once more under the learned prior ("normal_state_mean_one_std") and the sphere prior ("hypersphere_uniform") on
+engines that opted in (`set_ppo_priors`), under names that start with "prior_": every other digest is the one printed
+without the flag.  A library without the option "ppo_priors" cannot run it.
 """
 import argparse
 import hashlib
@@ -46,6 +51,8 @@ CFG = P.PPOConfig(clip_param=0.2, kl_coeff=0.3, entropy_coeff=0.01, vf_clip_para
 DIAG = False                                                     # set by main() from `--diag`
 ORDER = "none"                                                   # set by main() from `--order`
 CLIP = None                                                      # set by main() for the scenarios `--grad-clip` adds
+OLD_PRIORS, NEW_PRIORS = ("normal_zero_mean_one_std", False), ("normal_state_mean_one_std", "hypersphere_uniform")
+PRIORS = OLD_PRIORS                                              # set by main() for the scenarios `--priors` adds
 
 
 def bind_diag(eng):
@@ -245,6 +252,8 @@ def fc_prepare(out):
 def vae_engine(prior, kind, max_batch, rng):
     arch = E.Arch(6, K, 4, te=(32, 2), md=(32, 2), wm=(16, 1), prior=prior)
     eng = E.HipEngine(arch, max_batch, device=DEV)
+    if prior in NEW_PRIORS:
+        eng.set_ppo_priors(True)
     fill(pairs(eng.named_views()), rng)
     ve = E.StackSetEngine(12, [(E.Stack.of((16, 2)), 1)], max_batch, device=DEV)
     fill(ve.views(0), rng)
@@ -255,7 +264,7 @@ def vae_engine(prior, kind, max_batch, rng):
 
 
 def vae_sgd(out):
-    for prior in ("normal_zero_mean_one_std", False):
+    for prior in PRIORS:
         for kind in (0, 1):
             for with_eps in (False, True):
                 for mask in (7, 3, 4):
@@ -272,7 +281,7 @@ def vae_sgd(out):
 
 
 def vae_prepare(out):
-    for prior in ("normal_zero_mean_one_std", False):
+    for prior in PRIORS:
         rng = np.random.default_rng(600)
         eng, _, _ = vae_engine(prior, 0, 32, rng)
         ro, sampler = rollout(rng, 12)
@@ -284,7 +293,7 @@ def vae_prepare(out):
 
 
 def vae_steps(out):
-    for prior in ("normal_zero_mean_one_std", False):
+    for prior in PRIORS:
         for kind in (0, 1):
             for with_eps in (False, True):
                 rng = np.random.default_rng(900 + kind)
@@ -297,18 +306,19 @@ def vae_steps(out):
 
 
 def vae_act(out):
-    for prior in ("normal_zero_mean_one_std", False):
+    for prior in PRIORS:
         rng = np.random.default_rng(1000)
         eng, _, _ = vae_engine(prior, 0, 32, rng)
         act(out, ("vae", "prior_%s" % prior), eng, CFG.gae_params(0), rng, 12, latent=4)
 
 
 def main():
-    global DIAG, ORDER, CLIP
+    global DIAG, ORDER, CLIP, PRIORS
     ap = argparse.ArgumentParser()
     ap.add_argument("--diag", action="store_true")
     ap.add_argument("--order", choices=("philox", "none"), default="none")
     ap.add_argument("--grad-clip", type=float, default=None)
+    ap.add_argument("--priors", action="store_true")
     a = ap.parse_args()
     DIAG, ORDER = a.diag, a.order
     assert torch.cuda.is_available(), "the digests are of what the GPU computes: there is nothing to report without one"
@@ -321,6 +331,11 @@ def main():
         for scenario in (fc_sgd, fc_steps, vae_sgd, vae_steps):
             scenario(clipped)
         out.update({"clip%g %s" % (CLIP, name): d for name, d in clipped.items()})
+    if a.priors:
+        CLIP, PRIORS, opted = None, NEW_PRIORS, {}
+        for scenario in (vae_sgd, vae_steps, vae_act, vae_prepare):
+            scenario(opted)
+        out.update({"prior_" + name: d for name, d in opted.items()})
     print(json.dumps(out, sort_keys=True))
 
 

@@ -20,6 +20,9 @@ replaces, and the whole `ppo_learn` call (sgd_minibatch_size `--rows`, 20 passes
 the optimizer step, and a fifth way is timed in the same rounds, alternating with (d): e  ppo_sgd_clip, (d) with the clip
 bound (`ppo_grad_clip`: one launch more per step); (c) and (d) stay unbound.  Reported beside it: e.median - d.median.
 `--one-step`: run a single fused step and exit (for a kernel trace of one step).
+`--prior {zero_mean,state_mean,sphere}`: the model's latent_prior_type (default zero_mean, whose output is the one printed
+without the flag); the other two run the fused ways on a module that opted in ("ppo_priors") and ways a and b under that
+prior -- the path the fused step replaces for such a model.
 """
 import argparse
 import json
@@ -41,13 +44,16 @@ from physicsvae_amd.model import PhysicsVAE, fc_spec             # noqa: E402
 from physicsvae_amd.spaces import Box                            # noqa: E402
 
 DB, DA, Z = 197, 45, 32
+PRIORS = {"zero_mean": "normal_zero_mean_one_std", "state_mean": "normal_state_mean_one_std", "sphere": "hypersphere_uniform"}
 
 
-def make_model(max_batch):
+def make_model(max_batch, prior="zero_mean"):
     cmc = dict(observation_space=Box(np.zeros(2 * DB), np.zeros(2 * DB)), observation_space_body=Box(np.zeros(DB), np.zeros(DB)),
                observation_space_task=Box(np.zeros(DB), np.zeros(DB)), action_space=Box(np.zeros(DA), np.zeros(DA)),
                task_encoder_layers=fc_spec(256, 2), motor_decoder_layers=fc_spec(512, 3), value_fn_layers=fc_spec(256, 2),
                task_encoder_output_dim=Z, device="cuda", max_batch=max_batch, sample_std=0.3)
+    if prior != "zero_mean":
+        cmc.update(latent_prior_type=PRIORS[prior], ppo_priors=True)
     return PhysicsVAE(cmc["observation_space"], cmc["action_space"], 2 * DA, {"custom_model_config": cmc}, "physics_vae")
 
 
@@ -89,6 +95,7 @@ def main():
                     help="ways c and d with a learner-diagnostics buffer bound (ppo.DIAG): one small launch more per step")
     ap.add_argument("--grad-clip", type=float, default=None,
                     help="max_norm: ways a and b with clip_grad_norm_, and way e = way d with the clip bound")
+    ap.add_argument("--prior", choices=tuple(PRIORS), default="zero_mean", help="the model's latent_prior_type")
     order_bench.add_arguments(ap)
     a = ap.parse_args()
     if a.order:
@@ -98,8 +105,10 @@ def main():
     torch.manual_seed(0)
     g = torch.Generator(device="cuda").manual_seed(0)
     mb = max(a.rows, 32)
-    m = make_model(mb)                  # ways a, b: torch.optim.Adam
-    f = make_model(mb)                  # ways c, d: the fused step (its own weights and Adam state)
+    if a.prior != "zero_mean":
+        out["prior"] = PRIORS[a.prior]
+    m = make_model(mb, a.prior)         # ways a, b: torch.optim.Adam
+    f = make_model(mb, a.prior)         # ways c, d: the fused step (its own weights and Adam state)
     f.load_state_dict(m.state_dict())
     m._world_model.requires_grad_(False)         # (the learner's loss never reaches the world model)
     mini = make_batch(m, a.rows, g, mb)
