@@ -573,6 +573,82 @@ int pvae_net_forward(pvae_ctx* ctx, int net, const float* in, int32_t rows, floa
 int pvae_reparam(pvae_ctx* ctx, const float* mu_logvar, int32_t rows, const float* eps, int noise,
                  uint64_t rng_seed, uint64_t rng_offset, float* z_out, void* stream);
 
+/* ---- imagined rollouts: H closed-loop steps of the policy and the world model in ONE call ------------------------------
+ * Replaces the Python loop a user of the reference writes to unroll a trained model without the simulator: per step
+ * forward_encoder + reparameterize + forward_decoder (+ the helper, rmt:833-835) + forward_world (rmt:773-844, 734-740;
+ * the "pass_through" rollout of envs/rllib_env_imitation.py:234-258 when the code comes from the prior), with the world
+ * model's prediction fed back as the next body state (what tpv:417-421 does inside the lookahead loss) -- torch.cat,
+ * three or four module calls and their pad / copy launches per step.  The rule is stated in torch in
+ * physicsvae_amd/imagine.py (imagine_torch), which is the specification.
+ *
+ * Step t = 0 .. horizon - 1 on `rows` start states s_0:
+ *   PVAE_IMAGINE_REPLAY   a_t = actions(t);                                   s_{t+1} = WM([s_t | a_t])
+ *   PVAE_IMAGINE_TRACK    h = TE([s_t | goals(t)]); z_t = sampler(h) as pvae_infer forms it (eps(t) supplied, or Philox at
+ *                         (rng_seed, rng_offset + t), row r drawing row r; noise 0: z = mu); a_t = MD([s_t | z_t])
+ *                         (+ mh_range * helper);                               s_{t+1} = WM([s_t | a_t])
+ *   PVAE_IMAGINE_PRIOR    z_t = z(t) when supplied; else PVAE_PRIOR_ZERO_MEAN: z_t = n_t, PVAE_PRIOR_STATE_MEAN: z_t =
+ *                         prior(s_t) + n_t (one float add), n_t = the draw the sampler would use as eps at (rng_seed,
+ *                         rng_offset + t); the other prior kinds need z.  Then the decoder, the helper and the world model.
+ * Input subsets hold (a stack that does not read the body columns never sees s_t); the actions are the decoder's means; the
+ * value branch does not run.
+ *
+ * A source (s0, goals, actions, z, targets) is a descriptor: element (t, r, c) = base[idx(r) * ld + t * step + c], idx(r) =
+ * row_index ? row_index[r] : r.  Dense [H][rows][D]: {p, D, rows * D, NULL}.  The demonstration set in place, window starts
+ * in a device index array: {states + Db, Db, Db, window_row}.  s0 is read at t = 0.  Rows need 4-byte alignment only; the
+ * index array's contents are the caller's contract (as seg_start is).  base NULL: absent.
+ * Results (each may be NULL), dense: states_out [H][rows][Db] = s_1 .. s_H, actions_out [H][rows][Da], z_out [H][rows][Z]
+ * (not written in replay mode), err [H]: with targets, err[t] = float(sum_{r,c} double(d) * double(d) / (rows * Db)), d =
+ * s_{t+1} - targets(t) in float; partial sums in double in `scratch` (pvae_imagine_scratch_bytes), one per workgroup, folded
+ * in a fixed order -- no atomics, the same bits on every call.
+ *
+ * Launches per step: the forward launches of the stacks the mode runs (as pvae_infer's staged path issues them), the
+ * sampler, the helper's layers and its add, and ONE hand-over launch, which writes s_{t+1} to states_out and into the body
+ * columns of the next step's input panels, copies a_t out, fetches the next step's goal / action / z columns and adds the
+ * step's squared-error partials.  Per call: one launch that stages step 0 (pad rows and columns zeroed) and, with err, one
+ * that folds the partials.  No per-step stage, pad or copy launch, no host synchronisation, no allocation.
+ * pvae_imagine_launches states the counts of a call with err (per_call = 2) and, in prior mode under
+ * PVAE_PRIOR_STATE_MEAN, with z drawn (the prior stack's layers + the launch that adds n_t; a call with z supplied issues
+ * neither).  pvae_imagine returns the number of launches it enqueued.
+ * The workspace is row block 0 of the context's panels: horizon is free of pvae_config.lookahead.  Like pvae_net_forward the
+ * call overwrites the staging panels (the trainer gathers again).
+ * Refused with -1 and a message, nothing launched: null args / s0, rows outside [1, max_batch], horizon < 1, a mode's drive
+ * missing (replay: actions; track: goals; prior without z under PVAE_PRIOR_HYPERSPHERE / PVAE_PRIOR_NONE), err without
+ * targets or without scratch of pvae_imagine_scratch_bytes(ctx, horizon) bytes.
+ *   pvae_imagine_sizeof          sizeof(pvae_imagine_args) / sizeof(pvae_imagine_src): which = 0 / 1
+ *   pvae_imagine_scratch_bytes   a multiple of 16; 0 on error */
+#define PVAE_IMAGINE_REPLAY 0
+#define PVAE_IMAGINE_TRACK 1
+#define PVAE_IMAGINE_PRIOR 2
+typedef struct pvae_imagine_src {      /* element (t, r, c) = base[idx(r) * ld + t * step + c] */
+    const float* base;                 /* idx(r) = row_index ? row_index[r] : r */
+    int64_t ld;
+    int64_t step;
+    const int32_t* row_index;
+} pvae_imagine_src;
+typedef struct pvae_imagine_args {
+    int32_t mode;                      /* PVAE_IMAGINE_* */
+    int32_t rows;                      /* 1 .. max_batch */
+    int32_t horizon;                   /* >= 1 */
+    int32_t noise;                     /* track: 0 -> z = mu */
+    pvae_imagine_src s0;               /* [rows][Db] */
+    pvae_imagine_src goals;            /* track: (t, r, 0 .. Db) */
+    pvae_imagine_src actions;          /* replay: (t, r, 0 .. Da) */
+    pvae_imagine_src z;                /* prior: (t, r, 0 .. Z), or absent: drawn */
+    pvae_imagine_src targets;          /* (t, r, 0 .. Db) = what s_{t+1} is compared with, or absent */
+    const float* eps;                  /* track: dense [H][rows][Z] draws, or NULL: Philox */
+    uint64_t rng_seed, rng_offset;
+    float* states_out;
+    float* actions_out;
+    float* z_out;
+    float* err;
+    void* scratch;
+    size_t scratch_bytes;
+} pvae_imagine_args;
+int pvae_imagine(pvae_ctx* ctx, const pvae_imagine_args* args, void* stream);
+int pvae_imagine_sizeof(int which);
+size_t pvae_imagine_scratch_bytes(const pvae_ctx* ctx, int32_t horizon);
+int pvae_imagine_launches(const pvae_ctx* ctx, int mode, int32_t* per_step, int32_t* per_call);
+
 /* ---- backward of the stand-alone stages (torch autograd through the module: physicsvae_amd/autograd.py) ---------
  * What PPO's loss.backward() does to PhysicsVAE.forward / forward_encoder / forward_decoder / forward_world
  * (rmt:743-771 -> rmt:773-853) when the stacks are learnable (rmt:473, 488), on the tile kernels of the trainer.

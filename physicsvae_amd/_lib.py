@@ -131,6 +131,21 @@ class PpoActOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("actions", "env_actions", "old_dist", "old_logp", "vf_preds", "noise_out", "obs_dst")]
 
 
+class ImagineSrc(C.Structure):
+    """pvae_imagine_src: element (t, r, c) = base[idx(r) * ld + t * step + c], idx(r) = row_index ? row_index[r] : r."""
+    _fields_ = [("base", C.c_void_p), ("ld", C.c_int64), ("step", C.c_int64), ("row_index", C.c_void_p)]
+
+
+class ImagineArgs(C.Structure):
+    """pvae_imagine_args: one imagined rollout -- mode, sizes, the sources, the draws, the results, the scratch."""
+    _fields_ = [("mode", C.c_int32), ("rows", C.c_int32), ("horizon", C.c_int32), ("noise", C.c_int32),
+                ("s0", ImagineSrc), ("goals", ImagineSrc), ("actions", ImagineSrc), ("z", ImagineSrc), ("targets", ImagineSrc),
+                ("eps", C.c_void_p), ("rng_seed", C.c_uint64), ("rng_offset", C.c_uint64),
+                ("states_out", C.c_void_p), ("actions_out", C.c_void_p), ("z_out", C.c_void_p), ("err", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+IMAGINE_MODES = {"replay": 0, "track": 1, "prior": 2}                # PVAE_IMAGINE_*
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
 
 _P = C.c_void_p
@@ -204,6 +219,10 @@ _SIGS = {
     "pvae_mlp_forward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "pvae_net_forward": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P]),
     "pvae_reparam": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int, C.c_uint64, C.c_uint64, _P, _P]),
+    "pvae_imagine": (C.c_int, [_P, C.POINTER(ImagineArgs), _P]),
+    "pvae_imagine_sizeof": (C.c_int, [C.c_int]),
+    "pvae_imagine_scratch_bytes": (C.c_size_t, [_P, C.c_int32]),
+    "pvae_imagine_launches": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_net_backward": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "pvae_reparam_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, _P, _P]),
     "pvae_fc_num_layers": (C.c_int, [C.POINTER(FcConfig)]),

@@ -6,6 +6,7 @@
 //   pvae_step.hip            the training step at lookahead 1 and the step's C ABI (direct, prefetch and data-parallel steps)
 //   pvae_lookahead.hip       the training step at lookahead > 1 (the multi-step unroll)
 //   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
+//   pvae_imagine.hip         imagined rollouts: the H-step closed-loop unroll of policy and world model, its hand-over launch
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test;
 //                            the set-up of the PPO learners' gradient exchange between workers
 //   pvae_rollout_server.hip  the call-persistent rollout server

@@ -916,6 +916,37 @@ class PhysicsVAE(PpoPolicy, nn.Module):
         and `compute_actions` take the same arguments; under the sphere `eps` is accepted and not read, and nothing is drawn."""
         return self._policy_learn(batch, config, perm, eps, dp, diag_out)
 
+    def imagine(self, mode, s0, horizon, goals=None, actions=None, z=None, eps=None, targets=None, want=("states", "actions", "z")):
+        """`horizon` closed-loop steps of this model and its world model from the start states s0, without the simulator
+        (`HipEngine.imagine`, one library call per chunk of at most `max_batch` rows; the rule: `imagine.py`'s module
+        docstring).  mode "replay" / "track" / "prior"; the sources are dense tensors or in-place pairs as there.  The noise
+        switch is `latent_prior_noise`; draws come from the module's seed: chunk i, step t draws at `_rng_calls` + 1 + i *
+        horizon + t, and `_rng_calls` advances by `horizon` per chunk in every mode, drawn or not.  Returns the dict of
+        `HipEngine.imagine`; the chunks' `err` are combined weighted by their rows."""
+        eng, H = self.engine, int(horizon)
+        rows = int(s0[1].shape[0] if isinstance(s0, (tuple, list)) else s0.shape[0])
+
+        def part(x, lo, hi, dense_dim):
+            if x is None:
+                return None
+            if isinstance(x, (tuple, list)):
+                return (x[0], x[1][lo:hi].contiguous()) + tuple(x[2:])
+            return x[lo:hi] if dense_dim == 0 else x[:, lo:hi]
+
+        outs = []
+        spans = AG.chunks(rows, eng.max_batch)
+        for lo, hi in spans:
+            outs.append(eng.imagine(mode, part(s0, lo, hi, 0), H, goals=part(goals, lo, hi, 1), actions=part(actions, lo, hi, 1),
+                                    z=part(z, lo, hi, 1), eps=part(eps, lo, hi, 1), targets=part(targets, lo, hi, 1),
+                                    noise=bool(self.latent_prior_noise), seed=self._rng_seed, offset=self._rng_calls + 1, want=want))
+            self._rng_calls += H
+        if len(outs) == 1:
+            return outs[0]
+        res = {k: torch.cat([o[k] for o in outs], dim=1) for k in outs[0] if k != "err"}
+        if "err" in outs[0]:
+            res["err"] = sum(o["err"] * float(hi - lo) for o, (lo, hi) in zip(outs, spans)) / float(rows)
+        return res
+
     def set_exploration_std(self, std):
         self._motor_decoder._model[-1].set_val(float(np.log(std)))
 

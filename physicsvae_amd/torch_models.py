@@ -202,6 +202,25 @@ def dp_buckets(plan, limit=None):
     return out
 
 
+def rollout_windows(dataset, horizon, max_windows=None):
+    """Window starts (int32 rows of s_0) for an imagined rollout of `horizon` steps over a window dataset: the starts whose
+    span of `horizon` steps stays inside one episode (`with_lookahead(horizon)`), the first `max_windows` of them.  A
+    dataset of cond "rel" windows is refused by name: its goal s_{t+1} - s_t depends on the imagined state.  A dataset whose
+    lookahead L is neither 1 nor `horizon` holds only the starts that have L - 1 successors, and that list is what gets
+    widened: the result is then conservative -- a start within L - 1 rows of an episode's end is not offered although its
+    span would fit -- and carries no `meta`."""
+    import numpy as np
+    if getattr(dataset, "next_states", None) is not None:
+        raise NotImplementedError('evaluate_rollout: cond="rel" windows are out of scope (the goal would depend on the imagined state)')
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon %d < 1" % horizon)
+    if dataset.lookahead not in (1, horizon):
+        dataset = type(dataset)(dataset.states, dataset.actions, dataset.window_row, 1)     # (its starts are window starts too)
+    starts = np.asarray(dataset.with_lookahead(horizon).window_row, dtype=np.int32)
+    return starts if max_windows is None else starts[: int(max_windows)]
+
+
 class TrainModel(tune.Trainable):
     """Epoch-per-step supervised trainer (tm:109-216)."""
 
@@ -284,6 +303,37 @@ class TrainModel(tune.Trainable):
         if self.lr_scheduler:
             self.lr_scheduler.step()              # once per EPOCH (tm:158-159)
         return {"mean_train_loss": mean_train, "mean_test_loss": mean_test}
+
+    # -- evaluation without the simulator ------------------------------------------------------
+    ROLLOUT_RNG_OFFSET = 1 << 48                  # evaluate_rollout's draws: offsets no training step reaches
+
+    def evaluate_rollout(self, horizon, mode="track", data="train", max_windows=None):
+        """How far the model runs on its own before it leaves the demonstration: imagined rollouts of `horizon` steps
+        (`HipEngine.imagine`; the rule: `imagine.py`) from the window starts of the train or the test set whose span stays
+        inside an episode, against the demonstrated states.  s_0, the goals s_{t+1} ("track"), the actions ("replay") and the
+        targets are read where the set lies on the device, through the window -> row table.  Returns {"horizon_mse": [H
+        floats]}, the mean squared error of s_{t+1} per step over all windows; one host synchronisation, at the end.  The
+        noise switch is the model's `latent_prior_noise`; chunk i, step t draws at ROLLOUT_RNG_OFFSET + i * horizon + t of
+        the trainer's seed.  Not part of `step()`."""
+        loader = {"train": self.train_loader, "test": self.test_loader}[data]
+        if not loader:
+            raise ValueError("no %s set" % data)
+        eng, H = self.engine, int(horizon)
+        starts = rollout_windows(loader.dataset, H, max_windows)
+        if len(starts) == 0:
+            raise ValueError("no window of %d steps inside an episode" % H)
+        arrays = loader.dataset.device_arrays(eng.device)
+        states, actions = arrays[0], arrays[1]
+        index = torch.from_numpy(starts).to(eng.device)
+        total = torch.zeros(H, dtype=torch.float64, device=eng.device)
+        for i, lo in enumerate(range(0, len(starts), eng.max_batch)):
+            idx = index[lo: lo + eng.max_batch]
+            out = eng.imagine(mode, (states, idx), H, goals=(states, idx, 1) if mode == "track" else None,
+                              actions=(actions, idx) if mode == "replay" else None, targets=(states, idx, 1),
+                              noise=bool(self.model.latent_prior_noise), seed=self.rng_seed,
+                              offset=self.ROLLOUT_RNG_OFFSET + i * H, want=())
+            total += out["err"].double() * float(idx.numel())
+        return {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
 
     # -- the hot loop ---------------------------------------------------------------------
     def phase(self):
