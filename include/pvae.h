@@ -649,6 +649,74 @@ int pvae_imagine_sizeof(int which);
 size_t pvae_imagine_scratch_bytes(const pvae_ctx* ctx, int32_t horizon);
 int pvae_imagine_launches(const pvae_ctx* ctx, int mode, int32_t* per_step, int32_t* per_call);
 
+/* ---- planning in the latent space: sampled candidates over imagined rollouts ------------------------------------------
+ * Random shooting / MPPI over the decoder's codes, in one call: `candidates` (K) code sequences per environment, each
+ * unrolled `horizon` steps through the decoder (+ helper) and the world model, scored against a target sequence, and the
+ * nominal moved to the best (lam == 0) or to the cost-weighted mean (lam > 0); `iters` times.  The rule is this
+ * project's own (the reference has no planner) and is stated in torch in physicsvae_amd/plan.py (plan_torch), which is the
+ * specification.
+ *
+ * rows = envs * candidates, row r = e * K + k.  s0 (e, 0 .. Db) and targets (t, e, 0 .. Db) are pvae_imagine_src
+ * descriptors OVER ENVIRONMENTS (row r reads environment r / K), so the demonstration set can be read in place.  Iteration
+ * i = 0 .. iters - 1, nominal u [H][E][Z] (NULL: zeros):
+ *   candidates  v(t, r) = u(t, e) + sigma * n_i(t, r); candidate k = 0 is the nominal itself (noise 0, not drawn).  n from
+ *               `noise` [iters][H][rows][Z], or Philox at (rng_seed, rng_offset + i * H + t), Philox row row0 + r, the
+ *               sampler's groups below Z / 4.  z = v; under PVAE_PRIOR_HYPERSPHERE z = v / max(|v|, 1e-12).  The learned
+ *               prior's mean does not enter: candidates are centred on the nominal.
+ *   unroll      pvae_imagine's prior mode with z supplied on `rows` rows: the same launches.
+ *   cost        J(r) = sum_t sw[t] * sum_c cw[c] * double(d)^2 / Db, d = s_{t+1}(r, c) - targets(t, e, c) in float, squares
+ *               and sums in double in a fixed order, added by the hand-over launches (no atomics); rounded once to float.
+ *   selection   best(e) = argmin_k cost(e, k), ties to the lowest k.  lam == 0: u'(t, e) = z(t, e * K + best).  lam > 0:
+ *               w_k = exp(-(cost_k - cost_best) / lam) in double, u' = float(sum_k w_k z_k / sum_k w_k), k ascending, and
+ *               projected onto the sphere again under PVAE_PRIOR_HYPERSPHERE.  iter_cost[i][e] = cost(e, best).
+ * After the last iteration the plan's first step runs once more on `envs` rows with z = u(0) -- pvae_imagine, prior mode,
+ * horizon 1 -- for a0 [E][Da] (the decoder's mean, + the helper) and s1 [E][Db].
+ * Results (each may be NULL), dense: plan_z [H][E][Z], best [E], cost [E][K], iter_cost [iters][E], a0, s1 and, of the last
+ * iteration, z_cand / noise_out [H][rows][Z] and states [H][rows][Db].
+ *
+ * Launches: iters * (horizon * per_step + per_iter) + closing, as pvae_plan_launches states them (per_step: the unroll's;
+ * per_iter = 3: candidates, stage, selection; closing: the one-step pass).  pvae_plan returns the number it enqueued.  No host
+ * synchronisation, no allocation; `scratch` (pvae_plan_scratch_bytes(ctx, horizon, rows), 16-byte aligned) is the
+ * caller's: the rows' costs in double, the candidate codes, the nominal between iterations.
+ * Selection keeps the K costs and weights of an environment in LDS: candidates above PVAE_PLAN_MAX_CANDIDATES are REFUSED
+ * (not tiled).  Refused with -1 and a message, nothing launched: null args / s0 / targets, envs < 1, candidates outside
+ * [1, PVAE_PLAN_MAX_CANDIDATES], rows outside [1, max_batch], horizon < 1, iters < 1, sigma or lam negative or not finite,
+ * scratch missing, short or misaligned.
+ *   pvae_plan_sizeof          sizeof(pvae_plan_args): which = 0
+ *   pvae_plan_scratch_bytes   a multiple of 16; 0 on error */
+#define PVAE_PLAN_MAX_CANDIDATES 4096
+typedef struct pvae_plan_args {
+    int32_t envs;                      /* E >= 1 */
+    int32_t candidates;                /* K >= 1; envs * candidates <= max_batch */
+    int32_t horizon;                   /* >= 1 */
+    int32_t iters;                     /* >= 1 */
+    float sigma;                       /* >= 0 */
+    float lam;                         /* 0: take the best; > 0: MPPI temperature */
+    pvae_imagine_src s0;               /* (e, 0 .. Db) */
+    pvae_imagine_src targets;          /* (t, e, 0 .. Db) */
+    const float* nominal;              /* [H][E][Z], or NULL: zeros */
+    const float* noise;                /* [iters][H][rows][Z], or NULL: Philox */
+    const float* col_weight;           /* cw [Db] >= 0, or NULL: ones */
+    const float* step_weight;          /* sw [H] >= 0, or NULL: ones */
+    uint64_t rng_seed, rng_offset;
+    int64_t row0;                      /* Philox row of row 0 (chunked callers number their rows globally) */
+    float* plan_z;
+    int32_t* best;
+    float* cost;
+    float* iter_cost;
+    float* a0;
+    float* s1;
+    float* z_cand;
+    float* noise_out;
+    float* states;
+    void* scratch;
+    size_t scratch_bytes;
+} pvae_plan_args;
+int pvae_plan(pvae_ctx* ctx, const pvae_plan_args* args, void* stream);
+int pvae_plan_sizeof(int which);
+size_t pvae_plan_scratch_bytes(const pvae_ctx* ctx, int32_t horizon, int32_t rows);
+int pvae_plan_launches(const pvae_ctx* ctx, int32_t* per_step, int32_t* per_iter, int32_t* closing);
+
 /* ---- backward of the stand-alone stages (torch autograd through the module: physicsvae_amd/autograd.py) ---------
  * What PPO's loss.backward() does to PhysicsVAE.forward / forward_encoder / forward_decoder / forward_world
  * (rmt:743-771 -> rmt:773-853) when the stacks are learnable (rmt:473, 488), on the tile kernels of the trainer.

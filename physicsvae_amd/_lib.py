@@ -145,6 +145,17 @@ class ImagineArgs(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+class PlanArgs(C.Structure):
+    """pvae_plan_args: one planning call -- sizes, sigma / lam, the sources over environments, the draws, the results, the scratch."""
+    _fields_ = [("envs", C.c_int32), ("candidates", C.c_int32), ("horizon", C.c_int32), ("iters", C.c_int32),
+                ("sigma", C.c_float), ("lam", C.c_float), ("s0", ImagineSrc), ("targets", ImagineSrc),
+                ("nominal", C.c_void_p), ("noise", C.c_void_p), ("col_weight", C.c_void_p), ("step_weight", C.c_void_p),
+                ("rng_seed", C.c_uint64), ("rng_offset", C.c_uint64), ("row0", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("plan_z", "best", "cost", "iter_cost", "a0", "s1", "z_cand", "noise_out", "states")] + [
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+PLAN_MAX_CANDIDATES = 4096                                           # PVAE_PLAN_MAX_CANDIDATES
 IMAGINE_MODES = {"replay": 0, "track": 1, "prior": 2}                # PVAE_IMAGINE_*
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
 
@@ -223,6 +234,10 @@ _SIGS = {
     "pvae_imagine_sizeof": (C.c_int, [C.c_int]),
     "pvae_imagine_scratch_bytes": (C.c_size_t, [_P, C.c_int32]),
     "pvae_imagine_launches": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pvae_plan": (C.c_int, [_P, C.POINTER(PlanArgs), _P]),
+    "pvae_plan_sizeof": (C.c_int, [C.c_int]),
+    "pvae_plan_scratch_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "pvae_plan_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_net_backward": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "pvae_reparam_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, _P, _P]),
     "pvae_fc_num_layers": (C.c_int, [C.POINTER(FcConfig)]),

@@ -6,26 +6,6 @@
 
 #include <cstdint>
 
-// What the two kernels below know of the call: the input panels of row block 0 (null: the mode does not run that stack),
-// the sources, and how the next step's z columns come about.
-enum { kZNone = 0, kZSupplied = 1, kZDrawn = 2, kZLater = 3 };   // kZLater: prior(s_t) + n_t, formed by prior_z_kernel
-struct ImagineIo {
-    float* te_in; int ld_te;
-    float* md_in; int ld_md;
-    float* md_z;                        // the panel whose columns [Db, Db + Z) take z (z_panel(): md_in, or the side panel)
-    float* wm_in; int ld_wm;
-    float* pr_in; int ld_pr;
-    int te_body, te_task, md_body;      // input subsets: 0 = the stack does not read that block, which stays zero
-    int Db, Da, Z, rows, rows_pad, mode, zkind;
-    pvae_imagine_src s0, goals, actions, z, targets;
-    unsigned long long seed, offset;
-};
-
-__device__ inline const float* src_row(const pvae_imagine_src& s, int r, long long t) {
-    const long long i = s.row_index ? (long long)s.row_index[r] : (long long)r;
-    return s.base + i * s.ld + t * s.step;
-}
-
 // z of step t, row r, column j as the hand-over (or the staging launch) puts it into the decoder's input: a supplied code,
 // or the sampler's eps draw (latent groups below Z / 4 of Philox row r at offset + t)
 __device__ inline float drive_z(const ImagineIo& io, const float* zrow, int r, long long t, int j) {
@@ -168,7 +148,7 @@ imagine_fold_kernel(const double* __restrict__ part, int nwg, double inv_n, floa
 
 static bool imagine_draws_prior(const pvae_ctx* c) { return c->L.cfg.prior_kind == PVAE_PRIOR_STATE_MEAN; }
 
-static int imagine_counts(const pvae_ctx* c, int mode, bool z_supplied, int* per_step) {
+int imagine_per_step(const pvae_ctx* c, int mode, bool z_supplied) {
     const auto layers = [&](int n) { return (int)c->L.net[n].layers.size(); };
     int n = layers(PVAE_NET_WM) + 1;                                   // the world model + the hand-over
     if (mode != PVAE_IMAGINE_REPLAY) {
@@ -177,7 +157,83 @@ static int imagine_counts(const pvae_ctx* c, int mode, bool z_supplied, int* per
     }
     if (mode == PVAE_IMAGINE_TRACK) n += layers(PVAE_NET_TE) + 1;      // the encoder + the sampler
     if (mode == PVAE_IMAGINE_PRIOR && !z_supplied && imagine_draws_prior(c)) n += layers(PVAE_NET_PR) + 1;
-    *per_step = n;
+    return n;
+}
+
+ImagineIo imagine_io(pvae_ctx* c, int mode, int zkind, int rows) {
+    float* w = c->ws;
+    const bool track = mode == PVAE_IMAGINE_TRACK, prior = mode == PVAE_IMAGINE_PRIOR;
+    ImagineIo io;
+    memset(&io, 0, sizeof(io));
+    if (track) { io.te_in = w + c->W.net[PVAE_NET_TE].in; io.ld_te = c->L.net[PVAE_NET_TE].layers[0].ld; }
+    if (track || prior) {
+        io.md_in = w + c->W.net[PVAE_NET_MD].in; io.ld_md = c->L.net[PVAE_NET_MD].layers[0].ld;
+        io.md_z = w + z_panel(c);
+    }
+    io.wm_in = w + c->W.net[PVAE_NET_WM].in; io.ld_wm = c->L.net[PVAE_NET_WM].layers[0].ld;
+    if (zkind == kZLater) { io.pr_in = w + c->W.net[PVAE_NET_PR].in; io.ld_pr = c->L.net[PVAE_NET_PR].layers[0].ld; }
+    io.te_body = c->L.cfg.te_inputs != PVAE_INPUT_TASK; io.te_task = c->L.cfg.te_inputs != PVAE_INPUT_BODY;
+    io.md_body = c->L.cfg.md_inputs != PVAE_INPUT_TASK;
+    io.Db = c->L.cfg.dim_body; io.Da = c->L.cfg.dim_action; io.Z = c->L.cfg.latent;
+    io.rows = rows; io.rows_pad = pad32(rows); io.mode = mode; io.zkind = zkind;
+    // the training panels are no longer a coherent batch (as pvae_net_forward leaves them); forward_net picks its kernels
+    // by staged_rows_f
+    c->staged_rows = 0;
+    c->staged_rows_f = rows;
+    c->dx.on = false;
+    return io;
+}
+
+int imagine_unroll(pvae_ctx* c, const ImagineIo& io, int H, const float* eps, int noise, float* z_out,
+                   const std::function<int(int t, bool more)>& handover, hipStream_t st, int* launches) {
+    int rc;
+    float* w = c->ws;
+    const int Db = io.Db, Da = io.Da, Z = io.Z, rows = io.rows, rows_pad = io.rows_pad;
+    const NetLayout& TE = c->L.net[PVAE_NET_TE];
+    const NetLayout& MD = c->L.net[PVAE_NET_MD];
+    const NetLayout& WM = c->L.net[PVAE_NET_WM];
+    const NetLayout& PR = c->L.net[PVAE_NET_PR];
+    const bool helper = !c->L.net[PVAE_NET_MH].layers.empty();
+    const bool track = io.mode == PVAE_IMAGINE_TRACK, prior = io.mode == PVAE_IMAGINE_PRIOR;
+    const bool prior_later = io.zkind == kZLater;
+    const int ldo_te = TE.layers.back().n_out_pad;
+    for (int t = 0; t < H; ++t) {
+        if (track) {
+            if ((rc = forward_net(c, PVAE_NET_TE, rows_pad, st))) return rc;
+            *launches += (int)TE.layers.size();
+            // (the learned prior mean plays no part in the action: rmt:801-809 only records it)
+            if ((rc = launch_sampler(c, w + c->W.net[PVAE_NET_TE].act.back(), ldo_te,
+                                     eps ? eps + (size_t)t * rows * Z : (const float*)nullptr, w + c->W.eps, io.md_in,
+                                     io.ld_md, rows, rows_pad, noise ? 1 : 0, io.seed, io.offset + t, (float*)nullptr,
+                                     z_out ? z_out + (size_t)t * rows * Z : (float*)nullptr, (const float*)nullptr, 0, st)))
+                return rc;
+            ++*launches;
+        }
+        if (prior_later) {
+            if ((rc = forward_net(c, PVAE_NET_PR, rows_pad, st))) return rc;
+            *launches += (int)PR.layers.size();
+            hipLaunchKernelGGL(imagine_prior_z_kernel, dim3(grid1d((long long)rows * Z, 64)), dim3(256), 0, st,
+                               w + c->W.net[PVAE_NET_PR].act.back(), PR.layers.back().n_out_pad, io.md_z, io.ld_md, Db, Z, rows,
+                               io.seed, io.offset + t, z_out ? z_out + (size_t)t * rows * Z : (float*)nullptr);
+            HIP_TRY(hipGetLastError());
+            ++*launches;
+        }
+        if (track || prior) {
+            FwdTail md_tail;                   // a_hat -> the action columns of the world model's input panel
+            md_tail.out2 = io.wm_in; md_tail.ld2 = io.ld_wm; md_tail.off2 = Db; md_tail.n2 = Da;
+            if ((rc = forward_net(c, PVAE_NET_MD, rows_pad, st, md_tail))) return rc;
+            *launches += (int)MD.layers.size();
+            if (helper) {                      // rmt:833-835
+                if ((rc = forward_net(c, PVAE_NET_MH, rows_pad, st))) return rc;
+                if ((rc = helper_add_launch(c, rows, 0, 0, st))) return rc;
+                *launches += (int)c->L.net[PVAE_NET_MH].layers.size() + 1;
+            }
+        }
+        if ((rc = forward_net(c, PVAE_NET_WM, rows_pad, st))) return rc;
+        *launches += (int)WM.layers.size();
+        if ((rc = handover(t, t + 1 < H))) return rc;
+        ++*launches;
+    }
     return 0;
 }
 
@@ -196,9 +252,7 @@ size_t pvae_imagine_scratch_bytes(const pvae_ctx* c, int32_t horizon) {
 int pvae_imagine_launches(const pvae_ctx* c, int mode, int32_t* per_step, int32_t* per_call) {
     if (!c) return fail(-1, "null ctx");
     if (mode < PVAE_IMAGINE_REPLAY || mode > PVAE_IMAGINE_PRIOR) return fail(-1, "unknown mode %d", mode);
-    int n = 0;
-    imagine_counts(c, mode, false, &n);
-    if (per_step) *per_step = n;
+    if (per_step) *per_step = imagine_per_step(c, mode, false);
     if (per_call) *per_call = 2;
     return 0;
 }
@@ -226,85 +280,25 @@ int pvae_imagine(pvae_ctx* c, const pvae_imagine_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
 
     const int Db = c->L.cfg.dim_body, Da = c->L.cfg.dim_action, Z = c->L.cfg.latent;
-    const int rows_pad = pad32(rows);
     float* w = c->ws;
-    const NetLayout& TE = c->L.net[PVAE_NET_TE];
-    const NetLayout& MD = c->L.net[PVAE_NET_MD];
-    const NetLayout& WM = c->L.net[PVAE_NET_WM];
-    const NetLayout& PR = c->L.net[PVAE_NET_PR];
-    const bool helper = !c->L.net[PVAE_NET_MH].layers.empty();
-    const bool track = mode == PVAE_IMAGINE_TRACK, prior = mode == PVAE_IMAGINE_PRIOR;
+    const bool prior = mode == PVAE_IMAGINE_PRIOR;
     const bool prior_later = prior && !z_supplied && imagine_draws_prior(c);
 
-    ImagineIo io;
-    memset(&io, 0, sizeof(io));
-    if (track) { io.te_in = w + c->W.net[PVAE_NET_TE].in; io.ld_te = TE.layers[0].ld; }
-    if (track || prior) {
-        io.md_in = w + c->W.net[PVAE_NET_MD].in; io.ld_md = MD.layers[0].ld;
-        io.md_z = w + z_panel(c);
-    }
-    io.wm_in = w + c->W.net[PVAE_NET_WM].in; io.ld_wm = WM.layers[0].ld;
-    if (prior_later) { io.pr_in = w + c->W.net[PVAE_NET_PR].in; io.ld_pr = PR.layers[0].ld; }
-    io.te_body = c->L.cfg.te_inputs != PVAE_INPUT_TASK; io.te_task = c->L.cfg.te_inputs != PVAE_INPUT_BODY;
-    io.md_body = c->L.cfg.md_inputs != PVAE_INPUT_TASK;
-    io.Db = Db; io.Da = Da; io.Z = Z; io.rows = rows; io.rows_pad = rows_pad; io.mode = mode;
-    io.zkind = !prior ? kZNone : z_supplied ? kZSupplied : prior_later ? kZLater : kZDrawn;
+    ImagineIo io = imagine_io(c, mode, !prior ? kZNone : z_supplied ? kZSupplied : prior_later ? kZLater : kZDrawn, rows);
     io.s0 = a->s0; io.goals = a->goals; io.actions = a->actions; io.z = a->z; io.targets = a->targets;
     io.seed = a->rng_seed; io.offset = a->rng_offset;
 
-    // the training panels are no longer a coherent batch (as pvae_net_forward leaves them); forward_net picks its kernels
-    // by staged_rows_f
-    c->staged_rows = 0;
-    c->staged_rows_f = rows;
-    c->dx.on = false;
-
     int launches = 0;
-    hipLaunchKernelGGL(imagine_stage_kernel, dim3(rows_pad / 4), dim3(256), 0, st, io, prior ? a->z_out : (float*)nullptr);
+    hipLaunchKernelGGL(imagine_stage_kernel, dim3(io.rows_pad / 4), dim3(256), 0, st, io, prior ? a->z_out : (float*)nullptr);
     HIP_TRY(hipGetLastError());
     ++launches;
 
     const int nwg = (rows + 3) / 4;
     double* part = with_err ? (double*)a->scratch : nullptr;
-    const int ldo_te = TE.layers.back().n_out_pad, ldo_md = MD.layers.back().n_out_pad, ldo_wm = WM.layers.back().n_out_pad;
-    for (int t = 0; t < H; ++t) {
-        if (track) {
-            if ((rc = forward_net(c, PVAE_NET_TE, rows_pad, st))) return rc;
-            launches += (int)TE.layers.size();
-            // (the learned prior mean plays no part in the action: rmt:801-809 only records it)
-            if ((rc = launch_sampler(c, w + c->W.net[PVAE_NET_TE].act.back(), ldo_te,
-                                     a->eps ? a->eps + (size_t)t * rows * Z : (const float*)nullptr, w + c->W.eps, io.md_in,
-                                     io.ld_md, rows, rows_pad, a->noise ? 1 : 0, (unsigned long long)a->rng_seed,
-                                     (unsigned long long)(a->rng_offset + t), (float*)nullptr,
-                                     a->z_out ? a->z_out + (size_t)t * rows * Z : (float*)nullptr, (const float*)nullptr, 0, st)))
-                return rc;
-            ++launches;
-        }
-        if (prior_later) {
-            if ((rc = forward_net(c, PVAE_NET_PR, rows_pad, st))) return rc;
-            launches += (int)PR.layers.size();
-            hipLaunchKernelGGL(imagine_prior_z_kernel, dim3(grid1d((long long)rows * Z, 64)), dim3(256), 0, st,
-                               w + c->W.net[PVAE_NET_PR].act.back(), PR.layers.back().n_out_pad, io.md_z, io.ld_md, Db, Z, rows,
-                               (unsigned long long)a->rng_seed, (unsigned long long)(a->rng_offset + t),
-                               a->z_out ? a->z_out + (size_t)t * rows * Z : (float*)nullptr);
-            HIP_TRY(hipGetLastError());
-            ++launches;
-        }
-        if (track || prior) {
-            FwdTail md_tail;                   // a_hat -> the action columns of the world model's input panel
-            md_tail.out2 = io.wm_in; md_tail.ld2 = io.ld_wm; md_tail.off2 = Db; md_tail.n2 = Da;
-            if ((rc = forward_net(c, PVAE_NET_MD, rows_pad, st, md_tail))) return rc;
-            launches += (int)MD.layers.size();
-            if (helper) {                      // rmt:833-835
-                if ((rc = forward_net(c, PVAE_NET_MH, rows_pad, st))) return rc;
-                if ((rc = helper_add_launch(c, rows, 0, 0, st))) return rc;
-                launches += (int)c->L.net[PVAE_NET_MH].layers.size() + 1;
-            }
-        }
-        if ((rc = forward_net(c, PVAE_NET_WM, rows_pad, st))) return rc;
-        launches += (int)WM.layers.size();
-        const bool more = t + 1 < H;
-        const float* a_src = mode == PVAE_IMAGINE_REPLAY ? io.wm_in + Db : w + c->W.net[PVAE_NET_MD].act.back();
-        const int lda = mode == PVAE_IMAGINE_REPLAY ? io.ld_wm : ldo_md;
+    const int ldo_md = c->L.net[PVAE_NET_MD].layers.back().n_out_pad, ldo_wm = c->L.net[PVAE_NET_WM].layers.back().n_out_pad;
+    const float* a_src = mode == PVAE_IMAGINE_REPLAY ? io.wm_in + Db : w + c->W.net[PVAE_NET_MD].act.back();
+    const int lda = mode == PVAE_IMAGINE_REPLAY ? io.ld_wm : ldo_md;
+    const auto handover = [&](int t, bool more) {
         hipLaunchKernelGGL(imagine_handover_kernel, dim3(nwg), dim3(256), 0, st, io, w + c->W.net[PVAE_NET_WM].act.back(), ldo_wm,
                            a_src, lda, (long long)t, more ? 1 : 0,
                            a->states_out ? a->states_out + (size_t)t * rows * Db : (float*)nullptr,
@@ -312,8 +306,9 @@ int pvae_imagine(pvae_ctx* c, const pvae_imagine_args* a, void* stream) {
                            (prior && more && a->z_out) ? a->z_out + (size_t)(t + 1) * rows * Z : (float*)nullptr,
                            part ? part + (size_t)t * nwg : (double*)nullptr);
         HIP_TRY(hipGetLastError());
-        ++launches;
-    }
+        return 0;
+    };
+    if ((rc = imagine_unroll(c, io, H, a->eps, a->noise, a->z_out, handover, st, &launches))) return rc;
     if (with_err) {
         hipLaunchKernelGGL(imagine_fold_kernel, dim3(H), dim3(64), 0, st, part, nwg, 1.0 / ((double)rows * Db), a->err);
         HIP_TRY(hipGetLastError());

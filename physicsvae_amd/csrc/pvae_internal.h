@@ -7,6 +7,7 @@
 //   pvae_lookahead.hip       the training step at lookahead > 1 (the multi-step unroll)
 //   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
 //   pvae_imagine.hip         imagined rollouts: the H-step closed-loop unroll of policy and world model, its hand-over launch
+//   pvae_plan.hip            planning over imagined rollouts: sampled candidate codes, per-row cost in the hand-over, selection
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test;
 //                            the set-up of the PPO learners' gradient exchange between workers
 //   pvae_rollout_server.hip  the call-persistent rollout server
@@ -560,6 +561,36 @@ int launch_sampler(pvae_ctx* c, const float* te_out, int ldte, const float* eps,
                    float* z_dense, const float* mu_p, int ldmp, hipStream_t st);
 bool sampler_folds(const pvae_ctx* c, int rows);
 XSrc xsrc_of(const pvae_ctx* c, int net, int phase, bool with_s1, int rows);
+// ---- pvae_imagine.hip: the closed-loop unroll, shared with pvae_plan.hip ----
+// What the kernels of an unroll know of the call: the input panels of row block 0 (null: the mode does not run that stack),
+// the sources, and how the next step's z columns come about.
+enum { kZNone = 0, kZSupplied = 1, kZDrawn = 2, kZLater = 3 };   // kZLater: prior(s_t) + n_t, formed by prior_z_kernel
+struct ImagineIo {
+    float* te_in; int ld_te;
+    float* md_in; int ld_md;
+    float* md_z;                        // the panel whose columns [Db, Db + Z) take z (z_panel(): md_in, or the side panel)
+    float* wm_in; int ld_wm;
+    float* pr_in; int ld_pr;
+    int te_body, te_task, md_body;      // input subsets: 0 = the stack does not read that block, which stays zero
+    int Db, Da, Z, rows, rows_pad, mode, zkind;
+    pvae_imagine_src s0, goals, actions, z, targets;
+    unsigned long long seed, offset;
+};
+
+__device__ inline const float* src_row(const pvae_imagine_src& s, int r, long long t) {
+    const long long i = s.row_index ? (long long)s.row_index[r] : (long long)r;
+    return s.base + i * s.ld + t * s.step;
+}
+// The panels and sizes of a call on `rows` rows (sources, seed and offset are the caller's to fill in); marks the staging
+// panels as overwritten, as pvae_net_forward does.
+ImagineIo imagine_io(pvae_ctx* c, int mode, int zkind, int rows);
+int imagine_per_step(const pvae_ctx* c, int mode, bool z_supplied);      // launches of one step, the hand-over included
+// Steps t = 0 .. H - 1 on panels that hold step 0 already: per step the stacks' own launches, then `handover(t, more)`, ONE
+// launch that feeds s_{t+1} and the next drive into the panels.  `eps`, `noise`, `z_out`: track mode's draws and the dense
+// z result of track mode and of prior mode under the learned prior.  Adds what it enqueued to *launches.
+int imagine_unroll(pvae_ctx* c, const ImagineIo& io, int H, const float* eps, int noise, float* z_out,
+                   const std::function<int(int t, bool more)>& handover, hipStream_t st, int* launches);
+
 // A backward pass is a list of stages = launches in stream order.  `ready_*` names the slice of
 // the gradient arena that is final once the stage has run (data-parallel callers start that
 // slice's all-reduce right away, while later stages execute).

@@ -947,6 +947,46 @@ class PhysicsVAE(PpoPolicy, nn.Module):
             res["err"] = sum(o["err"] * float(hi - lo) for o, (lo, hi) in zip(outs, spans)) / float(rows)
         return res
 
+    def plan(self, s0, targets, horizon, candidates, iters=1, sigma=1.0, lam=0.0, nominal=None, col_weight=None, step_weight=None,
+             noise=None, seed=None, offset=None, want=("plan_z", "best", "cost", "iter_cost", "a0", "s1")):
+        """Sampling-based planning in the latent space (`HipEngine.plan`; the rule: `plan.py`'s module docstring): per
+        environment `candidates` code sequences around `nominal` [H, E, Z], unrolled `horizon` steps through the decoder and
+        the world model and scored against `targets` [H, E, Db] from the start states s0 [E, Db] (dense, or in-place pairs as
+        in `imagine`), `iters` times; returns the dict of `HipEngine.plan` -- "a0" is the first action of the plan.  One
+        library call per chunk of floor(max_batch / candidates) environments; the chunks number their rows globally
+        (`row0`), so no two of them draw the same noise.  Draws come from the module's seed: iteration i, step t draws at
+        `_rng_calls` + 1 + i * horizon + t, and `_rng_calls` advances by iters * horizon per call, drawn or not; `seed` /
+        `offset` override both and leave the counter alone."""
+        from .plan import plan_chunks
+        eng, H, K, iters = self.engine, int(horizon), int(candidates), int(iters)
+        if K > eng.max_batch:
+            raise ValueError("candidates %d above max_batch %d" % (K, eng.max_batch))
+        E = int(s0[1].shape[0] if isinstance(s0, (tuple, list)) else s0.shape[0])
+        use_seed = self._rng_seed if seed is None else int(seed)
+        if offset is None:
+            use_offset = self._rng_calls + 1
+            self._rng_calls += iters * H
+        else:
+            use_offset = int(offset)
+
+        def part(x, lo, hi, dim):
+            if x is None:
+                return None
+            if isinstance(x, (tuple, list)):
+                return (x[0], x[1][lo:hi].contiguous()) + tuple(x[2:])
+            return x[lo:hi] if dim == 0 else x[:, lo:hi]
+
+        outs = []
+        for lo, hi, row0 in plan_chunks(E, K, eng.max_batch):
+            outs.append(eng.plan(part(s0, lo, hi, 0), part(targets, lo, hi, 1), H, K, iters=iters, sigma=sigma, lam=lam,
+                                 nominal=part(nominal, lo, hi, 1), noise=None if noise is None else noise[:, :, lo * K: hi * K],
+                                 col_weight=col_weight, step_weight=step_weight, seed=use_seed, offset=use_offset, row0=row0,
+                                 want=want))
+        if len(outs) == 1:
+            return outs[0]
+        env_dim = {"best": 0, "cost": 0, "a0": 0, "s1": 0}
+        return {k: torch.cat([o[k] for o in outs], dim=env_dim.get(k, 1)) for k in outs[0]}
+
     def set_exploration_std(self, std):
         self._motor_decoder._model[-1].set_val(float(np.log(std)))
 

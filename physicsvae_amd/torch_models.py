@@ -335,6 +335,33 @@ class TrainModel(tune.Trainable):
             total += out["err"].double() * float(idx.numel())
         return {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
 
+    def evaluate_plan(self, horizon, candidates, iters=1, sigma=1.0, lam=0.0, data="train", max_windows=None):
+        """How closely a PLANNED code sequence follows the demonstration: per window start, `HipEngine.plan` against the
+        demonstrated next states (read where the set lies on the device, as `evaluate_rollout` reads them), then the plan
+        replayed open loop through one `imagine` prior-mode call with z = plan_z and the same targets.  Returns
+        {"horizon_mse": [H floats]}, the per-horizon mean squared error of the planned rollout over all windows, to be set
+        beside `evaluate_rollout`'s; one host synchronisation, at the end.  Chunk i, iteration j, step t draws at
+        ROLLOUT_RNG_OFFSET + (i * iters + j) * horizon + t of the trainer's seed, rows numbered globally.  Not part of
+        `step()`."""
+        from .plan import plan_chunks
+        loader = {"train": self.train_loader, "test": self.test_loader}[data]
+        if not loader:
+            raise ValueError("no %s set" % data)
+        eng, H, K, iters = self.engine, int(horizon), int(candidates), int(iters)
+        starts = rollout_windows(loader.dataset, H, max_windows)
+        if len(starts) == 0:
+            raise ValueError("no window of %d steps inside an episode" % H)
+        states = loader.dataset.device_arrays(eng.device)[0]
+        index = torch.from_numpy(starts).to(eng.device)
+        total = torch.zeros(H, dtype=torch.float64, device=eng.device)
+        for i, (lo, hi, row0) in enumerate(plan_chunks(len(starts), K, eng.max_batch)):
+            idx = index[lo:hi].contiguous()
+            p = eng.plan((states, idx), (states, idx, 1), H, K, iters=iters, sigma=sigma, lam=lam, seed=self.rng_seed,
+                         offset=self.ROLLOUT_RNG_OFFSET + i * iters * H, row0=row0, want=("plan_z",))
+            out = eng.imagine("prior", (states, idx), H, z=p["plan_z"], targets=(states, idx, 1), want=())
+            total += out["err"].double() * float(idx.numel())
+        return {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
+
     # -- the hot loop ---------------------------------------------------------------------
     def phase(self):
         """World phase <=> only the world model is learnable (tpv:326-329 / 347-350)."""
