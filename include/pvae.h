@@ -717,6 +717,91 @@ int pvae_plan_sizeof(int which);
 size_t pvae_plan_scratch_bytes(const pvae_ctx* ctx, int32_t horizon, int32_t rows);
 int pvae_plan_launches(const pvae_ctx* ctx, int32_t* per_step, int32_t* per_iter, int32_t* closing);
 
+/* ---- backpropagation through imagined rollouts; gradient-refined latent plans -----------------------------------------
+ * The rule is this project's own and is stated in torch in physicsvae_amd/refine.py (rollout_grad_torch, refine_torch),
+ * which is the specification.  Every stack is frozen: parameters, the gradient arena and the Adam state are not touched.
+ *
+ * pvae_imagine_grad: the planner's unroll (pvae_imagine's prior mode with z supplied: the same launches) on rows = envs *
+ * group rows, row r = e * G + g; s0 (e, 0 .. Db) and targets (t, e, 0 .. Db) are descriptors OVER ENVIRONMENTS, z is dense
+ * [H][rows][Z], the code as the decoder reads it.  cost [rows] is pvae_plan's J(r), bit for bit (the same per-row
+ * arithmetic, by the hand-over launches); dz [H][rows][Z] = dJ(r) / dz_t(r) and ds [H][rows][Db] = dJ(r) / ds_t(r)
+ * (ds[0]: at the start state) by backpropagation through time through the decoder, the helper and the world model:
+ *   cot_{t+1} = coef(t, c) * d + ds_{t+1},  coef = float(2 * sw[t] * cw[c] / Db) formed in double, d = s_{t+1} - target in
+ *   float, a product and then a sum, ds_H = 0; ds_t = the world model's body columns + (where the decoder reads the body)
+ *   the decoder's + the helper's, in this order; dz_t = +0.0 where the decoder does not read the code.
+ * The workspace holds one step's activations: the states are kept on a tape in `scratch`, and for t < H - 1 the step's
+ * forward launches run again before its backward launches.  Launches: per_call + horizon * fwd_per_step and, when dz or ds
+ * is asked for, + horizon * bwd_per_step + (horizon - 1) * (fwd_per_step - 1), as pvae_imagine_grad_launches states them
+ * (bwd_per_step = the layers of the world model, the decoder and the helper + 2: the action seed and the backward
+ * hand-over).  No atomics, a fixed summation order: the same bits on every call.  Results (each may be NULL and is then not
+ * written): cost, dz, ds, states_out [H][rows][Db] = s_1 .. s_H.  With neither dz nor ds the call is forward only.
+ * Refused with -1 and a message, nothing launched: null args / s0 / targets / z, envs < 1, group < 1, rows above
+ * max_batch, horizon < 1, scratch (pvae_imagine_grad_scratch_bytes(ctx, horizon, rows), 16-byte aligned) missing, short or
+ * misaligned.
+ *
+ * pvae_plan_refine: `steps` Adam steps on the codes of `envs` environments (group 1) from `nominal` [H][E][Z] (NULL: zeros),
+ * entirely on the stream.  The iterate is v; the code fed to the unroll is z = v, under PVAE_PRIOR_HYPERSPHERE z = v /
+ * max(|v|, 1e-12).  Iteration i = 0 .. steps - 1: forward and backward at z_i (iter_cost[i][e] = float(J)), then ONE update
+ * launch, a workgroup per environment: keep z_i if its stored float cost is smaller than the best so far (ties: the lowest
+ * i), pull dz back through the projection under the sphere, Adam on v (beta 0.9 / 0.999, eps 1e-8, bias-corrected, zero
+ * moments at the start of every call, float, every operation rounded on its own, the order of refine.py), project the new
+ * iterate.  Then one forward-only unroll for iter_cost[steps], the last keep, and the closing pass: pvae_imagine, prior mode,
+ * horizon 1, on z = plan_z[0] for a0 [E][Da] and s1 [E][Db].  Results (each may be NULL and is then not written): plan_z
+ * [H][E][Z] = z_{best_iter(e)}, cost [E] = iter_cost[best_iter], best_iter [E], iter_cost [steps + 1][E], a0, s1, z_iters
+ * [steps + 1][H][E][Z], grad [H][E][Z] = dJ / dv of the last backward (zeros with steps == 0).
+ * Launches: steps * (G(horizon) + per_iter) + F(horizon) + per_call, G / F = pvae_imagine_grad's count with / without the
+ * backward, as pvae_plan_refine_launches states per_iter (1) and per_call (init, the last keep, the closing pass).
+ * Refused with -1: null args / s0 / targets, envs < 1, rows (= envs) above max_batch, horizon < 1, steps < 0, lr not finite
+ * or <= 0, scratch (pvae_plan_refine_scratch_bytes(ctx, horizon, envs), 16-byte aligned) missing, short or misaligned.
+ *   pvae_*_sizeof          sizeof the args struct: which = 0
+ *   pvae_*_scratch_bytes   a multiple of 16; 0 on error */
+typedef struct pvae_imagine_grad_args {
+    int32_t envs;                      /* E >= 1 */
+    int32_t group;                     /* G >= 1; envs * group <= max_batch */
+    int32_t horizon;                   /* >= 1 */
+    int32_t reserved;
+    pvae_imagine_src s0;               /* (e, 0 .. Db) */
+    pvae_imagine_src targets;          /* (t, e, 0 .. Db) */
+    const float* z;                    /* [H][rows][Z] */
+    const float* col_weight;           /* cw [Db] >= 0, or NULL: ones */
+    const float* step_weight;          /* sw [H] >= 0, or NULL: ones */
+    float* cost;
+    float* dz;
+    float* ds;
+    float* states_out;
+    void* scratch;
+    size_t scratch_bytes;
+} pvae_imagine_grad_args;
+int pvae_imagine_grad(pvae_ctx* ctx, const pvae_imagine_grad_args* args, void* stream);
+int pvae_imagine_grad_sizeof(int which);
+size_t pvae_imagine_grad_scratch_bytes(const pvae_ctx* ctx, int32_t horizon, int32_t rows);
+int pvae_imagine_grad_launches(const pvae_ctx* ctx, int32_t* fwd_per_step, int32_t* bwd_per_step, int32_t* per_call);
+typedef struct pvae_plan_refine_args {
+    int32_t envs;                      /* E >= 1, <= max_batch */
+    int32_t horizon;                   /* >= 1 */
+    int32_t steps;                     /* >= 0 */
+    float lr;                          /* > 0 */
+    pvae_imagine_src s0;               /* (e, 0 .. Db) */
+    pvae_imagine_src targets;          /* (t, e, 0 .. Db) */
+    const float* nominal;              /* [H][E][Z], or NULL: zeros */
+    const float* col_weight;           /* cw [Db] >= 0, or NULL: ones */
+    const float* step_weight;          /* sw [H] >= 0, or NULL: ones */
+    float* plan_z;
+    float* cost;
+    int32_t* best_iter;
+    float* iter_cost;
+    float* a0;
+    float* s1;
+    float* z_iters;
+    float* grad;
+    void* scratch;
+    size_t scratch_bytes;
+} pvae_plan_refine_args;
+int pvae_plan_refine(pvae_ctx* ctx, const pvae_plan_refine_args* args, void* stream);
+int pvae_plan_refine_sizeof(int which);
+size_t pvae_plan_refine_scratch_bytes(const pvae_ctx* ctx, int32_t horizon, int32_t envs);
+int pvae_plan_refine_launches(const pvae_ctx* ctx, int32_t* per_iter, int32_t* per_call);
+
 /* ---- backward of the stand-alone stages (torch autograd through the module: physicsvae_amd/autograd.py) ---------
  * What PPO's loss.backward() does to PhysicsVAE.forward / forward_encoder / forward_decoder / forward_world
  * (rmt:743-771 -> rmt:773-853) when the stacks are learnable (rmt:473, 488), on the tile kernels of the trainer.

@@ -155,6 +155,23 @@ class PlanArgs(C.Structure):
         ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+class ImagineGradArgs(C.Structure):
+    """pvae_imagine_grad_args"""
+    _fields_ = [("envs", C.c_int32), ("group", C.c_int32), ("horizon", C.c_int32), ("reserved", C.c_int32),
+                ("s0", ImagineSrc), ("targets", ImagineSrc)] + [
+        (n, C.c_void_p) for n in ("z", "col_weight", "step_weight", "cost", "dz", "ds", "states_out")] + [
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+class PlanRefineArgs(C.Structure):
+    """pvae_plan_refine_args"""
+    _fields_ = [("envs", C.c_int32), ("horizon", C.c_int32), ("steps", C.c_int32), ("lr", C.c_float),
+                ("s0", ImagineSrc), ("targets", ImagineSrc)] + [
+        (n, C.c_void_p) for n in ("nominal", "col_weight", "step_weight", "plan_z", "cost", "best_iter", "iter_cost", "a0", "s1",
+                                  "z_iters", "grad")] + [
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 PLAN_MAX_CANDIDATES = 4096                                           # PVAE_PLAN_MAX_CANDIDATES
 IMAGINE_MODES = {"replay": 0, "track": 1, "prior": 2}                # PVAE_IMAGINE_*
 LOG_STD_KINDS = {"constant": 0, "state_independent": 1, "state_dependent": 2}
@@ -238,6 +255,14 @@ _SIGS = {
     "pvae_plan_sizeof": (C.c_int, [C.c_int]),
     "pvae_plan_scratch_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
     "pvae_plan_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pvae_imagine_grad": (C.c_int, [_P, C.POINTER(ImagineGradArgs), _P]),
+    "pvae_imagine_grad_sizeof": (C.c_int, [C.c_int]),
+    "pvae_imagine_grad_scratch_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "pvae_imagine_grad_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pvae_plan_refine": (C.c_int, [_P, C.POINTER(PlanRefineArgs), _P]),
+    "pvae_plan_refine_sizeof": (C.c_int, [C.c_int]),
+    "pvae_plan_refine_scratch_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "pvae_plan_refine_launches": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pvae_net_backward": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "pvae_reparam_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, _P, _P]),
     "pvae_fc_num_layers": (C.c_int, [C.POINTER(FcConfig)]),

@@ -10,6 +10,7 @@ Their forwards are the very calls the module makes without autograd, so values a
   HipReparam  the sampler: mu_logvar -> z, with the draws the forward used kept for the backward
   HipPolicy   `forward()` as ONE `pvae_infer_logits` call: (obs, *TE, *MD, *MH, *WM) -> (a_hat, z, mu_logvar, s2)
   HipStackSet a stack set (`pvae_fc_*`, FullyConnectedPolicy): (x, *params of all stacks) -> (out_0, ..., out_{S-1})
+  HipImagineCost  the cost of an imagined rollout (`pvae_imagine_grad`): (s0, z) -> cost, the stacks frozen
 
 Every backward runs in chunks of at most `max_batch` rows, the parameter gradient summed over the chunks into one flat
 buffer per stack (accumulate = 1 after the first chunk) and handed back as views shaped like the parameters.  The
@@ -297,3 +298,31 @@ class HipStackSet(torch.autograd.Function):
                     grads[k: k + n] = [v if nd else None for v, nd in zip(views[k: k + n], needs[k: k + n])]
                 k += n
         return (None, dx) + tuple(grads)
+
+
+class HipImagineCost(torch.autograd.Function):
+    """The planner's rollout cost, differentiable in the codes and the start states: `HipImagineCost.apply(module, s0, z,
+    targets, group, col_weight, step_weight)` -> cost [rows] (`PhysicsVAE.imagine_grad`, chunked by environments; the rule:
+    refine.py).  The forward runs the backward through the unroll as well and keeps dz (and, group == 1, ds[0]); the
+    backward scales them by the incoming per-row gradient.  The model's parameters get NO gradient: every stack is frozen
+    in this call.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, module, s0, z, targets, group, col_weight, step_weight):
+        want_s0 = ctx.needs_input_grad[1]
+        if want_s0 and int(group) != 1:
+            raise ValueError("s0.grad needs group == 1 (a start state is shared by the rows of its group)")
+        out = module.imagine_grad(s0.detach(), z.detach(), targets, group=group, col_weight=col_weight, step_weight=step_weight,
+                                  want=("cost", "dz") + (("ds",) if want_s0 else ()))
+        ctx.want_s0, ctx.dtypes = want_s0, (s0.dtype, z.dtype)
+        ctx.save_for_backward(out["dz"], *((out["ds"][0],) if want_s0 else ()))
+        return out["cost"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        dz = ctx.saved_tensors[0]
+        gy = gy.to(dz.device, torch.float32)
+        gz = (gy[None, :, None] * dz).to(ctx.dtypes[1]) if ctx.needs_input_grad[2] else None
+        gs = (gy[:, None] * ctx.saved_tensors[1]).to(ctx.dtypes[0]) if ctx.want_s0 else None
+        return None, gs, gz, None, None, None, None

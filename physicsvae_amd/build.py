@@ -10,7 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpvae_gfx950.so")
 UNITS = ["pvae.hip", "pvae_net.hip", "pvae_step.hip", "pvae_lookahead.hip", "pvae_infer.hip", "pvae_imagine.hip", "pvae_plan.hip",
-         "pvae_exchange.hip", "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip", "pvae_ppo.hip"]
+         "pvae_refine.hip", "pvae_exchange.hip", "pvae_rollout_server.hip", "pvae_probe.hip", "pvae_fc.hip", "pvae_ppo_core.hip",
+         "pvae_ppo.hip"]
 GEMM_HEADERS = ["pvae_gemm_common.h", "pvae_stage.h", "pvae_gemm_src.h", "pvae_gemm_reg.h", "pvae_gemm_ws.h",
                 "pvae_gemm_wgrad.h", "pvae_adam.h", "pvae_gemm_fused.h", "pvae_gemm_epi.h", "pvae_gemm_launch.h"]   # what pvae_gemm.h includes
 HEADERS = ["pvae_internal.h", "pvae_ppo_learner.h", "pvae_gemm.h"] + GEMM_HEADERS + ["pvae_layout.h", "pvae_fc_layout.h"]

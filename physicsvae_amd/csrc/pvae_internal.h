@@ -8,6 +8,8 @@
 //   pvae_infer.hip           rollout and inference, the autograd entry points, the PPO learner's hooks into a stack
 //   pvae_imagine.hip         imagined rollouts: the H-step closed-loop unroll of policy and world model, its hand-over launch
 //   pvae_plan.hip            planning over imagined rollouts: sampled candidate codes, per-row cost in the hand-over, selection
+//   pvae_refine.hip          backpropagation through the unroll (state tape, per-step recompute, the backward hand-over) and
+//                            gradient refinement of a plan: Adam on the codes, keeping the best iterate
 //   pvae_exchange.hip        data-parallel exchange: RCCL calls, the peer-mapped exchange kernels, their set-up and self-test;
 //                            the set-up of the PPO learners' gradient exchange between workers
 //   pvae_rollout_server.hip  the call-persistent rollout server
@@ -580,6 +582,21 @@ struct ImagineIo {
 __device__ inline const float* src_row(const pvae_imagine_src& s, int r, long long t) {
     const long long i = s.row_index ? (long long)s.row_index[r] : (long long)r;
     return s.base + i * s.ld + t * s.step;
+}
+// One row's cost term of step t (plan.py step 3; the hand-overs of pvae_plan.hip and pvae_refine.hip), by ONE wavefront:
+//   sw_t * (sum_c cw[c] * double(d) * double(d)) / Db,   d = s[c] - tg[c] in float,
+// lanes striding the columns, then the xor tree from 32 down: every lane returns the same double.
+__device__ inline double rollout_cost_row(const float* __restrict__ s, const float* __restrict__ tg, const float* __restrict__ cw,
+                                          const float* __restrict__ sw, int t, int Db, int lane) {
+    double acc = 0.0;
+    for (int c = lane; c < Db; c += 64) {
+        const float d = s[c] - tg[c];
+        const double q = (double)d * (double)d;
+        acc += cw ? (double)cw[c] * q : q;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    return (sw ? (double)sw[t] : 1.0) * acc / (double)Db;
 }
 // The panels and sizes of a call on `rows` rows (sources, seed and offset are the caller's to fill in); marks the staging
 // panels as overwritten, as pvae_net_forward does.

@@ -96,12 +96,9 @@ plan_handover_kernel(ImagineIo io, PlanIo p, const float* __restrict__ wm_out, i
     const float* s = wm_out + (size_t)r * ldo_wm;
     const float* tg = src_row(io.targets, r / p.K, t);
     const double j_prev = (lane == 0 && t > 0) ? p.J[r] : 0.0;      // (asked for first: off the reduction's path)
-    double acc = 0.0;
+    const double step = rollout_cost_row(s, tg, p.cw, p.sw, t, Db, lane);      // (pvae_internal.h: shared with pvae_refine.hip)
     for (int c = lane; c < Db; c += 64) {
         const float v = s[c];
-        const float d = v - tg[c];
-        const double q = (double)d * (double)d;
-        acc += p.cw ? (double)p.cw[c] * q : q;
         if (states_out) states_out[(size_t)r * Db + c] = v;
         if (more) {
             if (io.md_body) io.md_in[(size_t)r * io.ld_md + c] = v;
@@ -112,12 +109,7 @@ plan_handover_kernel(ImagineIo io, PlanIo p, const float* __restrict__ wm_out, i
         const float* zr = p.zc + ((size_t)(t + 1) * io.rows + r) * Z;
         for (int c = lane; c < Z; c += 64) io.md_z[(size_t)r * io.ld_md + Db + c] = zr[c];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) {
-        const double step = (p.sw ? (double)p.sw[t] : 1.0) * acc / (double)Db;
-        p.J[r] = j_prev + step;
-    }
+    if (lane == 0) p.J[r] = j_prev + step;
 }
 
 // Selection: one workgroup per environment.  The K costs, rounded once to float, go through LDS (and to `cost`); wave 0

@@ -9,11 +9,14 @@ happens in the library (physicsvae_amd/csrc).  Split by job:
     engine_rollout.py  RolloutClient: infer_host and the rollout server's client
     engine_imagine.py  ImagineSurface: imagine, the H-step closed-loop unroll of policy and world model (pvae_imagine)
     engine_plan.py     PlanSurface: plan, sampled candidate codes over imagined rollouts (pvae_plan)
+    engine_refine.py   RefineSurface: imagine_grad and refine, backpropagation through the unroll and Adam on the codes
+                       (pvae_imagine_grad, pvae_plan_refine)
     engine_ppo.py      PpoSurface: the PPO learner surface both engines inherit, its struct builders, ppo_loss, gae, ppo_order
     stack_set.py       StackSetEngine, set_fc_per_stack
 
-HipEngine = core + DataParallelExchange + RolloutClient + ImagineSurface + PlanSurface + PpoSurface; StackSetEngine = core +
-PpoSurface.  The first six of the other modules stand on `_lib` and torch alone; every name that was importable from here still is.
+HipEngine = core + DataParallelExchange + RolloutClient + ImagineSurface + PlanSurface + RefineSurface + PpoSurface;
+StackSetEngine = core + PpoSurface.  The first seven of the other modules stand on `_lib` and torch alone; every name that
+was importable from here still is.
 """
 import ctypes as C
 
@@ -27,6 +30,7 @@ from .engine_ppo import (PPO_COLUMNS, PpoSurface, evaluate_plan, gae, gae_scratc
                          make_prepared, make_rollout, ppo_loss, ppo_loss_diag, ppo_order, prepare_plan)
 from .engine_imagine import ImagineSurface
 from .engine_plan import PlanSurface
+from .engine_refine import RefineSurface
 from .engine_rollout import RolloutClient
 from .stack_set import StackSetEngine, set_fc_per_stack                                                    # noqa: F401
 
@@ -87,7 +91,7 @@ def make_step_params(lr, adam_t=(1, 1, 1), a_rec=1.0, kl=1.0, s_rec=0.0, cyc=1e-
     return sp
 
 
-class HipEngine(PpoSurface, DataParallelExchange, RolloutClient, ImagineSurface, PlanSurface):
+class HipEngine(PpoSurface, DataParallelExchange, RolloutClient, ImagineSurface, PlanSurface, RefineSurface):
     def __init__(self, arch, max_batch, device="cuda", lookahead=1):
         self.lib = _lib.load()
         self.arch = arch

@@ -228,6 +228,15 @@ def _cur_property(name):
     return property(lambda self: getattr(self._st, name), lambda self, v: setattr(self._st, name, v))
 
 
+def _env_part(x, lo, hi, dim):
+    """Environments [lo, hi) of a dense tensor (environments along `dim`) or of an in-place pair (tensor, row_index[, shift])."""
+    if x is None:
+        return None
+    if isinstance(x, (tuple, list)):
+        return (x[0], x[1][lo:hi].contiguous()) + tuple(x[2:])
+    return x[lo:hi] if dim == 0 else x[:, lo:hi]
+
+
 class PhysicsVAE(PpoPolicy, nn.Module):
     DEFAULT_CONFIG = {
         "project_dir": None,
@@ -986,6 +995,44 @@ class PhysicsVAE(PpoPolicy, nn.Module):
             return outs[0]
         env_dim = {"best": 0, "cost": 0, "a0": 0, "s1": 0}
         return {k: torch.cat([o[k] for o in outs], dim=env_dim.get(k, 1)) for k in outs[0]}
+
+    def imagine_grad(self, s0, z, targets, group=1, col_weight=None, step_weight=None, want=("cost", "dz")):
+        """The planner's rollout cost of the codes z [H, E * group, Z] from s0 [E, Db] against targets [H, E, Db] and its
+        gradient through the decoder, the helper and the world model (`HipEngine.imagine_grad`; the rule: `refine.py`'s
+        module docstring): "cost" [rows], "dz" [H, rows, Z], "ds" [H, rows, Db], "states" [H, rows, Db].  One library call
+        per chunk of floor(max_batch / group) environments; the chunks are independent and nothing is drawn, so `_rng_calls`
+        stays where it is.  The model's parameters get no gradient."""
+        from .refine import refine_chunks
+        eng, G = self.engine, int(group)
+        E = int(s0[1].shape[0] if isinstance(s0, (tuple, list)) else s0.shape[0])
+        outs = [eng.imagine_grad(_env_part(s0, lo, hi, 0), z[:, lo * G: hi * G], _env_part(targets, lo, hi, 1), group=G,
+                                 col_weight=col_weight, step_weight=step_weight, want=want)
+                for lo, hi in refine_chunks(E, G, eng.max_batch)]
+        if len(outs) == 1:
+            return outs[0]
+        return {k: torch.cat([o[k] for o in outs], dim=0 if k == "cost" else 1) for k in outs[0]}
+
+    def imagine_cost(self, s0, z, targets, group=1, col_weight=None, step_weight=None):
+        """cost [rows] of `imagine_grad` as a differentiable torch value (`autograd.HipImagineCost`): its backward gives
+        `z.grad` and, with group == 1, `s0.grad`.  The model's parameters get no gradient -- every stack is frozen here; a
+        caller that wants to train through the unroll composes the stage functions instead."""
+        return AG.HipImagineCost.apply(self, s0, z, targets, int(group), col_weight, step_weight)
+
+    def refine(self, s0, targets, horizon, steps, lr, nominal=None, col_weight=None, step_weight=None,
+               want=("plan_z", "cost", "best_iter", "iter_cost", "a0", "s1")):
+        """Gradient refinement of a latent plan (`HipEngine.refine`; the rule: `refine.py`'s module docstring): `steps` Adam
+        steps on the codes of every environment from `nominal` [H, E, Z] (None: zeros; typically `plan`'s "plan_z"),
+        keeping the best iterate, so the returned "cost" is never above the nominal's.  One library call per chunk of
+        `max_batch` environments; nothing is drawn and `_rng_calls` stays where it is."""
+        eng = self.engine
+        E = int(s0[1].shape[0] if isinstance(s0, (tuple, list)) else s0.shape[0])
+        outs = [eng.refine(_env_part(s0, lo, hi, 0), _env_part(targets, lo, hi, 1), horizon, steps, lr,
+                           nominal=_env_part(nominal, lo, hi, 1), col_weight=col_weight, step_weight=step_weight, want=want)
+                for lo, hi in AG.chunks(E, eng.max_batch)]
+        if len(outs) == 1:
+            return outs[0]
+        env_dim = {"cost": 0, "best_iter": 0, "a0": 0, "s1": 0, "iter_cost": 1, "plan_z": 1, "grad": 1, "z_iters": 2}
+        return {k: torch.cat([o[k] for o in outs], dim=env_dim[k]) for k in outs[0]}
 
     def set_exploration_std(self, std):
         self._motor_decoder._model[-1].set_val(float(np.log(std)))

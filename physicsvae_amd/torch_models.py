@@ -335,14 +335,18 @@ class TrainModel(tune.Trainable):
             total += out["err"].double() * float(idx.numel())
         return {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
 
-    def evaluate_plan(self, horizon, candidates, iters=1, sigma=1.0, lam=0.0, data="train", max_windows=None):
+    def evaluate_plan(self, horizon, candidates, iters=1, sigma=1.0, lam=0.0, data="train", max_windows=None, refine_steps=0,
+                      refine_lr=0.05):
         """How closely a PLANNED code sequence follows the demonstration: per window start, `HipEngine.plan` against the
         demonstrated next states (read where the set lies on the device, as `evaluate_rollout` reads them), then the plan
         replayed open loop through one `imagine` prior-mode call with z = plan_z and the same targets.  Returns
         {"horizon_mse": [H floats]}, the per-horizon mean squared error of the planned rollout over all windows, to be set
         beside `evaluate_rollout`'s; one host synchronisation, at the end.  Chunk i, iteration j, step t draws at
-        ROLLOUT_RNG_OFFSET + (i * iters + j) * horizon + t of the trainer's seed, rows numbered globally.  Not part of
-        `step()`."""
+        ROLLOUT_RNG_OFFSET + (i * iters + j) * horizon + t of the trainer's seed, rows numbered globally.  With
+        `refine_steps` > 0 the planned codes go through `HipEngine.refine` (that many Adam steps at `refine_lr`, the best
+        iterate kept) before the rollout that is scored, and the result also holds, per window, "window_cost" (the refined
+        plan's cost J) and "window_cost_unrefined" (the sampled plan's: never below the refined one); with the default 0 the
+        call is what it was.  Not part of `step()`."""
         from .plan import plan_chunks
         loader = {"train": self.train_loader, "test": self.test_loader}[data]
         if not loader:
@@ -354,13 +358,22 @@ class TrainModel(tune.Trainable):
         states = loader.dataset.device_arrays(eng.device)[0]
         index = torch.from_numpy(starts).to(eng.device)
         total = torch.zeros(H, dtype=torch.float64, device=eng.device)
+        refined, unrefined = [], []
         for i, (lo, hi, row0) in enumerate(plan_chunks(len(starts), K, eng.max_batch)):
             idx = index[lo:hi].contiguous()
             p = eng.plan((states, idx), (states, idx, 1), H, K, iters=iters, sigma=sigma, lam=lam, seed=self.rng_seed,
                          offset=self.ROLLOUT_RNG_OFFSET + i * iters * H, row0=row0, want=("plan_z",))
+            if int(refine_steps) > 0:
+                p = eng.refine((states, idx), (states, idx, 1), H, int(refine_steps), float(refine_lr), nominal=p["plan_z"],
+                               want=("plan_z", "cost", "iter_cost"))
+                refined.append(p["cost"])
+                unrefined.append(p["iter_cost"][0])
             out = eng.imagine("prior", (states, idx), H, z=p["plan_z"], targets=(states, idx, 1), want=())
             total += out["err"].double() * float(idx.numel())
-        return {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
+        res = {"horizon_mse": (total / float(len(starts))).cpu().tolist()}
+        if refined:
+            res["window_cost"], res["window_cost_unrefined"] = torch.cat(refined).cpu().tolist(), torch.cat(unrefined).cpu().tolist()
+        return res
 
     # -- the hot loop ---------------------------------------------------------------------
     def phase(self):
